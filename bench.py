@@ -8,7 +8,14 @@ EKF update; reference reflector_ekf_slam.cc:229-309) on a filter whose covarianc
 path) runs untimed before it.  Inputs per step are the scan's 32 float32 points,
 passed by value with the launch; nothing else crosses PCIe in the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: build the session and the map, W warm-up steps, K timed
+steps, and one JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+`--dump-outputs DIR` then writes what a caller of the timed path holds after its last step -- the state
+(time, mu, sigma) and the last scan's association lists -- as DIR/<name>.npy in float64; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.  Everything else
+the line can carry (the parity figure per rank and the extra objects below) is measured with `--full`.
 
 `--gpus N` with N > 1 and no torchrun environment re-executes itself under
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU over RCCL);
@@ -18,7 +25,7 @@ data-path collective: a start barrier, MAX over ranks of the elapsed time and on
 all-gather of a 64-byte result record per rank (reflector_ekf_slam_amd/dist.py).
 Rank 0 prints ONE JSON line.
 
-Extra objects on that line (rank 0, N = 1 unless noted):
+Extra objects on that line with --full (rank 0, N = 1 unless noted):
   roofline       the update's ONE launch, k_mid<4, 0>: the scan's mid role (a latency chain), the previous scan's downdate P -= K (H P) as a
                  role beside it (the HBM / MFMA work) and the next scan's speculative front end.  `frac` / `achieved` / `mfma.frac` are over
                  the launch's average duration measured in this run (the update period of an un-instrumented window); P is stored as its LOWER
@@ -46,8 +53,8 @@ Extra objects on that line (rank 0, N = 1 unless noted):
                  scan and HandlePointCloud on a 28.8 k-point sweep -- call us (median / p99, host buffers in, centres
                  out: PCIe inclusive), input bytes / call time in GB/s, and the CPU oracle's time for the same inputs
                  (part of the CPU-baseline leg: skipped with --no-cpu-baseline).
-  ranks          per-rank updates/s: min / median / max, and every rank's parity figure -- max |mu - oracle| over
-                 `--rank-parity-steps` updates run AFTER the timed region, oracle started from the rank's own state.
+  ranks          per-rank updates/s: min / median / max (also on a plain run), and every rank's parity figure -- max |mu - oracle|
+                 over `--rank-parity-steps` updates run AFTER the timed region, oracle started from the rank's own state.
 """
 from __future__ import annotations
 
@@ -101,7 +108,15 @@ def parse_args(argv=None):
     ap.add_argument("--timed-only", action="store_true",
                     help="map build, warm-up and the timed steps only (no instrumented legs): what scripts/gpu_profile_round.sh "
                          "runs under rocprofv3, so that the LAST dispatches of every kernel are the timed region's")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-rank parity figure and the instrumented legs (roofline, latency, CPU baseline, secondary configs, "
+                         "multi_session, detectors, ...); a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def config_by_name(name):
@@ -194,6 +209,30 @@ def rank_parity(cfg, sess, ekf, scans):
     return float(np.abs(ekf.mu() - o.mu()).max()), same
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ekf, out_dir):
+    """--dump-outputs: what a caller of the timed path (HandleObservationMessage) holds after its last step -- GetState's time, mu and
+    sigma and the last scan's ReflectorMatchResult -- as out_dir/<name>.npy, float64 (the int index lists are exact in it).  No file is
+    empty: `match_counts` holds the lengths of the three association lists, and a list is written only when it has entries (in the
+    steady state no reflector is new, and a session without a pre-loaded map matches none against one)."""
+    st = ekf.GetState()
+    mm = ekf.last_match()
+    sp, mp, nw = mm if isinstance(mm, tuple) else (mm.state_obs_match_ids, mm.map_obs_match_ids, mm.new_ids)
+    lists = {"state_obs_match_ids": np.asarray(sp).reshape(-1, 2), "map_obs_match_ids": np.asarray(mp).reshape(-1, 2),
+             "new_ids": np.asarray(nw).reshape(-1)}
+    arrays = {"time": [st.time], "mu": st.mu, "sigma": st.sigma, "match_counts": [len(v) for v in lists.values()]}
+    arrays.update({k: v for k, v in lists.items() if len(v)})
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def run_rank(args, dist_mod, rank, local_rank, world, make_filter=gpu_filter_factory, device_sync=lambda: None,
              full=True):
     """One rank's share of the bench.  `full` = also the rank-0 instrumented legs that need the HIP handle."""
@@ -215,7 +254,9 @@ def run_rank(args, dist_mod, rank, local_rank, world, make_filter=gpu_filter_fac
     if n != n_expect:
         raise SystemExit(f"warm-up ended with n={n}, expected {n_expect}")
 
-    n_extra = 16 + 3 * max(args.latency_steps, 0) + 700 + max(args.instr_steps, 0) + 2 * max(args.steps, 200) + max(args.rank_parity_steps, 0) + 700
+    n_extra = 0
+    if args.full:         # (the first warmup + steps scans are the same whatever the count: one seeded stream)
+        n_extra = 16 + 3 * max(args.latency_steps, 0) + 700 + max(args.instr_steps, 0) + 2 * max(args.steps, 200) + max(args.rank_parity_steps, 0) + 700
     steady = synth.steady_state_scans(sess, args.warmup + args.steps + n_extra)
     m = 2 * steady[0][1].shape[0]
 
@@ -226,9 +267,12 @@ def run_rank(args, dist_mod, rank, local_rank, world, make_filter=gpu_filter_fac
     nw = mm[2] if isinstance(mm, tuple) else mm.new_ids
     assert len(nw) == 0 and len(sp) == m // 2, "not steady state"
     assert ekf.n == n_expect
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(ekf, args.dump_outputs)
     # every rank, after the timed region: its own parity figure (the gloo CPU test drives this function with an oracle stub: nothing to compare)
     err, assoc_ok = float("nan"), True
-    if args.rank_parity_steps > 0 and hasattr(ekf, "GetState"):
+    ran_parity = args.full and args.rank_parity_steps > 0 and hasattr(ekf, "GetState")
+    if ran_parity:
         err, assoc_ok = rank_parity(cfg, sess, ekf, steady[used:used + args.rank_parity_steps])
         used += args.rank_parity_steps
     mu = ekf.mu()
@@ -259,10 +303,11 @@ def run_rank(args, dist_mod, rank, local_rank, world, make_filter=gpu_filter_fac
                   "updates_per_s_max": rates[-1], "final_n": [int(r["final_n"]) for r in recs],
                   "seeds": [int(r["seed"]) for r in recs],
                   "max_abs_err_vs_oracle": [None if r["max_abs_err"] != r["max_abs_err"] else float(r["max_abs_err"]) for r in recs],
-                  "parity_note": f"per rank: max |mu - CPU oracle| after {args.rank_parity_steps} updates replayed by both from the rank's own "
-                                 "state behind the timed region (inf: an association list differed; null: not run)"},
+                  "parity_note": (f"per rank: max |mu - CPU oracle| after {args.rank_parity_steps} updates replayed by both from the rank's own "
+                                  "state behind the timed region (inf: an association list differed; null: not run)") if ran_parity else
+                                 "not measured: the parity replay runs with --full"},
     }
-    if not full or args.timed_only:
+    if not full or not args.full or args.timed_only:
         return out
     rest = steady[used:]
     out.update(instrumented_legs(args, base, cfg, sess, ekf, rest, n, m, local_rank, world, chain_us=1e6 * elapsed / args.steps))

@@ -5,7 +5,7 @@
 # 2./3. two SEPARATE --pmc passes (FETCH_SIZE, WRITE_SIZE) with --kernel-trace only, as the MI355X guide prescribes;
 # 4. a third --pmc pass: SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE (counter-based MFMA utilisation);
 # 5. the detectors: call latencies, --kernel-trace --stats, the two --pmc passes (scripts/gpu_bench_detectors.py);
-# 6. the bench lines (driver command and default) of the same tree.
+# 6. the bench lines (driver command and default, both --full) of the same tree.
 # Summaries are written HERE (the databases are too big to travel) into gpurun_out/profiles_<tag>/; the builder runs
 # `python scripts/profiles_commit.py <tag> <commit>` to move them into profiles/ and rewrite profiles/MANIFEST.json.
 TAG=${1:-x}; COMMIT=${2:-unknown}; STEPS=${3:-1000}
@@ -31,7 +31,7 @@ python scripts/pmc_detectors.py gpurun_out/prof_det_fetch/fetch_results.db gpuru
 head -14 $OUT/${TAG}_detectors_kernel_stats.txt | cut -c1-130
 rm -rf gpurun_out/prof_det gpurun_out/prof_det_fetch gpurun_out/prof_det_write
 # ---- bench lines of the same tree
-python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${TAG}_bench_driver_cmd.json
-python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench_default.json
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${TAG}_bench_driver_cmd.json
+python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_default.json
 cut -c1-260 $OUT/${TAG}_bench_driver_cmd.json; echo; cut -c1-260 $OUT/${TAG}_bench_default.json; echo
 ls -la $OUT

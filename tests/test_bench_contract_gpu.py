@@ -1,11 +1,12 @@
 """bench.py's one-line JSON contract (the driver parses it): required keys, types, the roofline / cpu_baseline objects.
-The first test runs the DRIVER'S EXACT COMMAND (`--gpus 1 --steps 20 --warmup 5`): round 1's cpu_baseline was empty at
-exactly that setting, so every object on the line is checked there."""
+The driver's command (`--gpus 1 --steps 20 --warmup 5`) is a plain run: the headline only, and --dump-outputs.  With --full at
+exactly that setting (round 1's cpu_baseline was empty there) every object on the line is checked."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,14 +22,19 @@ def _run(*extra, env=None):
     return json.loads(lines[0])
 
 
-def _check_contract(d, steps, warmup):
+def _check_headline(d, steps, warmup):
     for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int), ("ms_per_step", float),
-                 ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict), ("roofline", dict)):
+                 ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict)):
         assert isinstance(d[k], t), (k, d[k])
     assert d["vs_baseline"] is None and d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup and d["higher_is_better"] is True
     assert d["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
-    assert d["dtype"] == "f64" and d["scaling"] == "weak" and "workload" in d["config"]
+    assert d["dtype"] == "f64" and d["scaling"] == "weak" and "workload" in d["config"] and d["unit"] == "updates/s"
     assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+
+
+def _check_contract(d, steps, warmup):
+    _check_headline(d, steps, warmup)
+    assert isinstance(d["roofline"], dict)
     r = d["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "avg_launch_us_method"):
         assert k in r
@@ -56,8 +62,32 @@ def _check_contract(d, steps, warmup):
     assert 0 <= pl["of_those_computing_its_correction_themselves"] <= pl["scans_beside_a_pending_downdate"]
 
 
+def test_driver_command_is_lean_and_dumps_its_outputs(tmp_path):
+    """The plain run: the headline, no instrumented leg, and --dump-outputs writes the state and the association lists the last timed
+    step left, the same on every run with the same arguments."""
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out))
+        _check_headline(d, 20, 5)
+        assert d["value"] > 5000
+        for leg in ("roofline", "pipeline", "latency_us", "cpu_baseline", "secondary", "multi_session", "detectors", "not_full", "kernel_us"):
+            assert leg not in d, leg
+        assert d["ranks"]["final_n"] == [2051] and d["ranks"]["max_abs_err_vs_oracle"] == [None]
+        assert d["ranks"]["parity_note"].startswith("not measured")
+        arrs = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert set(arrs) == {"time", "mu", "sigma", "match_counts", "state_obs_match_ids"}    # (no new reflector, no pre-loaded map)
+        assert all(a.dtype == np.float64 and a.size > 0 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["mu"].shape == (2051,) and arrs["sigma"].shape == (2051, 2051) and arrs["time"].shape == (1,)
+        assert arrs["state_obs_match_ids"].shape == (32, 2) and arrs["match_counts"].tolist() == [32, 0, 0]
+        assert np.all(np.isfinite(arrs["sigma"])) and np.all(np.diag(arrs["sigma"]) > 0)
+        runs.append(arrs)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+
+
 def test_driver_command_steps20_warmup5_has_every_object():
-    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5")
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--full")
     _check_contract(d, 20, 5)
     c = d["cpu_baseline"]
     for k in ("value", "unit", "cores", "kind", "sample"):
@@ -102,7 +132,7 @@ def test_driver_command_steps20_warmup5_has_every_object():
 
 
 def test_bench_light_run_steps200():
-    d = _run("--steps", "200", "--warmup", "20", "--no-cpu-baseline", "--multi-sessions", "0", "--secondary", "", "--latency-steps", "0")
+    d = _run("--full", "--steps", "200", "--warmup", "20", "--no-cpu-baseline", "--multi-sessions", "0", "--secondary", "", "--latency-steps", "0")
     _check_contract(d, 200, 20)
     assert "cpu_baseline" not in d and "secondary" not in d and "latency_us" not in d
     assert "cpu_oracle_us" not in d["detectors"]["cloud_3d"]                    # the oracle is only timed in the CPU-baseline leg
@@ -111,7 +141,7 @@ def test_bench_light_run_steps200():
 def test_rccl_path_at_world_size_one():
     """The collectives of the session-per-GPU harness on the ONE GPU there is (no 8-GPU node is reachable from the builder): process
     group "nccl" (= RCCL) with device_id, barrier, all_reduce(MAX) of a cuda float64, all_gather of the 64-byte records."""
-    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--secondary", "", "--multi-sessions", "0",
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--secondary", "", "--multi-sessions", "0",
              "--latency-steps", "0", "--detector-reps", "0", env={"REKF_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29541"})
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["dist_backend"] == "nccl"
     r = d["ranks"]

@@ -182,7 +182,7 @@ class Stub:
     n = property(lambda self: self.o.n)
 
 dist, rank, local_rank, world = D.init("gloo")
-args = bench.parse_args(["--gpus", "2", "--config", "T0", "--steps", "7", "--warmup", "3"])
+args = bench.parse_args(["--gpus", "2", "--config", "T0", "--steps", "7", "--warmup", "3", "--full"])
 out = bench.run_rank(args, dist, rank, local_rank, world, make_filter=Stub, full=False)
 if rank == 0:
     assert out["n_gpus"] == 2 and out["steps"] == 7 and out["warmup"] == 3 and out["scaling"] == "weak"
@@ -214,6 +214,58 @@ def test_bench_rank_function_over_gloo_world_size_2(tmp_path, oracle_lib):
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "BENCH_GLOO_OK" in out.stdout
+
+
+class _OracleFilter:
+    """The CPU oracle behind the snake_case filter interface bench.run_rank drives (test only)."""
+    def __init__(self, cfg, sess, device):
+        from oracle.binding import OracleEKF
+        self.o = OracleEKF(cfg.odom_model, sess.init_time, sess.init_pose, cfg.sigma_v ** 2, cfg.sigma_w ** 2, cfg.sigma_obs ** 2)
+    def handle_odometry(self, *a): self.o.handle_odometry(*a)
+    def handle_observation(self, *a): self.o.handle_observation(*a)
+    def sync(self): pass
+    def mu(self): return self.o.mu()
+    def last_match(self): return self.o.last_match()
+    def GetState(self):
+        from types import SimpleNamespace
+        mu, P = self.o.state()
+        return SimpleNamespace(time=self.o.time, mu=mu, sigma=P)
+    n = property(lambda self: self.o.n)
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path, oracle_lib):
+    """A plain run (no --full): the timed steps and the headline only -- no parity replay behind them -- and --dump-outputs holds the
+    state and the association lists the LAST timed step left: the same as a --full run's, and as a replay of warmup + steps scans."""
+    import numpy as np
+    import bench
+    from reflector_ekf_slam_amd import session as S
+    from reflector_ekf_slam_amd import synth
+    dumps = {}
+    for mode in ("plain", "full"):
+        argv = ["--config", "T0", "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path / mode)] + (["--full"] if mode == "full" else [])
+        out = bench.run_rank(bench.parse_args(argv), None, 0, 0, 1, make_filter=_OracleFilter, full=False)
+        assert out["steps"] == 7 and out["warmup"] == 3 and abs(out["ms_per_step"] - 1e3 / out["value"]) < 1e-9 * out["ms_per_step"]
+        assert out["ranks"]["max_abs_err_vs_oracle"] == ([None] if mode == "plain" else [0.0])
+        assert out["ranks"]["parity_note"].startswith("not measured" if mode == "plain" else "per rank: max |mu - CPU oracle| after 20 updates")
+        dumps[mode] = {f[:-4]: np.load(tmp_path / mode / f) for f in os.listdir(tmp_path / mode)}
+    assert set(dumps["plain"]) == {"time", "mu", "sigma", "match_counts", "state_obs_match_ids"}
+    assert set(dumps["full"]) == set(dumps["plain"])
+    for k, a in dumps["plain"].items():
+        assert a.dtype == np.float64 and a.size > 0 and np.array_equal(a, dumps["full"][k]), k
+    assert dumps["plain"]["match_counts"].tolist() == [dumps["plain"]["state_obs_match_ids"].shape[0], 0, 0]
+    base, cfg, sess = bench.build_session("T0", 0, 1)
+    f = _OracleFilter(cfg, sess, 0)
+    S.replay(sess, f)
+    for t, ob in synth.steady_state_scans(sess, 10):
+        f.handle_observation(t, ob)
+    assert np.array_equal(dumps["plain"]["mu"], f.mu()) and dumps["plain"]["sigma"].shape == (27, 27)
+    assert np.array_equal(dumps["plain"]["state_obs_match_ids"], np.asarray(f.last_match()[0], np.float64).reshape(-1, 2))
+
+
+def test_bench_rejects_a_step_count_below_one():
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
 
 
 def test_bench_gpus_flag_respawns_under_torchrun(monkeypatch):
