@@ -231,6 +231,111 @@ def steady_state_scans(session: Session, n: int, seed_offset: int = 1000) -> lis
     return out
 
 
+MOVING_PATTERNS = ("twist", "odom50")
+
+
+def moving_scans(session: Session, n: int, pattern: str = "twist", seed_offset: int = 3000) -> Session:
+    """``n`` scans of the robot MOVING through the completed map, from the session's final true pose (the middle of
+    the field), as an event stream of its own: a ``Session`` whose ``init_time`` / ``init_pose`` are that pose and time
+    and whose events all lie after them (replay it with ``drop_first_scan=False``).  Each scan holds the
+    ``obs_per_scan`` nearest reflectors inside ``[range_min, range_max]`` of the true pose at scan time, in bearing
+    order, with ``obs_noise``, float32 -- as ``steady_state_scans`` -- drawn only from reflectors the session itself
+    observed after its first (dropped) scan, so that a filter that ran the session augments nothing.
+
+    ``twist``: ONE odometry message (v = 0.5 m/s, w = 0.2 rad/s, noise-free) 10 ms after the start, then scans only at
+    ``scan_hz``: the robot drives the constant-twist circle (r = v / w = 2.5 m) a filter predicts from that message, and
+    every scan can ride the speculation pipeline.
+    ``odom50``: odometry at ``odom_hz`` between the scans (each scan 10 ms after the last of its messages), v = 0.5 m/s
+    and w = +-0.2 rad/s flipping sign every 5 s, with the configuration's velocity noise on the messages.
+    Such a slalom drifts 0.48 m/s along its mean heading and would leave the field within 1000 scans: the robot
+    drives it forward for 50 s and in reverse for the next 50 s (same w schedule), which brings it back to its start
+    every 100 s -- a closed loop of at most 24 m out."""
+    if pattern not in MOVING_PATTERNS:
+        raise ValueError(f"pattern must be one of {MOVING_PATTERNS}")
+    cfg = session.config
+    rng = np.random.Generator(np.random.PCG64(cfg.seed + seed_offset))
+    lms = session.landmarks
+    scans = session.scan_indices()
+    seen = np.unique(session.obs_truth_id[session.obs_off[scans[1]]:]) if scans.size > 1 else np.zeros(0, np.int64)
+    known = lms[seen]
+    pose0 = session.true_pose[-1].astype(np.float64).copy()
+    t0 = float(session.ev_time[-1]) if session.n_events else 0.0
+    dt_scan = 1.0 / cfg.scan_hz
+
+    def observe(pose):
+        rel = known - pose[:2]
+        dist = np.hypot(rel[:, 0], rel[:, 1])
+        cand = np.nonzero((dist >= cfg.range_min) & (dist <= cfg.range_max))[0]
+        cand = cand[np.argsort(dist[cand], kind="stable")][: cfg.obs_per_scan]
+        c, sn = math.cos(pose[2]), math.sin(pose[2])
+        rx = c * rel[cand, 0] + sn * rel[cand, 1]
+        ry = -sn * rel[cand, 0] + c * rel[cand, 1]
+        order = np.argsort(np.arctan2(ry, rx), kind="stable")
+        cand, rx, ry = cand[order], rx[order], ry[order]
+        meas = np.stack([rx, ry], -1) + rng.normal(0, cfg.obs_noise, size=(cand.size, 2))
+        return meas.astype(np.float32), seen[cand].astype(np.int32)
+
+    def wrap(a):
+        return math.atan2(math.sin(a), math.cos(a))
+
+    ev_type, ev_time, odom, true_pose, obs_chunks, id_chunks = [], [], [], [], [], []
+
+    def odometry(t, u, pose):
+        ev_type.append(EV_ODOM); ev_time.append(t); odom.append(u); true_pose.append(pose.copy())
+        obs_chunks.append(np.zeros((0, 2), np.float32)); id_chunks.append(np.zeros(0, np.int32))
+
+    def scan(t, pose):
+        meas, ids = observe(pose)
+        ev_type.append(EV_SCAN); ev_time.append(t); odom.append((0.0, 0.0, 0.0)); true_pose.append(pose.copy())
+        obs_chunks.append(meas); id_chunks.append(ids)
+
+    if pattern == "twist":
+        v, w = 0.5, 0.2
+
+        def on_circle(tau):                   # the exact constant-twist pose tau seconds after the start
+            th = pose0[2] + w * tau
+            return np.array([pose0[0] + v / w * (math.sin(th) - math.sin(pose0[2])),
+                             pose0[1] - v / w * (math.cos(th) - math.cos(pose0[2])), wrap(th)])
+
+        odometry(t0 + 0.01, (v, 0.0, w), on_circle(0.01))
+        for k in range(1, n + 1):
+            scan(t0 + k * dt_scan, on_circle(k * dt_scan))
+    else:
+        dt = 1.0 / cfg.odom_hz
+        per_scan = int(round(cfg.odom_hz / cfg.scan_hz))
+        flip, shuttle = int(round(5.0 / dt)), int(round(50.0 / dt))      # odometry periods per w sign / per driving direction
+        pose = pose0.copy()
+
+        def step(p, v, w, h):                 # the integrator the filter linearises (DIFF, cc:156-183)
+            half = p[2] + w * h / 2
+            q = p + np.array([v * h * math.cos(half), v * h * math.sin(half), w * h])
+            q[2] = wrap(q[2])
+            return q
+
+        j = 0
+        for k in range(1, n + 1):
+            for _ in range(per_scan):
+                v = 0.5 if (j // shuttle) % 2 == 0 else -0.5
+                w = 0.2 if (j // flip) % 2 == 0 else -0.2
+                pose = step(pose, v, w, dt)
+                j += 1
+                odometry(t0 + j * dt, (v + rng.normal(0, cfg.sigma_v), 0.0, w + rng.normal(0, cfg.sigma_w)), pose)
+            v = 0.5 if (j // shuttle) % 2 == 0 else -0.5          # the command of the interval the scan falls into
+            w = 0.2 if (j // flip) % 2 == 0 else -0.2
+            scan(t0 + j * dt + 0.01, step(pose, v, w, 0.01))
+
+    sizes = np.array([c.shape[0] for c in obs_chunks], np.int64)
+    return Session(
+        config=cfg, landmarks=lms, init_pose=pose0, init_time=t0,
+        ev_type=np.array(ev_type, dtype=np.uint8), ev_time=np.array(ev_time, dtype=np.float64),
+        odom=np.array(odom, dtype=np.float64).reshape(-1, 3),
+        obs_off=np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
+        obs=np.concatenate(obs_chunks).astype(np.float32), obs_truth_id=np.concatenate(id_chunks).astype(np.int32),
+        true_pose=np.array(true_pose, dtype=np.float64).reshape(-1, 3),
+        meta={"pattern": pattern, "n_scans": n, "seed_offset": seed_offset},
+    )
+
+
 # ---------------------------------------------------------------------------------------------
 # raw sensor synthesis for the detector paths (SURVEY.md 8(d): "2D-detect variant")
 # ---------------------------------------------------------------------------------------------

@@ -255,7 +255,8 @@ def test_heading_at_the_wrap_and_observations_on_the_gate(oracle_lib, seed):
 # ---------------------------------------------------------------------------------------------- C3 at full size
 def test_c3_500_steady_state_updates_match_the_structured_oracle(oracle_lib):
     """BASELINE.json configs[2] at full size: 500 consecutive steady-state updates against the oracle from the same state --
-    associations every scan, the mean every 25.  (Since round 5 the steady-state chain of a full filter is ONE launch per update,
+    associations and the mean every 25 (and the first three) in this call pattern, and every scan through a reading twin the sampled run
+    must end on.  (Since round 5 the steady-state chain of a full filter is ONE launch per update,
     k_mid<4, 0>: the scan's mid role, the previous scan's downdate role over all tile classes and the next scan's speculative front
     end; the scans whose pose is read back here go out as k_front_mb + the same launch.)"""
     from reflector_ekf_slam_amd import session as S
@@ -270,9 +271,13 @@ def test_c3_500_steady_state_updates_match_the_structured_oracle(oracle_lib):
     vt = sess.odom[np.nonzero(sess.ev_type == synth.EV_ODOM)[0][-1]]
     o.set_state(st.time, st.mu, st.sigma, vt)
     worst = 0.0
-    for k, (t, ob) in enumerate(synth.steady_state_scans(sess, 500)):
+    scans = synth.steady_state_scans(sess, 500)
+    o_match, o_mu = [], []
+    for k, (t, ob) in enumerate(scans):
         g.handle_observation(t, ob)
         o.handle_observation(t, ob)
+        o_match.append(norm_match(o.last_match()))
+        o_mu.append(o.mu())
         if k % 25 == 24 or k < 3:
             assert _same_match(g, o), f"association differs at update {k}"
             worst = max(worst, float(np.abs(g.mu() - o.mu()).max()))
@@ -282,6 +287,26 @@ def test_c3_500_steady_state_updates_match_the_structured_oracle(oracle_lib):
     mo, Po = o.state()
     assert np.abs(st2.mu - mo).max() < TIGHT and np.abs(st2.sigma - Po).max() < 1e-11     # (measured: 2.6e-10 m, 1.5e-12 after 500 updates)
     assert np.array_equal(st2.sigma, st2.sigma.T) and g.sync_code() == 0
+    # every scan: a reading twin through the same map build reads the match record and the mean after EVERY update and is compared
+    # with the oracle there (reading changes the launch path: the sampled run above cannot read more often without testing something
+    # else); the sampled run must end on the twin, so one different association anywhere in it shows up here
+    tw = make_gpu(cfg.odom_model, sess.init_time, sess.init_pose, cfg.sigma_v ** 2, cfg.sigma_w ** 2, cfg.sigma_obs ** 2,
+                  cfg.n_landmarks)
+    S.replay(sess, tw)
+    st_tw = tw.GetState()
+    assert np.array_equal(st_tw.mu, st.mu) and np.array_equal(st_tw.sigma, st.sigma)
+    for k, (t, ob) in enumerate(scans):
+        tw.handle_observation(t, ob)
+        m = norm_match(tw.last_match())
+        assert all(np.array_equal(a, b) for a, b in zip(m, o_match[k])), f"association differs at update {k} (reading twin)"
+        assert np.abs(tw.mu() - o_mu[k]).max() < TIGHT, f"mean differs at update {k} (reading twin)"
+    fin = tw.GetState()
+    assert tw.sync_code() == 0
+    # (a different association anywhere would move landmark means by millimetres; the reads themselves leave round-off between the
+    # two: scans that follow a scan without a pose read-back are device-predicted, and there reading or not is not bit-neutral)
+    d_mu, d_sig = float(np.abs(fin.mu - st2.mu).max()), float(np.abs(fin.sigma - st2.sigma).max())
+    print(f"sampled run vs reading twin: |d mu| {d_mu:.3e} |d sigma| {d_sig:.3e}")
+    assert fin.mu.shape == st2.mu.shape and d_mu < TIGHT and d_sig < 1e-11, f"the sampled run left its reading twin: {d_mu:.3e}"
 
 
 def test_c3_map_build_checkpoints_match_the_oracle(oracle_lib):

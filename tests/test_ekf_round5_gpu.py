@@ -77,7 +77,9 @@ def test_speculative_match_gives_the_exact_matchs_bits_gate_cases_included(oracl
 def test_the_deployed_default_at_full_size_in_both_call_patterns(oracle_lib):
     """BASELINE.json configs[2] with the wrapper defaults -- auto_grow on, initial capacity 64 (it doubles its way to >= 1024 reflectors) --
     built through the reference's own map build, then 300 steady-state updates with the pose read back after every scan (the reference
-    node's pattern, src/ros_node.cc:514-515) and 300 scan after scan: associations identical, |mu - oracle| < 1e-9, sigma to 1e-11."""
+    node's pattern, src/ros_node.cc:514-515) and 300 scan after scan: associations identical, |mu - oracle| < 1e-9, sigma to 1e-11.
+    Associations are sampled in these call patterns (every 20th / 50th update); a reading twin checks every update, and the sampled
+    run must end on its state."""
     from reflector_ekf_slam_amd import ReflectorEKFSLAM
     from reflector_ekf_slam_amd import session as S
     cfg = synth.C3
@@ -90,18 +92,24 @@ def test_the_deployed_default_at_full_size_in_both_call_patterns(oracle_lib):
     vt = sess.odom[np.nonzero(sess.ev_type == synth.EV_ODOM)[0][-1]]
     o.set_state(st.time, st.mu, st.sigma, vt)
     scans = synth.steady_state_scans(sess, 600)
+    o_match, o_mu, poses = [], [], []
     worst = 0.0
     for k, (t, ob) in enumerate(scans[:300]):                              # the node's pattern
         g.handle_observation(t, ob)
         o.handle_observation(t, ob)
-        pose = g.pose()[1]
-        worst = max(worst, float(np.abs(pose - o.mu()[:3]).max()))
+        o_match.append(norm_match(o.last_match()))
+        o_mu.append(o.mu())
+        p = g.pose()
+        poses.append(p)
+        worst = max(worst, float(np.abs(p[1] - o.mu()[:3]).max()))
         if k % 20 == 0:
             assert _same_match(g, o), f"association differs at update {k} (read-back pattern)"
     assert worst < TIGHT
     for k, (t, ob) in enumerate(scans[300:]):                              # scan after scan
         g.handle_observation(t, ob)
         o.handle_observation(t, ob)
+        o_match.append(norm_match(o.last_match()))
+        o_mu.append(o.mu())
         if k % 50 == 49:
             assert _same_match(g, o), f"association differs at update {k} (pipelined)"
             assert np.abs(g.mu() - o.mu()).max() < TIGHT
@@ -111,6 +119,30 @@ def test_the_deployed_default_at_full_size_in_both_call_patterns(oracle_lib):
     mo, Po = o.state()
     assert st2.mu.shape == mo.shape and np.abs(st2.mu - mo).max() < TIGHT and np.abs(st2.sigma - Po).max() < 1e-11
     assert g.sync_code() == 0 and g.flags() == 0
+    # every scan, both halves: a reading twin through the same map build reads the match record and the mean after EVERY update (and the
+    # pose where the run above reads it: a read-back makes the next scan host-predicted) and is compared with the oracle there;
+    # the sampled run must read the twin's poses and end on its state, so one different association anywhere in it shows up here
+    tw = ReflectorEKFSLAM(S.options_for(sess), max_landmarks=64)
+    S.replay(sess, tw)
+    st_tw = tw.GetState()
+    assert np.array_equal(st_tw.mu, st.mu) and np.array_equal(st_tw.sigma, st.sigma)
+    for k, (t, ob) in enumerate(scans):
+        tw.handle_observation(t, ob)
+        half = "read-back pattern" if k < 300 else "pipelined"
+        if k < 300:
+            p = tw.pose()
+            assert p[0] == poses[k][0] and np.array_equal(p[1], poses[k][1]) and np.array_equal(p[2], poses[k][2]), \
+                f"pose differs from the reading twin's at update {k}"
+        m = norm_match(tw.last_match())
+        assert all(np.array_equal(a, b) for a, b in zip(m, o_match[k])), f"association differs at update {k} ({half}, reading twin)"
+        assert np.abs(tw.mu() - o_mu[k]).max() < TIGHT, f"mean differs at update {k} ({half}, reading twin)"
+    fin = tw.GetState()
+    assert tw.sync_code() == 0 and tw.flags() == 0
+    # (a different association anywhere would move landmark means by millimetres; the reads themselves leave round-off between the
+    # two: scans that follow a scan without a pose read-back are device-predicted, and there reading or not is not bit-neutral)
+    d_mu, d_sig = float(np.abs(fin.mu - st2.mu).max()), float(np.abs(fin.sigma - st2.sigma).max())
+    print(f"sampled run vs reading twin: |d mu| {d_mu:.3e} |d sigma| {d_sig:.3e}")
+    assert fin.mu.shape == st2.mu.shape and d_mu < TIGHT and d_sig < 1e-11, f"the sampled run left its reading twin: {d_mu:.3e}"
 
 
 @pytest.mark.parametrize("full", [True, False], ids=["full_filters_one_launch_per_scan", "growing_filters"])

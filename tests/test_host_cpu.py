@@ -72,6 +72,79 @@ def test_synth_is_deterministic_and_covers_the_world():
     assert st[0][1].shape == (synth.C2.obs_per_scan, 2) and st[1][0] > st[0][0]
 
 
+def _digest(*arrays):
+    import hashlib
+    m = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        m.update(str(a.dtype).encode()); m.update(str(a.shape).encode()); m.update(a.tobytes())
+    return m.hexdigest()[:16]
+
+
+@pytest.mark.parametrize("pattern", ["twist", "odom50"])
+def test_moving_scans_are_deterministic_nearest_sets_that_change(pattern):
+    """synth.moving_scans (the moving steady state of tests/test_ekf_moving_gpu.py) against an independent nearest-neighbour
+    witness, and the generators the golden files and the bench depend on are byte for byte what they were."""
+    from scipy.spatial import cKDTree
+    from reflector_ekf_slam_amd import synth
+    cfg = synth.C3
+    sess = synth.make_session(cfg)
+    assert _digest(sess.landmarks, sess.init_pose, np.array([sess.init_time]), sess.ev_type, sess.ev_time, sess.odom,
+                   sess.obs_off, sess.obs, sess.obs_truth_id, sess.true_pose) == "db256c6deb31fd47"
+    ss = synth.steady_state_scans(sess, 50)
+    assert _digest(np.array([t for t, _ in ss]), *[o for _, o in ss]) == "836e3a2f60cebe01"
+
+    n = 1000
+    m = synth.moving_scans(sess, n, pattern)
+    m2 = synth.moving_scans(sess, n, pattern)
+    assert _digest(m.ev_type, m.ev_time, m.odom, m.obs_off, m.obs, m.obs_truth_id) == \
+        _digest(m2.ev_type, m2.ev_time, m2.odom, m2.obs_off, m2.obs, m2.obs_truth_id)
+    assert m.obs.dtype == np.float32 and m.config is cfg
+    assert m.init_time == sess.ev_time[-1] and np.array_equal(m.init_pose, sess.true_pose[-1])
+    assert np.all(np.diff(m.ev_time) > 0) and m.ev_time[0] > m.init_time
+
+    scans = m.scan_indices()
+    assert scans.size == n
+    assert np.all(m.obs_off[scans + 1] - m.obs_off[scans] == cfg.obs_per_scan)
+    odo = np.nonzero(m.ev_type == synth.EV_ODOM)[0]
+    if pattern == "twist":                                  # one odometry message, then scans only
+        assert odo.tolist() == [0] and np.array_equal(m.odom[0], [0.5, 0.0, 0.2])
+        assert np.allclose(np.diff(m.ev_time[scans]), 1.0 / cfg.scan_hz)
+        c = m.true_pose[scans, :2]
+        centre = m.init_pose[:2] + 2.5 * np.array([-np.sin(m.init_pose[2]), np.cos(m.init_pose[2])])
+        assert np.allclose(np.hypot(*(c - centre).T), 2.5)                     # the r = v / w circle
+    else:                                                   # five 50 Hz messages in front of every scan, none after the last
+        per = int(round(cfg.odom_hz / cfg.scan_hz))
+        assert odo.size == per * n
+        assert np.array_equal(scans, np.arange(1, n + 1) * (per + 1) - 1)
+        assert np.allclose(np.diff(m.ev_time[odo]), 1.0 / cfg.odom_hz)
+        w = m.odom[odo, 2].reshape(-1, 250).mean(1)                            # per 5 s stretch (the messages carry the launch noise)
+        assert np.all(np.abs(w[::2] - 0.2) < 0.02) and np.all(np.abs(w[1::2] + 0.2) < 0.02)
+        v = m.odom[odo, 0].reshape(-1, 2500).mean(1)                           # 50 s forward, 50 s in reverse
+        assert np.all(np.abs(v[::2] - 0.5) < 0.01) and np.all(np.abs(v[1::2] + 0.5) < 0.01)
+        assert np.abs(m.true_pose[scans[-1], :2] - m.init_pose[:2]).max() < 0.05   # the shuttle closes after 100 s
+
+    seen = np.unique(sess.obs_truth_id[sess.obs_off[sess.scan_indices()[1]]:])
+    tree = cKDTree(sess.landmarks[seen])
+    changes, prev = 0, None
+    for e in scans:
+        pose = m.true_pose[e]
+        ids = m.obs_truth_id[m.obs_off[e]: m.obs_off[e + 1]]
+        d, ix = tree.query(pose[:2], k=3 * cfg.obs_per_scan, distance_upper_bound=cfg.range_max)
+        keep = np.isfinite(d) & (d >= cfg.range_min)
+        want = seen[ix[keep][: cfg.obs_per_scan]]
+        assert set(ids.tolist()) == set(want.tolist()), f"scan at event {e}"
+        rel = sess.landmarks[ids] - pose[:2]                                    # robot frame, bearing order, noise ~ obs_noise
+        c, s = np.cos(pose[2]), np.sin(pose[2])
+        loc = np.stack([c * rel[:, 0] + s * rel[:, 1], -s * rel[:, 0] + c * rel[:, 1]], -1)
+        assert np.all(np.diff(np.arctan2(loc[:, 1], loc[:, 0])) >= 0)
+        assert np.abs(m.obs_of(e) - loc).max() < 6 * cfg.obs_noise
+        cur = frozenset(ids.tolist())
+        changes += prev is not None and cur != prev
+        prev = cur
+    assert changes >= 80, changes                           # (measured: twist 129, odom50 118 of the 999 scan-to-scan steps)
+
+
 def test_golden_inputs_match_the_generator(golden_dir):
     """The committed fixtures carry their own inputs; they must equal what synth generates today."""
     from reflector_ekf_slam_amd import synth
