@@ -1,0 +1,83 @@
+/*
+ * rfleet.h -- C ABI of the fleet filter (librfleet.so): many small reflector EKF-SLAM sessions advanced by ONE kernel
+ * launch per call.
+ *
+ * rekf.h serves one large filter per handle.  A fleet host (one hall, many AGVs, each with a few dozen to ~100 reflectors
+ * in its own map) hands over this tick's messages of ALL robots in one rfleet_submit and reads all poses back: each member
+ * with events in the call is advanced by one workgroup of one launch (csrc/fleet_kernels.hip), whatever the number of members.
+ *
+ * Per member the semantics are the single filter's (reference reflector_ekf_slam.cc): Predict (DIFF / OMNI), ReflectorMatch's
+ * state branch, the joint EKF update, landmark augmentation, and the odometry quirks (a message with t < state time is
+ * dropped, use_imu ignores odometry, an empty scan is a Predict).
+ *
+ * Conventions: as rekf.h -- opaque handle, one HIP stream per handle, NOT thread-safe, caller-owned host buffers borrowed
+ * for the duration of the call, 0 or a negative REKF_ERR_* code, nothing calls exit().  rekf_options, the REKF_ERR_* codes
+ * and the REKF_FLAGBIT_* bits are rekf.h's.
+ *
+ * Capacity is fixed at rfleet_create (max_landmarks <= RFLEET_MAX_LANDMARKS, else REKF_ERR_UNSUPPORTED).  A member that
+ * outgrows it drops the extra reflectors of a scan -- the first (n_max - n) / 2 new observations, in observation order, are
+ * appended -- and raises its OWN sticky REKF_FLAGBIT_CAPACITY, like a rekf_create handle without auto-grow.
+ *
+ * Deliberately OUT OF SCOPE (use a rekf handle): the pre-loaded map branch (rekf_set_map; n_map is always 0 here), the
+ * USE_GPS pose observation, scans wider than RFLEET_MAX_OBS, auto-grow, PredictState, marker ellipses.
+ *
+ * The covariance of a member lives on the device as its lower triangle; the getters mirror it (as rekf_get_state does).
+ */
+#ifndef RFLEET_H_
+#define RFLEET_H_
+
+#include "rekf.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RFLEET_ABI_VERSION 1
+#define RFLEET_MAX_LANDMARKS 128     /* per member: n <= 259 */
+#define RFLEET_MAX_OBS 32            /* per scan: one joint update, m <= 64 innovation rows */
+
+typedef struct rfleet rfleet_t;
+
+enum { RFLEET_EV_ODOM = 0, RFLEET_EV_SCAN = 1 };
+
+typedef struct rfleet_event {
+    int member;          /* 0 .. B-1 */
+    int kind;            /* RFLEET_EV_* */
+    double t;
+    double v[3];         /* ODOM: vx, vy, wz */
+    const float *xy;     /* SCAN: K robot-frame points (x, y pairs) */
+    int K;
+} rfleet_event;
+
+/* B members, opts[i] for member i (each starts as ReflectorEKFSLAM(opts[i]) does: n = 3, zero covariance).  B = 0,
+ * max_landmarks outside 1 .. RFLEET_MAX_LANDMARKS or a null pointer are refused before any HIP call. */
+int rfleet_create(const rekf_options *opts, int B, int max_landmarks, int device, rfleet_t **out);
+void rfleet_destroy(rfleet_t *f);
+
+/* Any number of events for any subset of members; a member's events are applied in the order given
+ * (HandleOdometryMessage / HandleObservationMessage each).  EVERYTHING is validated first: on an error return (a member out
+ * of range, an unknown kind, K < 0, K > RFLEET_MAX_OBS = REKF_ERR_TOO_MANY_OBS, K > 0 with a null xy) no member has moved.
+ * Packs the events into a pinned staging ring, enqueues ONE kernel launch and returns; consecutive calls do not synchronise. */
+int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count);
+
+/* All getters synchronise.  sigma3x3 / sigma are column-major. */
+int rfleet_get_poses(rfleet_t *f, double *t /*[B]*/, double *mu3 /*[B][3]*/, double *sigma3x3 /*[B][9]*/);
+int rfleet_get_n(rfleet_t *f, int *n /*[B]*/);
+int rfleet_get_flags(rfleet_t *f, int *flags /*[B], sticky REKF_FLAGBIT_* per member, not cleared*/);
+/* As rekf_get_state: mu (n) and sigma (n x n, ld = n) may each be NULL; caps in doubles (REKF_ERR_BUFFER when too small). */
+int rfleet_get_state(rfleet_t *f, int member, double *t, int *n, double *mu, long mu_cap, double *sigma, long sigma_cap);
+/* As rekf_set_state: only the lower triangle of sigma is used; vt3 = nullable last odometry velocity. */
+int rfleet_set_state(rfleet_t *f, int member, double t, int n, const double *mu, const double *sigma, const double *vt3);
+/* The member's last scan: pairs are (observation, landmark); buffers hold RFLEET_MAX_OBS entries (pairs: twice that).
+ * Any pointer may be NULL.  *n_map is always 0. */
+int rfleet_get_last_match(rfleet_t *f, int member, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new, int *new_ids);
+/* Wait for all enqueued work.  REKF_ERR_HIP when the device reported an error. */
+int rfleet_sync(rfleet_t *f);
+int rfleet_size(rfleet_t *f, int *B, int *max_landmarks);
+const char *rfleet_last_hip_error(rfleet_t *f);
+int rfleet_abi_version(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RFLEET_H_ */

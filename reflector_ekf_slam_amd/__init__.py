@@ -6,3 +6,4 @@ synthetic session generator (``synth``) and the session driver (``session``).
 """
 from .ekf_slam import (DIFF, OMNI, EKFOptions, Map, Observation, OdometryData,  # noqa: F401
                        ReflectorEKFSLAM, ReflectorMatchResult, RekfError, State)
+from .fleet import ReflectorEKFSLAMFleet  # noqa: F401

@@ -1,0 +1,63 @@
+// fleet_dev.h -- device-side layout shared by the fleet kernel (fleet_kernels.hip) and its C-ABI host (rfleet_api.hip).
+//
+// A fleet is B independent small filters (n <= 259) advanced by ONE launch per rfleet_submit: one workgroup per member
+// with events in the call.  Per member, sized once at rfleet_create for n_max = 3 + 2 max_landmarks:
+//
+//   mu  [ld]             state mean
+//   P   [ld x ld]        covariance, column-major, LOWER TRIANGLE valid (as ekf_dev.h), ld = roundup(n_max, 16): a C2-sized member
+//                        has 0.59 MB of covariance instead of the single filter's 0.82 MB (ld = roundup(n_max, 64))
+//   W   [ld x 64]        W = P H^T = (H P)^T of the current scan (P is exactly symmetric), column-major; rows [n, roundup(n, 16))
+//                        and columns [m, roundup(m, 16)) are written as zeros, nothing beyond them is read
+//   Kn  [ld x 64]        K = W S^-1, same shape and padding
+//   ctl                  FleetMemberCtl: n, sticky flags, the last scan's ReflectorMatchResult
+// W and Kn are scratch of the member's own workgroup: written and read inside one launch by that workgroup only.
+// Time and the last odometry velocity live on the HOST (rfleet_api.hip): an event arrives with its dt and velocity.
+#pragma once
+#include "ekf_dev.h"
+
+#define RFLEET_MAX_OBS_DEV 32
+#define RFLEET_PANEL_COLS 64
+#define RFLEET_THREADS 512
+
+struct FleetEvent {          // one Predict (+ scan) of one member, as the host packs it into the staging ring
+    double dt;               // t - state time
+    double vt[3];            // vt_ this Predict uses
+    int kind;                // 0 odometry (Predict only), 1 scan
+    int K;                   // observations (scan)
+    int obs_off;             // index of the scan's first float in FleetLaunch::obs
+    int pad_;
+};
+
+struct FleetMemberCtl {
+    int n;                   // state dimension 3 + 2 L
+    int flags;               // sticky REKF_FLAG_*
+    int K, n_state, n_new;   // the last scan's record
+    int pad_[3];
+    int state_pairs[2 * RFLEET_MAX_OBS_DEV];
+    int new_ids[RFLEET_MAX_OBS_DEV];
+};
+
+struct FleetMemberOpt { double lin_cov, ang_cov, obs_cov; int model; int pad_; };
+
+// what a launch leaves for the host in pinned memory, per member: read after a stream synchronisation, no copy of the state
+struct FleetPoseSlot { double mu3[3]; double C9[9]; int n; int flags; double pad_[3]; };
+
+struct FleetDev {
+    double *mu;              // [B][ld]
+    double *P;               // [B][ld * ld]
+    double *W, *Kn;          // [B][ld * RFLEET_PANEL_COLS]
+    FleetMemberCtl *ctl;     // [B]
+    const FleetMemberOpt *opt;   // [B]
+    FleetPoseSlot *pose;     // [B], pinned host memory
+    int ld, n_max, B, pad_;
+};
+
+struct FleetLaunch {         // one rfleet_submit: G members with events, member members[g] owns events [ev_begin[g], ev_begin[g + 1])
+    const int *members;
+    const int *ev_begin;
+    const FleetEvent *ev;
+    const float *obs;
+    int G, pad_;
+};
+
+hipError_t rfleet_launch_step(const FleetDev &d, const FleetLaunch &l, hipStream_t s);

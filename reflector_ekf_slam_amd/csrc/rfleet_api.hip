@@ -1,0 +1,381 @@
+// rfleet_api.hip -- host side of the fleet filter (include/rfleet.h): validation, the host's time / velocity mirror,
+// the pinned staging ring, one launch of k_fleet_step per rfleet_submit.
+//
+// Time and vt_ are host state: HandleOdometryMessage's `t < state time` test (cc:211-212) and the use_imu switch are decided
+// here, before packing, and every packed event carries its own dt and velocity.  A call's events are grouped by member (stable:
+// a member's events keep their order) into one segment of a ring of pinned buffers, which the kernel reads in place; a
+// segment is reused only after the launch that read it has finished (one hipEvent per segment), so consecutive submits
+// do not synchronise until the ring has gone round.
+#include "fleet_dev.h"
+#include "../../include/rfleet.h"
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace {
+constexpr int kSegs = 8;
+
+struct Segment {
+    char *host = nullptr;
+    char *dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t done = nullptr;
+    bool busy = false;
+};
+}  // namespace
+
+struct rfleet {
+    int B = 0, max_landmarks = 0, n_max = 0, ld = 0, device = 0;
+    hipStream_t stream = nullptr;
+    FleetDev dev{};
+    FleetPoseSlot *pose_host = nullptr;
+    std::vector<rekf_options> opts;
+    std::vector<double> time, vt;           // the host's mirror: state time [B], vt_ [B][3]
+    Segment seg[kSegs];
+    int next_seg = 0;
+    std::string hip_error;
+    // scratch of rfleet_submit (kept to avoid per-call allocation)
+    std::vector<int> cnt, pos, order;
+    std::vector<double> time_tmp, vt_tmp;
+    std::vector<double> stage;
+};
+
+#define FLEET_HIP(f, call)                                                     \
+    do {                                                                       \
+        hipError_t e_ = (call);                                                \
+        if (e_ != hipSuccess) {                                                \
+            (f)->hip_error = std::string(#call) + ": " + hipGetErrorString(e_); \
+            return REKF_ERR_HIP;                                               \
+        }                                                                      \
+    } while (0)
+
+static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+extern "C" {
+
+int rfleet_abi_version(void) { return RFLEET_ABI_VERSION; }
+
+const char *rfleet_last_hip_error(rfleet_t *f) { return f ? f->hip_error.c_str() : ""; }
+
+void rfleet_destroy(rfleet_t *f)
+{
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    for (Segment &s : f->seg) {
+        if (s.done) (void)hipEventDestroy(s.done);
+        if (s.host) (void)hipHostFree(s.host);
+    }
+    if (f->dev.mu) (void)hipFree(f->dev.mu);
+    if (f->dev.P) (void)hipFree(f->dev.P);
+    if (f->dev.W) (void)hipFree(f->dev.W);
+    if (f->dev.Kn) (void)hipFree(f->dev.Kn);
+    if (f->dev.ctl) (void)hipFree(f->dev.ctl);
+    if (f->dev.opt) (void)hipFree((void *)f->dev.opt);
+    if (f->pose_host) (void)hipHostFree(f->pose_host);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
+}
+
+static int fleet_create_body(rfleet_t *f, const rekf_options *opts)
+{
+    const int B = f->B;
+    const size_t ld = (size_t)f->ld;
+    FLEET_HIP(f, hipSetDevice(f->device));
+    FLEET_HIP(f, hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    FLEET_HIP(f, hipMalloc((void **)&f->dev.mu, sizeof(double) * ld * B));
+    FLEET_HIP(f, hipMalloc((void **)&f->dev.P, sizeof(double) * ld * ld * B));
+    FLEET_HIP(f, hipMalloc((void **)&f->dev.W, sizeof(double) * ld * RFLEET_PANEL_COLS * B));
+    FLEET_HIP(f, hipMalloc((void **)&f->dev.Kn, sizeof(double) * ld * RFLEET_PANEL_COLS * B));
+    FLEET_HIP(f, hipMalloc((void **)&f->dev.ctl, sizeof(FleetMemberCtl) * B));
+    FLEET_HIP(f, hipMalloc((void **)&f->dev.opt, sizeof(FleetMemberOpt) * B));
+    FLEET_HIP(f, hipHostMalloc((void **)&f->pose_host, sizeof(FleetPoseSlot) * B, hipHostMallocDefault));
+    FLEET_HIP(f, hipHostGetDevicePointer((void **)&f->dev.pose, f->pose_host, 0));
+    FLEET_HIP(f, hipMemset(f->dev.mu, 0, sizeof(double) * ld * B));
+    FLEET_HIP(f, hipMemset(f->dev.P, 0, sizeof(double) * ld * ld * B));
+    FLEET_HIP(f, hipMemset(f->dev.W, 0, sizeof(double) * ld * RFLEET_PANEL_COLS * B));
+    FLEET_HIP(f, hipMemset(f->dev.Kn, 0, sizeof(double) * ld * RFLEET_PANEL_COLS * B));
+    std::vector<FleetMemberCtl> ctl((size_t)B);
+    std::vector<FleetMemberOpt> dopt((size_t)B);
+    std::vector<double> mu(ld * B, 0.0);
+    memset(ctl.data(), 0, sizeof(FleetMemberCtl) * B);
+    memset(f->pose_host, 0, sizeof(FleetPoseSlot) * B);
+    for (int i = 0; i < B; ++i) {
+        const rekf_options &o = opts[i];
+        ctl[i].n = 3;
+        dopt[i].lin_cov = o.linear_velocity_cov;
+        dopt[i].ang_cov = o.angular_velocity_cov;
+        dopt[i].obs_cov = o.observation_cov;
+        dopt[i].model = (o.odom_model == REKF_ODOM_DIFF) ? 0 : 1;          // cc:13-32: anything else is OMNI
+        dopt[i].pad_ = 0;
+        for (int k = 0; k < 3; ++k) {
+            mu[(size_t)i * ld + k] = o.init_pose[k];
+            f->pose_host[i].mu3[k] = o.init_pose[k];
+        }
+        f->pose_host[i].n = 3;
+        f->time[i] = o.init_time;
+    }
+    FLEET_HIP(f, hipMemcpy(f->dev.ctl, ctl.data(), sizeof(FleetMemberCtl) * B, hipMemcpyHostToDevice));
+    FLEET_HIP(f, hipMemcpy((void *)f->dev.opt, dopt.data(), sizeof(FleetMemberOpt) * B, hipMemcpyHostToDevice));
+    FLEET_HIP(f, hipMemcpy(f->dev.mu, mu.data(), sizeof(double) * ld * B, hipMemcpyHostToDevice));
+    for (Segment &s : f->seg) FLEET_HIP(f, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    return REKF_OK;
+}
+
+int rfleet_create(const rekf_options *opts, int B, int max_landmarks, int device, rfleet_t **out)
+{
+    if (!out) return REKF_ERR_INVALID;
+    *out = nullptr;
+    if (!opts || B < 1 || B > (1 << 16) || max_landmarks < 1 || device < 0) return REKF_ERR_INVALID;
+    if (max_landmarks > RFLEET_MAX_LANDMARKS) return REKF_ERR_UNSUPPORTED;
+    rfleet_t *f = new rfleet;
+    f->B = B;
+    f->max_landmarks = max_landmarks;
+    f->n_max = 3 + 2 * max_landmarks;
+    f->ld = (f->n_max + 15) & ~15;
+    f->device = device;
+    f->dev.ld = f->ld;
+    f->dev.n_max = f->n_max;
+    f->dev.B = B;
+    f->opts.assign(opts, opts + B);
+    f->time.assign((size_t)B, 0.0);
+    f->vt.assign((size_t)3 * B, 0.0);
+    f->cnt.resize((size_t)B);
+    f->pos.resize((size_t)B);
+    const int rc = fleet_create_body(f, opts);
+    if (rc != REKF_OK) {
+        rfleet_destroy(f);
+        return rc;
+    }
+    *out = f;
+    return REKF_OK;
+}
+
+int rfleet_size(rfleet_t *f, int *B, int *max_landmarks)
+{
+    if (!f) return REKF_ERR_INVALID;
+    if (B) *B = f->B;
+    if (max_landmarks) *max_landmarks = f->max_landmarks;
+    return REKF_OK;
+}
+
+int rfleet_sync(rfleet_t *f)
+{
+    if (!f) return REKF_ERR_INVALID;
+    FLEET_HIP(f, hipSetDevice(f->device));
+    FLEET_HIP(f, hipStreamSynchronize(f->stream));
+    for (Segment &s : f->seg) s.busy = false;
+    return REKF_OK;
+}
+
+int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
+{
+    if (!f || count < 0 || (count > 0 && !ev)) return REKF_ERR_INVALID;
+    // ---- validate everything before anything moves
+    for (int i = 0; i < count; ++i) {
+        const rfleet_event &e = ev[i];
+        if (e.member < 0 || e.member >= f->B) return REKF_ERR_INVALID;
+        if (e.kind != RFLEET_EV_ODOM && e.kind != RFLEET_EV_SCAN) return REKF_ERR_INVALID;
+        if (e.kind == RFLEET_EV_SCAN) {
+            if (e.K < 0) return REKF_ERR_INVALID;
+            if (e.K > RFLEET_MAX_OBS) return REKF_ERR_TOO_MANY_OBS;
+            if (e.K > 0 && !e.xy) return REKF_ERR_INVALID;
+        }
+    }
+    if (count == 0) return REKF_OK;
+    // ---- which events reach the device (on a copy of the mirror: committed behind the launch)
+    const int B = f->B;
+    f->time_tmp = f->time;
+    f->vt_tmp = f->vt;
+    f->order.clear();
+    std::fill(f->cnt.begin(), f->cnt.end(), 0);
+    size_t n_obs = 0;
+    std::vector<double> &dts = f->stage;
+    dts.resize((size_t)count * 4);
+    for (int i = 0; i < count; ++i) {
+        const rfleet_event &e = ev[i];
+        const int b = e.member;
+        if (e.kind == RFLEET_EV_ODOM) {
+            if (f->opts[b].use_imu) continue;                              // cc:213-223: odometry is ignored with use_imu
+            if (e.t < f->time_tmp[b]) continue;                            // cc:211-212
+            for (int k = 0; k < 3; ++k) f->vt_tmp[3 * b + k] = e.v[k];     // cc:216
+        } else {
+            n_obs += (size_t)e.K;
+        }
+        dts[4 * (size_t)i] = e.t - f->time_tmp[b];                         // cc:217-218 / :232-233
+        for (int k = 0; k < 3; ++k) dts[4 * (size_t)i + 1 + k] = f->vt_tmp[3 * b + k];
+        f->time_tmp[b] = e.t;
+        f->cnt[b]++;
+        f->order.push_back(i);
+    }
+    const int E = (int)f->order.size();
+    if (E == 0) return REKF_OK;
+    int G = 0;
+    for (int b = 0; b < B; ++b) G += f->cnt[b] > 0;
+    // ---- a ring segment: members[G] | ev_begin[G + 1] | events[E] | obs[2 n_obs]
+    const size_t off_mem = 0, off_beg = align16(off_mem + sizeof(int) * G), off_ev = align16(off_beg + sizeof(int) * (G + 1));
+    const size_t off_obs = align16(off_ev + sizeof(FleetEvent) * E), need = align16(off_obs + sizeof(float) * 2 * n_obs + 16);
+    FLEET_HIP(f, hipSetDevice(f->device));
+    Segment &s = f->seg[f->next_seg];
+    if (s.busy) {
+        FLEET_HIP(f, hipEventSynchronize(s.done));
+        s.busy = false;
+    }
+    if (s.cap < need) {
+        size_t cap = s.cap ? s.cap : 4096;
+        while (cap < need) cap *= 2;
+        char *h = nullptr, *dv = nullptr;
+        FLEET_HIP(f, hipHostMalloc((void **)&h, cap, hipHostMallocDefault));
+        hipError_t e_ = hipHostGetDevicePointer((void **)&dv, h, 0);
+        if (e_ != hipSuccess) {
+            (void)hipHostFree(h);
+            f->hip_error = std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e_);
+            return REKF_ERR_HIP;
+        }
+        if (s.host) (void)hipHostFree(s.host);
+        s.host = h; s.dev = dv; s.cap = cap;
+    }
+    int *members = (int *)(s.host + off_mem), *ev_begin = (int *)(s.host + off_beg);
+    FleetEvent *pev = (FleetEvent *)(s.host + off_ev);
+    float *pobs = (float *)(s.host + off_obs);
+    int g = 0, acc = 0;
+    for (int b = 0; b < B; ++b) {
+        if (f->cnt[b] == 0) continue;
+        members[g] = b;
+        ev_begin[g] = acc;
+        f->pos[b] = acc;
+        acc += f->cnt[b];
+        ++g;
+    }
+    ev_begin[G] = acc;
+    size_t obs_at = 0;
+    for (int q = 0; q < E; ++q) {
+        const int i = f->order[q];
+        const rfleet_event &e = ev[i];
+        FleetEvent &pe = pev[f->pos[e.member]++];
+        pe.dt = dts[4 * (size_t)i];
+        for (int k = 0; k < 3; ++k) pe.vt[k] = dts[4 * (size_t)i + 1 + k];
+        pe.kind = (e.kind == RFLEET_EV_SCAN) ? 1 : 0;
+        pe.K = (e.kind == RFLEET_EV_SCAN) ? e.K : 0;
+        pe.obs_off = (int)obs_at;
+        pe.pad_ = 0;
+        if (pe.K > 0) {
+            memcpy(pobs + obs_at, e.xy, sizeof(float) * 2 * (size_t)pe.K);
+            obs_at += 2 * (size_t)pe.K;
+        }
+    }
+    FleetLaunch L{};
+    L.members = (const int *)(s.dev + off_mem);
+    L.ev_begin = (const int *)(s.dev + off_beg);
+    L.ev = (const FleetEvent *)(s.dev + off_ev);
+    L.obs = (const float *)(s.dev + off_obs);
+    L.G = G;
+    FLEET_HIP(f, rfleet_launch_step(f->dev, L, f->stream));
+    f->time.swap(f->time_tmp);
+    f->vt.swap(f->vt_tmp);
+    FLEET_HIP(f, hipEventRecord(s.done, f->stream));
+    s.busy = true;
+    f->next_seg = (f->next_seg + 1) % kSegs;
+    return REKF_OK;
+}
+
+int rfleet_get_poses(rfleet_t *f, double *t, double *mu3, double *sigma3x3)
+{
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    for (int b = 0; b < f->B; ++b) {
+        const FleetPoseSlot &p = f->pose_host[b];
+        if (t) t[b] = f->time[b];
+        if (mu3) memcpy(mu3 + 3 * (size_t)b, p.mu3, sizeof(double) * 3);
+        if (sigma3x3) memcpy(sigma3x3 + 9 * (size_t)b, p.C9, sizeof(double) * 9);
+    }
+    return REKF_OK;
+}
+
+int rfleet_get_n(rfleet_t *f, int *n)
+{
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    if (!n) return REKF_ERR_INVALID;
+    for (int b = 0; b < f->B; ++b) n[b] = f->pose_host[b].n;
+    return REKF_OK;
+}
+
+int rfleet_get_flags(rfleet_t *f, int *flags)
+{
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    if (!flags) return REKF_ERR_INVALID;
+    for (int b = 0; b < f->B; ++b) flags[b] = f->pose_host[b].flags;
+    return REKF_OK;
+}
+
+int rfleet_get_state(rfleet_t *f, int member, double *t, int *n_out, double *mu, long mu_cap, double *sigma, long sigma_cap)
+{
+    if (!f || member < 0 || member >= f->B) return REKF_ERR_INVALID;
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    const int n = f->pose_host[member].n;
+    const size_t ld = (size_t)f->ld;
+    if (t) *t = f->time[member];
+    if (n_out) *n_out = n;
+    if (mu) {
+        if (mu_cap < n) return REKF_ERR_BUFFER;
+        FLEET_HIP(f, hipMemcpy(mu, f->dev.mu + (size_t)member * ld, sizeof(double) * n, hipMemcpyDeviceToHost));
+    }
+    if (sigma) {
+        if (sigma_cap < (long)n * n) return REKF_ERR_BUFFER;
+        std::vector<double> tmp(ld * n);
+        FLEET_HIP(f, hipMemcpy(tmp.data(), f->dev.P + (size_t)member * ld * ld, sizeof(double) * ld * n, hipMemcpyDeviceToHost));
+        for (int j = 0; j < n; ++j)
+            for (int i = j; i < n; ++i) {
+                const double v = tmp[i + j * ld];
+                sigma[i + (size_t)j * n] = v;
+                sigma[j + (size_t)i * n] = v;
+            }
+    }
+    return REKF_OK;
+}
+
+int rfleet_set_state(rfleet_t *f, int member, double t, int n, const double *mu, const double *sigma, const double *vt3)
+{
+    if (!f || member < 0 || member >= f->B || !mu || !sigma) return REKF_ERR_INVALID;
+    if (n < 3 || n > f->n_max || ((n - 3) & 1)) return REKF_ERR_INVALID;
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    const size_t ld = (size_t)f->ld;
+    std::vector<double> tmp(ld * n, 0.0);
+    for (int j = 0; j < n; ++j)
+        for (int i = j; i < n; ++i) tmp[i + j * ld] = sigma[i + (size_t)j * n];
+    FLEET_HIP(f, hipMemcpy(f->dev.mu + (size_t)member * ld, mu, sizeof(double) * n, hipMemcpyHostToDevice));
+    FLEET_HIP(f, hipMemcpy(f->dev.P + (size_t)member * ld * ld, tmp.data(), sizeof(double) * ld * n, hipMemcpyHostToDevice));
+    FLEET_HIP(f, hipMemcpy(&f->dev.ctl[member].n, &n, sizeof(int), hipMemcpyHostToDevice));
+    FleetPoseSlot &p = f->pose_host[member];
+    for (int k = 0; k < 3; ++k) p.mu3[k] = mu[k];
+    for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < 3; ++i) p.C9[i + 3 * j] = (i >= j) ? sigma[i + (size_t)j * n] : sigma[j + (size_t)i * n];
+    p.n = n;
+    f->time[member] = t;
+    if (vt3)
+        for (int k = 0; k < 3; ++k) f->vt[3 * (size_t)member + k] = vt3[k];
+    return REKF_OK;
+}
+
+int rfleet_get_last_match(rfleet_t *f, int member, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new, int *new_ids)
+{
+    (void)map_pairs;
+    if (!f || member < 0 || member >= f->B) return REKF_ERR_INVALID;
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    FleetMemberCtl c;
+    FLEET_HIP(f, hipMemcpy(&c, f->dev.ctl + member, sizeof(c), hipMemcpyDeviceToHost));
+    if (n_state) *n_state = c.n_state;
+    if (n_map) *n_map = 0;
+    if (n_new) *n_new = c.n_new;
+    if (state_pairs) memcpy(state_pairs, c.state_pairs, sizeof(int) * 2 * (size_t)c.n_state);
+    if (new_ids) memcpy(new_ids, c.new_ids, sizeof(int) * (size_t)c.n_new);
+    return REKF_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,266 @@
+"""Fleet filter: many small reflector EKF-SLAM sessions advanced by ONE kernel launch per call (include/rfleet.h).
+
+``ReflectorEKFSLAMFleet(options_list)`` holds B independent filters (at most 128 reflectors each).  ``submit(events)`` hands
+over any number of odometry / scan messages of any subset of members and enqueues one launch of k_fleet_step (one workgroup
+per member with events); ``poses()`` reads all poses back.  ``member(i)`` is a view with the snake_case filter interface of
+``ReflectorEKFSLAM`` (each call a one-event submit), for code that drives one robot at a time.
+
+All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from .ekf_slam import ReflectorMatchResult, RekfError, State
+
+RFLEET_ABI_VERSION = 1        # must equal RFLEET_ABI_VERSION of include/rfleet.h and rfleet_abi_version() of the built library
+MAX_LANDMARKS = 128
+MAX_OBS = 32
+EV_ODOM, EV_SCAN = 0, 1
+
+
+class RfleetEvent(C.Structure):
+    """struct rfleet_event (include/rfleet.h)."""
+    _fields_ = [("member", C.c_int), ("kind", C.c_int), ("t", C.c_double), ("v", C.c_double * 3),
+                ("xy", C.c_void_p), ("K", C.c_int)]
+
+
+_rfleet = None
+
+
+def rfleet():
+    """librfleet.so with argtypes set.  Raises LibraryMissing when it was not built or speaks another ABI version."""
+    global _rfleet
+    if _rfleet is not None:
+        return _rfleet
+    path = _lib.lib_path("librfleet.so")
+    if not os.path.exists(path):
+        raise _lib.LibraryMissing(f"{path} not found: the HIP extension is not built "
+                                  "(run `python __graft_entry__.py`); there is no CPU fallback")
+    L = C.CDLL(path)
+    vp, ip = C.c_void_p, C.POINTER(C.c_int)
+    L.rfleet_abi_version.restype = C.c_int
+    have = L.rfleet_abi_version()
+    if have != RFLEET_ABI_VERSION:
+        raise _lib.LibraryMissing(f"{path} has ABI version {have}, this package speaks {RFLEET_ABI_VERSION}: rebuild it "
+                                  "(python __graft_entry__.py); there is no CPU fallback")
+    L.rfleet_last_hip_error.restype = C.c_char_p
+    L.rfleet_last_hip_error.argtypes = [vp]
+    L.rfleet_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.rfleet_destroy.argtypes = [vp]
+    L.rfleet_destroy.restype = None
+    L.rfleet_submit.argtypes = [vp, vp, C.c_int]
+    L.rfleet_get_poses.argtypes = [vp, vp, vp, vp]
+    L.rfleet_get_n.argtypes = [vp, vp]
+    L.rfleet_get_flags.argtypes = [vp, vp]
+    L.rfleet_get_state.argtypes = [vp, C.c_int, vp, ip, vp, C.c_long, vp, C.c_long]
+    L.rfleet_set_state.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, vp]
+    L.rfleet_get_last_match.argtypes = [vp, C.c_int, ip, vp, ip, vp, ip, vp]
+    L.rfleet_sync.argtypes = [vp]
+    L.rfleet_size.argtypes = [vp, ip, ip]
+    _rfleet = L
+    return L
+
+
+def odom_event(member, t, vx, vy, wz):
+    return (int(member), EV_ODOM, float(t), (float(vx), float(vy), float(wz)), None)
+
+
+def scan_event(member, t, cloud):
+    return (int(member), EV_SCAN, float(t), (0.0, 0.0, 0.0), cloud)
+
+
+class ReflectorEKFSLAMFleet:
+    """B independent ekf::ReflectorEKFSLAM filters on one MI355X, one kernel launch per ``submit``."""
+
+    def __init__(self, options_list, max_landmarks: int = MAX_LANDMARKS, device: int = 0):
+        self._L = rfleet()
+        self._h = None
+        self.options = list(options_list)
+        B = len(self.options)
+        arr = (_lib.RekfOptions * max(B, 1))()
+        for i, options in enumerate(self.options):
+            o = arr[i]
+            o.odom_model = int(options.odom_model)
+            o.use_imu = 1 if options.use_imu else 0
+            o.init_time = float(options.init_time)
+            for k in range(3):
+                o.init_pose[k] = float(options.init_pose[k])
+            o.linear_velocity_cov = float(options.linear_velocity_cov)
+            o.angular_velocity_cov = float(options.angular_velocity_cov)
+            o.observation_cov = float(options.observation_cov)
+        h = C.c_void_p()
+        rc = self._L.rfleet_create(C.cast(arr, C.c_void_p), B, int(max_landmarks), int(device), C.byref(h))
+        if rc != 0:
+            raise RekfError(rc, "rfleet_create")
+        self._h = h
+        self.B = B
+        self.max_landmarks = int(max_landmarks)
+
+    # -- lifetime -----------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.rfleet_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.B
+
+    def _chk(self, rc, where):
+        if rc != 0:
+            raise RekfError(rc, where, self._L.rfleet_last_hip_error(self._h).decode())
+
+    # -- the fleet interface --------------------------------------------------
+    @staticmethod
+    def pack(events):
+        """events: iterable of (member, kind, t, (vx, vy, wz), cloud or None) -- see ``odom_event`` / ``scan_event`` -- or
+        ``RfleetEvent``s.  -> (ctypes array, the float32 arrays it points into): reusable with ``submit_packed``."""
+        events = list(events)
+        arr = (RfleetEvent * max(len(events), 1))()
+        keep = []
+        for i, ev in enumerate(events):
+            if isinstance(ev, RfleetEvent):
+                arr[i] = ev
+                continue
+            member, kind, t, v, cloud = ev
+            e = arr[i]
+            e.member, e.kind, e.t = int(member), int(kind), float(t)
+            e.v[0], e.v[1], e.v[2] = float(v[0]), float(v[1]), float(v[2])
+            if kind == EV_SCAN and cloud is not None:
+                if not (type(cloud) is np.ndarray and cloud.dtype == np.float32 and cloud.flags.c_contiguous):
+                    cloud = np.ascontiguousarray(cloud, dtype=np.float32)
+                if cloud.size & 1:
+                    raise ValueError("observations are (x, y) pairs")
+                keep.append(cloud)
+                e.xy = cloud.ctypes.data if cloud.size else None
+                e.K = cloud.size >> 1
+        return arr, len(events), keep
+
+    def submit_code(self, events) -> int:
+        arr, count, _keep = self.pack(events)
+        return self._L.rfleet_submit(self._h, C.cast(arr, C.c_void_p), count)
+
+    def submit(self, events):
+        """Apply the events (a member's in the order given) with ONE kernel launch; returns without waiting for it."""
+        rc = self.submit_code(events)
+        if rc != 0:
+            self._chk(rc, "rfleet_submit")
+
+    def submit_packed(self, packed):
+        rc = self._L.rfleet_submit(self._h, C.cast(packed[0], C.c_void_p), packed[1])
+        if rc != 0:
+            self._chk(rc, "rfleet_submit")
+
+    def poses(self):
+        """-> (t [B], mu [B, 3], sigma [B, 3, 3]) of all members.  Synchronises; no copy of any state."""
+        t = np.zeros(self.B)
+        mu = np.zeros((self.B, 3))
+        sg = np.zeros((self.B, 9))
+        self._chk(self._L.rfleet_get_poses(self._h, t.ctypes.data, mu.ctypes.data, sg.ctypes.data), "rfleet_get_poses")
+        return t, mu, sg.reshape(self.B, 3, 3).transpose(0, 2, 1).copy()
+
+    def n(self) -> np.ndarray:
+        out = np.zeros(self.B, np.int32)
+        self._chk(self._L.rfleet_get_n(self._h, out.ctypes.data), "rfleet_get_n")
+        return out
+
+    def flags(self) -> np.ndarray:
+        """Sticky REKF_FLAGBIT_* bits per member, not cleared."""
+        out = np.zeros(self.B, np.int32)
+        self._chk(self._L.rfleet_get_flags(self._h, out.ctypes.data), "rfleet_get_flags")
+        return out
+
+    def sync(self):
+        self._chk(self._L.rfleet_sync(self._h), "rfleet_sync")
+
+    def member(self, i: int) -> "FleetMember":
+        if not 0 <= int(i) < self.B:
+            raise IndexError(i)
+        return FleetMember(self, int(i))
+
+    # -- per member -------------------------------------------------------------
+    def get_state(self, i: int, want_sigma: bool = True) -> State:
+        n = int(self.n()[i])
+        mu = np.zeros(n)
+        sig = np.zeros((n, n), order="F") if want_sigma else None
+        t = C.c_double()
+        nn = C.c_int()
+        self._chk(self._L.rfleet_get_state(self._h, int(i), C.addressof(t), C.byref(nn), mu.ctypes.data, n,
+                                           sig.ctypes.data if want_sigma else None, n * n if want_sigma else 0),
+                  "rfleet_get_state")
+        return State(t.value, mu, sig)
+
+    def set_state(self, i: int, t, mu, sigma, vt=None):
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        n = mu.shape[0]
+        flat = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).T).reshape(-1)   # column-major bytes
+        v = None
+        if vt is not None:
+            vv = np.ascontiguousarray(vt, dtype=np.float64)
+            v = vv.ctypes.data
+        self._chk(self._L.rfleet_set_state(self._h, int(i), float(t), n, mu.ctypes.data, flat.ctypes.data, v),
+                  "rfleet_set_state")
+
+    def last_match(self, i: int) -> ReflectorMatchResult:
+        sp = np.zeros((MAX_OBS, 2), np.int32)
+        nw = np.zeros((MAX_OBS,), np.int32)
+        ns, nm, nn = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self._L.rfleet_get_last_match(self._h, int(i), C.byref(ns), sp.ctypes.data, C.byref(nm), None,
+                                                C.byref(nn), nw.ctypes.data), "rfleet_get_last_match")
+        return ReflectorMatchResult(np.zeros((0, 2), np.int32), sp[: ns.value].copy(), nw[: nn.value].copy())
+
+
+class FleetMember:
+    """One member of a fleet with the snake_case filter interface; every message is a one-event ``submit``."""
+
+    def __init__(self, fleet: ReflectorEKFSLAMFleet, index: int):
+        self.fleet = fleet
+        self.index = index
+
+    def handle_odometry(self, t, vx, vy, wz):
+        self.fleet.submit([odom_event(self.index, t, vx, vy, wz)])
+
+    def handle_observation(self, t, cloud, gps_pose=None):
+        if gps_pose is not None:
+            raise ValueError("the fleet filter has no pose observation (include/rfleet.h: out of scope)")
+        self.fleet.submit([scan_event(self.index, t, cloud)])
+
+    @property
+    def n(self) -> int:
+        return int(self.fleet.n()[self.index])
+
+    def mu(self) -> np.ndarray:
+        return self.fleet.get_state(self.index, want_sigma=False).mu
+
+    def GetState(self) -> State:
+        return self.fleet.get_state(self.index)
+
+    def set_state(self, t, mu, sigma, vt=None):
+        self.fleet.set_state(self.index, t, mu, sigma, vt)
+
+    def last_match(self) -> ReflectorMatchResult:
+        return self.fleet.last_match(self.index)
+
+    def pose(self):
+        t, mu, sg = self.fleet.poses()
+        return float(t[self.index]), mu[self.index].copy(), sg[self.index].copy()
+
+    def flags(self) -> int:
+        return int(self.fleet.flags()[self.index])
+
+    def sync(self):
+        self.fleet.sync()
+
+    def sync_code(self) -> int:
+        return self.fleet._L.rfleet_sync(self.fleet._h)
+
