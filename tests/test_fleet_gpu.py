@@ -10,6 +10,7 @@ import pytest
 
 from reflector_ekf_slam_amd import synth
 from reflector_ekf_slam_amd import session as S
+from tests.fleet_cases import events_of, feed, fev, margins, same_bits, state_bits
 from tests.helpers import make_gpu, make_oracle, norm_match
 
 pytestmark = pytest.mark.gpu
@@ -27,61 +28,9 @@ def fleet_mod():
     return fleet
 
 
-def events_of(sess, stop=None):
-    """The session's messages as the node hands them over (the first scan only constructs the filter: session.replay)."""
-    out, first = [], True
-    for e in range(sess.n_events if stop is None else min(stop, sess.n_events)):
-        if sess.ev_type[e] == synth.EV_ODOM:
-            out.append((synth.EV_ODOM, float(sess.ev_time[e]), tuple(float(v) for v in sess.odom[e]), None))
-        elif first:
-            first = False
-        else:
-            out.append((synth.EV_SCAN, float(sess.ev_time[e]), (0.0, 0.0, 0.0), np.ascontiguousarray(sess.obs_of(e), np.float32)))
-    return out
-
-
 def oracle_for(sess):
     cfg = sess.config
     return make_oracle(cfg.odom_model, sess.init_time, sess.init_pose, cfg.sigma_v ** 2, cfg.sigma_w ** 2, cfg.sigma_obs ** 2)
-
-
-def feed(filt, ev):
-    kind, t, v, cloud = ev
-    if kind == synth.EV_ODOM:
-        filt.handle_odometry(t, *v)
-    else:
-        filt.handle_observation(t, cloud)
-
-
-def fev(member, ev):
-    return (member, ev[0], ev[1], ev[2], ev[3])
-
-
-def margins(mu_pred, cloud):
-    """Per observation (|d1 - 0.6|, d2 - d1) of ReflectorMatch's state branch at the predicted mean (float32 / FP64 as cc:426-451)."""
-    out = []
-    L = (mu_pred.shape[0] - 3) // 2
-    c, s = np.cos(mu_pred[2]), np.sin(mu_pred[2])
-    for p in np.asarray(cloud, np.float32).reshape(-1, 2):
-        gx = np.float32(float(p[0]) * c - float(p[1]) * s + mu_pred[0])
-        gy = np.float32(float(p[0]) * s + float(p[1]) * c + mu_pred[1])
-        if L == 0:
-            out.append((np.inf, np.inf))
-            continue
-        lm = mu_pred[3:].reshape(-1, 2).astype(np.float32)
-        ex, ey = (gx - lm[:, 0]).astype(np.float64), (gy - lm[:, 1]).astype(np.float64)
-        dd = np.sort(np.sqrt(ex * ex + ey * ey))
-        out.append((abs(dd[0] - 0.6), dd[1] - dd[0] if L > 1 else np.inf))
-    return out
-
-
-def state_bits(fl, i):
-    st = fl.get_state(i)
-    return st.mu.copy(), np.array(st.sigma, order="F", copy=True)
-
-
-def same_bits(a, b):
-    return a[0].shape == b[0].shape and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
 @pytest.fixture(scope="module")
