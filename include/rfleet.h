@@ -18,8 +18,14 @@
  * outgrows it drops the extra reflectors of a scan -- the first (n_max - n) / 2 new observations, in observation order, are
  * appended -- and raises its OWN sticky REKF_FLAGBIT_CAPACITY, like a rekf_create handle without auto-grow.
  *
- * Deliberately OUT OF SCOPE (use a rekf handle): the pre-loaded map branch (rekf_set_map; n_map is always 0 here), the
- * USE_GPS pose observation, scans wider than RFLEET_MAX_OBS, auto-grow, PredictState, marker ellipses.
+ * The USE_GPS deployment (reference reflector_ekf_slam_gps.cc:305-340, src/ros_node.cc:450-478) is served per member: a scan
+ * event may carry an absolute pose fix (x, y, yaw), which rides on the scan's update as three extra rows H = [I3 0] with the
+ * fixed noise diag(0.05^2, 0.05^2, 0.017^2) and the reference's quaternion -> angle-axis yaw innovation; as there, the rows
+ * exist only when the scan matched at least one reflector (a fix on a scan without a match, an empty one included, is
+ * ignored).  rfleet_predict_poses is PredictState's pose block for every member: the pose a scan matcher starts from.
+ *
+ * Deliberately OUT OF SCOPE (use a rekf handle): the pre-loaded map branch (rekf_set_map; n_map is always 0 here), scans
+ * wider than RFLEET_MAX_OBS, auto-grow, PredictState's landmark part (the full state), marker ellipses.
  *
  * The covariance of a member lives on the device as its lower triangle; the getters mirror it (as rekf_get_state does).
  */
@@ -32,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RFLEET_ABI_VERSION 1
+#define RFLEET_ABI_VERSION 2
 #define RFLEET_MAX_LANDMARKS 128     /* per member: n <= 259 */
 #define RFLEET_MAX_OBS 32            /* per scan: one joint update, m <= 64 innovation rows */
 
@@ -47,6 +53,8 @@ typedef struct rfleet_event {
     double v[3];         /* ODOM: vx, vy, wz */
     const float *xy;     /* SCAN: K robot-frame points (x, y pairs) */
     int K;
+    int has_pose_fix;    /* SCAN: non-zero = pose_fix holds an absolute pose observation of this scan's time */
+    double pose_fix[3];  /* x, y, yaw (read only when has_pose_fix is set) */
 } rfleet_event;
 
 /* B members, opts[i] for member i (each starts as ReflectorEKFSLAM(opts[i]) does: n = 3, zero covariance).  B = 0,
@@ -56,12 +64,18 @@ void rfleet_destroy(rfleet_t *f);
 
 /* Any number of events for any subset of members; a member's events are applied in the order given
  * (HandleOdometryMessage / HandleObservationMessage each).  EVERYTHING is validated first: on an error return (a member out
- * of range, an unknown kind, K < 0, K > RFLEET_MAX_OBS = REKF_ERR_TOO_MANY_OBS, K > 0 with a null xy) no member has moved.
+ * of range, an unknown kind, K < 0, K > RFLEET_MAX_OBS = REKF_ERR_TOO_MANY_OBS, K > 0 with a null xy, has_pose_fix on an
+ * odometry event, a non-finite component of a fix) no member has moved.
  * Packs the events into a pinned staging ring, enqueues ONE kernel launch and returns; consecutive calls do not synchronise. */
 int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count);
 
 /* All getters synchronise.  sigma3x3 / sigma are column-major. */
 int rfleet_get_poses(rfleet_t *f, double *t /*[B]*/, double *mu3 /*[B][3]*/, double *sigma3x3 /*[B][9]*/);
+/* PredictState's pose block (cc:97-152) of every member, from the member's state time to t[b] with its last odometry velocity:
+ * the pose and 3 x 3 covariance a scan matcher starts from.  Non-mutating.  Synchronises like the getters, then evaluates on
+ * the host; launches nothing.  As rekf_predict_state: t[b] before the state time gives a negative dt (no test), a use_imu
+ * member's velocity is the zero it was created with.  sigma3x3 may be NULL. */
+int rfleet_predict_poses(rfleet_t *f, const double *t /*[B]*/, double *mu3 /*[B][3]*/, double *sigma3x3 /*[B][9]*/);
 int rfleet_get_n(rfleet_t *f, int *n /*[B]*/);
 int rfleet_get_flags(rfleet_t *f, int *flags /*[B], sticky REKF_FLAGBIT_* per member, not cleared*/);
 /* As rekf_get_state: mu (n) and sigma (n x n, ld = n) may each be NULL; caps in doubles (REKF_ERR_BUFFER when too small). */
@@ -76,6 +90,8 @@ int rfleet_sync(rfleet_t *f);
 int rfleet_size(rfleet_t *f, int *B, int *max_landmarks);
 const char *rfleet_last_hip_error(rfleet_t *f);
 int rfleet_abi_version(void);
+/* sizeof(rfleet_event) as the library was compiled: a binding checks its own layout against it */
+int rfleet_sizeof_event(void);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,7 @@ struct FleetEvent {          // one Predict (+ scan) of one member, as the host 
     int kind;                // 0 odometry (Predict only), 1 scan
     int K;                   // observations (scan)
     int obs_off;             // index of the scan's first float in FleetLaunch::obs
-    int pad_;
+    int fix_off;             // index of the scan's pose fix (x, y, yaw) in FleetLaunch::fix, -1: the scan has none
 };
 
 struct FleetMemberCtl {
@@ -57,6 +57,7 @@ struct FleetLaunch {         // one rfleet_submit: G members with events, member
     const int *ev_begin;
     const FleetEvent *ev;
     const float *obs;
+    const double *fix;       // the pose fixes of the call's scans, three doubles each; NULL when no scan of the call has one
     int G, pad_;
 };
 

@@ -1,3 +1,4 @@
+#ifndef FLEET_STEP_KERNEL
 // fleet_kernels.hip -- k_fleet_step: many small EKF-SLAM filters, ONE workgroup per filter, one launch per rfleet_submit.
 //
 // The single filter's kernels (ekf_kernels.hip) spread one scan of an n = 2051 filter over 130 workgroups.  A fleet member is
@@ -15,12 +16,23 @@
 //   D  S^-1 in LDS: Gauss-Jordan without pivoting (S is SPD; a non-positive pivot raises REKF_FLAG_SINGULAR)
 //   E  K = W S^-1 on v_mfma_f64_16x16x4_f64 (S^-1 from LDS), mean update, heading wrap
 //   F  P -= K W^T on the lower triangle, 16 x 16 tiles on v_mfma_f64_16x16x4_f64, tiles dealt to the waves
+//   P  the scan's pose fix, if it has one and matched a reflector (gps.cc:305-340): a rank-3 step on what C-F left, see below
 //   G  augmentation rows and means (cc:311-364)
 // and, once per launch, the pose, pose block, n and flags into the member's slot in pinned host memory.
 //
 // FP64 MFMA operand layout (16x16x4): lane l supplies A[l & 15][l >> 4] and B[l >> 4][l & 15]; result register r of lane l is
 // D[(l >> 4) + 4 r][l & 15].  Phases E and F compute the TRANSPOSED tile (D = B-side rows along the lanes) so that the 16 lanes of
 // a group store 128 contiguous bytes of a column of Kn / P.
+//
+// Phase P.  The reference stacks three pose rows H = [I3 0] with noise R = diag(0.05^2, 0.05^2, 0.017^2) under the reflector rows
+// and solves the joint system: up to 67 rows, more than S in LDS and the W / Kn panels hold.  The noise of the joint system is
+// block-diagonal between reflector rows and pose rows, so the joint update EQUALS the reflector update (C-F: mu0 -> mu1, P1)
+// followed by the pose rows' update at the same linearisation point, whose innovation is taken against the mean C-F left:
+//   innov2 = wrap(z - mu0[0:3]) - (mu1[0:3] - mu0[0:3]),   S2 = P1[0:3, 0:3] + R,   K2 = P1[:, 0:3] S2^-1,
+//   mu2 = mu1 + K2 innov2,   P2 = P1 - K2 P1[0:3, :]
+// (the heading is normalised once, after both).  W2 = P1[:, 0:3] is three contiguous columns of the lower triangle; W2 and K2
+// (n x 4, k padded 3 -> 4 with zeros) sit in LDS, in the space S^-1 has left, and the downdate walks phase F's tiles with one
+// MFMA each.  A scan without a fix runs C-F as it always did.
 #include "fleet_dev.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
@@ -36,8 +48,49 @@ __device__ static inline void fleet_obs_to_global(double x, double y, double c, 
     gy = (float)((double)px * s + (double)py * c + y);
 }
 
-__global__ __launch_bounds__(RFLEET_THREADS) void k_fleet_step(FleetDev d, FleetLaunch L)
+// gps.cc:320-328: the yaw difference as quaternion (w, 0, 0, z) -> angle-axis z (reference transform.h:46-70)
+__device__ static inline double fleet_yaw_innovation(double delta_theta)
 {
+#pragma clang fp contract(off)
+    double w = cos(delta_theta / 2), z = sin(delta_theta / 2);
+    const double nrm = sqrt(w * w + z * z);
+    w /= nrm; z /= nrm;
+    if (w < 0.) { w = -w; z = -z; }
+    const double angle = 2. * atan2(fabs(z), w);
+    const double scale = angle < 1e-7 ? 2. : angle / sin(angle / 2.);
+    return scale * z;
+}
+
+// The kernel's body stands once, below the `#else`, and is compiled twice by this file including itself: k_fleet_step for a
+// launch in which no scan carries a fix (the host knows), k_fleet_step_fix otherwise.  In k_fleet_step phase P and its tests are
+// discarded statements, and as a plain (non-template) kernel of that name it compiles to the code it had before phase P existed
+// (a template's instantiation does not: its LDS variables get other names and another layout, and the common path lost 0.7 %).
+// Both kernels compute a member's plain scans with the same arithmetic (tests/test_fleet_pose_gpu.py: the same bits beside
+// neighbours with and without fixes).
+#define FLEET_STEP_KERNEL k_fleet_step
+#define FLEET_STEP_FIX false
+#include "fleet_kernels.hip"
+#undef FLEET_STEP_KERNEL
+#undef FLEET_STEP_FIX
+#define FLEET_STEP_KERNEL k_fleet_step_fix
+#define FLEET_STEP_FIX true
+#include "fleet_kernels.hip"
+#undef FLEET_STEP_KERNEL
+#undef FLEET_STEP_FIX
+
+hipError_t rfleet_launch_step(const FleetDev &d, const FleetLaunch &l, hipStream_t s)
+{
+    if (l.G <= 0) return hipSuccess;
+    if (l.fix) hipLaunchKernelGGL(k_fleet_step_fix, dim3((unsigned)l.G), dim3(RFLEET_THREADS), 0, s, d, l);
+    else hipLaunchKernelGGL(k_fleet_step, dim3((unsigned)l.G), dim3(RFLEET_THREADS), 0, s, d, l);
+    return hipGetLastError();
+}
+
+#else  // ---- the kernel's body: FLEET_STEP_KERNEL, FLEET_STEP_FIX
+
+__global__ __launch_bounds__(RFLEET_THREADS) void FLEET_STEP_KERNEL(FleetDev d, FleetLaunch L)
+{
+    constexpr bool FIX = FLEET_STEP_FIX;
     __shared__ double s_mu[FLEET_LD_MAX];
     __shared__ double s_S[64 * FLEET_SLD];
     __shared__ double s_hv[64][5];
@@ -51,6 +104,9 @@ __global__ __launch_bounds__(RFLEET_THREADS) void k_fleet_step(FleetDev d, Fleet
     __shared__ FleetEvent s_ev;
     __shared__ double s_cs[2];
     __shared__ double s_Gp[RFLEET_MAX_OBS_DEV][6], s_Sxi[9], s_RQR[4];
+    __shared__ double s_p0[3], s_in2[3], s_Si2[9];       // phase P: the linearisation pose, innov2, S2^-1
+    double *const s_W2 = s_S, *const s_K2 = s_S + 4 * FLEET_LD_MAX;     // phase P: W2, K2 as [4][FLEET_LD_MAX] (S^-1 is dead by then)
+    static_assert(8 * FLEET_LD_MAX <= 64 * FLEET_SLD, "W2 and K2 live in S's space");
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int g = blockIdx.x;
@@ -79,6 +135,8 @@ __global__ __launch_bounds__(RFLEET_THREADS) void k_fleet_step(FleetDev d, Fleet
         }
         __syncthreads();
         const int kind = s_ev.kind, K = s_ev.K, obs_off = s_ev.obs_off;    // (thread 0 rewrites s_ev at the top of the next event)
+        int fix_off = -1;
+        if constexpr (FIX) fix_off = s_ev.fix_off;
         {
 #pragma clang fp contract(off)
             const double a = s_mo.a, b = s_mo.b;
@@ -167,6 +225,9 @@ __global__ __launch_bounds__(RFLEET_THREADS) void k_fleet_step(FleetDev d, Fleet
                 h0[0] = -c; h0[1] = -s; h0[2] = -dx * s + dy * c; h0[3] = c;  h0[4] = s;      // cc:272-275
                 h1[0] = s;  h1[1] = -c; h1[2] = -dx * c - dy * s; h1[3] = -s; h1[4] = c;
             }
+            if constexpr (FIX) {
+                if (fix_off >= 0 && tid >= 64 && tid < 67) s_p0[tid - 64] = s_mu[tid - 64];   // mu0's pose, for phase P
+            }
             __syncthreads();
             const int n16 = (n + 15) & ~15, m16 = (m + 15) & ~15, m4 = (m + 3) & ~3;
             for (int idx = tid; idx < n16 * m16; idx += RFLEET_THREADS) {
@@ -230,7 +291,7 @@ __global__ __launch_bounds__(RFLEET_THREADS) void k_fleet_step(FleetDev d, Fleet
                 s_mu[r] += acc;
             }
             __syncthreads();
-            if (tid == 0) {
+            if (tid == 0 && (!FIX || fix_off < 0)) {                                          // (with a fix: after phase P)
                 double sn, cs;
                 rekf_sincos(s_mu[2], &sn, &cs);
                 s_mu[2] = atan2(sn, cs);
@@ -262,6 +323,99 @@ __global__ __launch_bounds__(RFLEET_THREADS) void k_fleet_step(FleetDev d, Fleet
                     }
             }
             __syncthreads();
+            // ---- P: the pose fix (gps.cc:305-340) as a rank-3 step on mu1 = s_mu (heading not yet wrapped), P1 = P
+            if constexpr (FIX) if (fix_off >= 0) {
+                for (int idx = tid; idx < 4 * n16; idx += RFLEET_THREADS) {
+                    const int k = idx / n16, r = idx - k * n16;
+                    s_W2[k * FLEET_LD_MAX + r] = (k < 3 && r < n) ? rekf_plower(P, (int)ld, r, k) : 0.0;
+                }
+                if (tid == 64) {
+#pragma clang fp contract(off)
+                    const double e0 = L.fix[fix_off] - s_p0[0], e1 = L.fix[fix_off + 1] - s_p0[1];
+                    const double e2 = fleet_yaw_innovation(L.fix[fix_off + 2] - s_p0[2]);
+                    s_in2[0] = e0 - (s_mu[0] - s_p0[0]);
+                    s_in2[1] = e1 - (s_mu[1] - s_p0[1]);
+                    s_in2[2] = e2 - (s_mu[2] - s_p0[2]);
+                }
+                if (tid == 0) {
+#pragma clang fp contract(off)
+                    // S2 = P1[0:3, 0:3] + R (gps.cc:312-316), inverted by Gauss-Jordan without pivoting as phase D does
+                    double A[9];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) A[3 * i + j] = rekf_plower(P, (int)ld, i, j);
+                    A[0] += 0.05 * 0.05; A[4] += 0.05 * 0.05; A[8] += 0.017 * 0.017;
+                    bool bad = false;
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) {
+                        const double piv = A[3 * p + p];
+                        bad = bad || !(piv > 0.0);
+                        const double inv = 1.0 / piv;
+                        double col[3], row[3];
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) { col[q] = A[3 * q + p]; row[q] = A[3 * p + q]; }
+#pragma unroll
+                        for (int i = 0; i < 3; ++i)
+#pragma unroll
+                            for (int j = 0; j < 3; ++j) {
+                                double v;
+                                if (i == p) v = (j == p) ? inv : row[j] * inv;
+                                else if (j == p) v = -col[i] * inv;
+                                else v = A[3 * i + j] - col[i] * (row[j] * inv);
+                                A[3 * i + j] = v;
+                            }
+                    }
+                    if (bad) s_flags |= REKF_FLAG_SINGULAR;
+#pragma unroll
+                    for (int q = 0; q < 9; ++q) s_Si2[q] = A[q];
+                }
+                __syncthreads();
+                for (int r = tid; r < n16; r += RFLEET_THREADS) {                             // K2 = W2 S2^-1, mu2 = mu1 + K2 innov2
+#pragma clang fp contract(off)
+                    const double w0 = s_W2[r], w1 = s_W2[FLEET_LD_MAX + r], w2 = s_W2[2 * FLEET_LD_MAX + r];
+                    double k[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        double acc = w0 * s_Si2[c];
+                        acc += w1 * s_Si2[3 + c];
+                        acc += w2 * s_Si2[6 + c];
+                        k[c] = acc;
+                        s_K2[c * FLEET_LD_MAX + r] = acc;
+                    }
+                    s_K2[3 * FLEET_LD_MAX + r] = 0.0;
+                    if (r < n) {
+                        double acc = k[0] * s_in2[0];
+                        acc += k[1] * s_in2[1];
+                        acc += k[2] * s_in2[2];
+                        s_mu[r] += acc;
+                    }
+                }
+                __syncthreads();
+                if (tid == 0) {                                                               // the update's one heading wrap
+                    double sn, cs;
+                    rekf_sincos(s_mu[2], &sn, &cs);
+                    s_mu[2] = atan2(sn, cs);
+                }
+                {
+                    const int nI = n16 >> 4;
+                    const int lr = lane & 15, lk = lane >> 4;
+                    int cntr = 0;
+                    for (int I = 0; I < nI; ++I)
+                        for (int J = 0; J <= I; ++J, ++cntr) {
+                            if ((cntr & (RFLEET_THREADS / 64 - 1)) != w) continue;
+                            v4d acc = {0, 0, 0, 0};
+                            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(s_W2[lk * FLEET_LD_MAX + 16 * J + lr], s_K2[lk * FLEET_LD_MAX + 16 * I + lr], acc, 0, 0, 0);
+                            const int i = 16 * I + lr;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const int j = 16 * J + lk + 4 * r;
+                                if (i < n && j <= i) P[i + (size_t)j * ld] -= acc[r];
+                            }
+                        }
+                }
+                __syncthreads();
+            }
         }
 
         // ---- G: augmentation (cc:311-364)
@@ -340,9 +494,4 @@ __global__ __launch_bounds__(RFLEET_THREADS) void k_fleet_step(FleetDev d, Fleet
     }
 }
 
-hipError_t rfleet_launch_step(const FleetDev &d, const FleetLaunch &l, hipStream_t s)
-{
-    if (l.G <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fleet_step, dim3((unsigned)l.G), dim3(RFLEET_THREADS), 0, s, d, l);
-    return hipGetLastError();
-}
+#endif

@@ -9,6 +9,7 @@
 #include "fleet_dev.h"
 #include "../../include/rfleet.h"
 
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -55,6 +56,8 @@ static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 extern "C" {
 
 int rfleet_abi_version(void) { return RFLEET_ABI_VERSION; }
+
+int rfleet_sizeof_event(void) { return (int)sizeof(rfleet_event); }
 
 const char *rfleet_last_hip_error(rfleet_t *f) { return f ? f->hip_error.c_str() : ""; }
 
@@ -181,6 +184,10 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
             if (e.K < 0) return REKF_ERR_INVALID;
             if (e.K > RFLEET_MAX_OBS) return REKF_ERR_TOO_MANY_OBS;
             if (e.K > 0 && !e.xy) return REKF_ERR_INVALID;
+            if (e.has_pose_fix && !(std::isfinite(e.pose_fix[0]) && std::isfinite(e.pose_fix[1]) && std::isfinite(e.pose_fix[2])))
+                return REKF_ERR_INVALID;
+        } else if (e.has_pose_fix) {
+            return REKF_ERR_INVALID;                                       // a fix belongs to a scan
         }
     }
     if (count == 0) return REKF_OK;
@@ -190,7 +197,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     f->vt_tmp = f->vt;
     f->order.clear();
     std::fill(f->cnt.begin(), f->cnt.end(), 0);
-    size_t n_obs = 0;
+    size_t n_obs = 0, n_fix = 0;
     std::vector<double> &dts = f->stage;
     dts.resize((size_t)count * 4);
     for (int i = 0; i < count; ++i) {
@@ -202,6 +209,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
             for (int k = 0; k < 3; ++k) f->vt_tmp[3 * b + k] = e.v[k];     // cc:216
         } else {
             n_obs += (size_t)e.K;
+            n_fix += e.has_pose_fix ? 1 : 0;
         }
         dts[4 * (size_t)i] = e.t - f->time_tmp[b];                         // cc:217-218 / :232-233
         for (int k = 0; k < 3; ++k) dts[4 * (size_t)i + 1 + k] = f->vt_tmp[3 * b + k];
@@ -213,9 +221,10 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     if (E == 0) return REKF_OK;
     int G = 0;
     for (int b = 0; b < B; ++b) G += f->cnt[b] > 0;
-    // ---- a ring segment: members[G] | ev_begin[G + 1] | events[E] | obs[2 n_obs]
+    // ---- a ring segment: members[G] | ev_begin[G + 1] | events[E] | fix[3 n_fix] | obs[2 n_obs]
     const size_t off_mem = 0, off_beg = align16(off_mem + sizeof(int) * G), off_ev = align16(off_beg + sizeof(int) * (G + 1));
-    const size_t off_obs = align16(off_ev + sizeof(FleetEvent) * E), need = align16(off_obs + sizeof(float) * 2 * n_obs + 16);
+    const size_t off_fix = align16(off_ev + sizeof(FleetEvent) * E), off_obs = align16(off_fix + sizeof(double) * 3 * n_fix);
+    const size_t need = align16(off_obs + sizeof(float) * 2 * n_obs + 16);
     FLEET_HIP(f, hipSetDevice(f->device));
     Segment &s = f->seg[f->next_seg];
     if (s.busy) {
@@ -238,6 +247,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     }
     int *members = (int *)(s.host + off_mem), *ev_begin = (int *)(s.host + off_beg);
     FleetEvent *pev = (FleetEvent *)(s.host + off_ev);
+    double *pfix = (double *)(s.host + off_fix);
     float *pobs = (float *)(s.host + off_obs);
     int g = 0, acc = 0;
     for (int b = 0; b < B; ++b) {
@@ -250,6 +260,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     }
     ev_begin[G] = acc;
     size_t obs_at = 0;
+    int fix_at = 0;
     for (int q = 0; q < E; ++q) {
         const int i = f->order[q];
         const rfleet_event &e = ev[i];
@@ -259,7 +270,12 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
         pe.kind = (e.kind == RFLEET_EV_SCAN) ? 1 : 0;
         pe.K = (e.kind == RFLEET_EV_SCAN) ? e.K : 0;
         pe.obs_off = (int)obs_at;
-        pe.pad_ = 0;
+        pe.fix_off = -1;
+        if (e.kind == RFLEET_EV_SCAN && e.has_pose_fix) {
+            pe.fix_off = fix_at;
+            for (int k = 0; k < 3; ++k) pfix[fix_at + k] = e.pose_fix[k];
+            fix_at += 3;
+        }
         if (pe.K > 0) {
             memcpy(pobs + obs_at, e.xy, sizeof(float) * 2 * (size_t)pe.K);
             obs_at += 2 * (size_t)pe.K;
@@ -270,6 +286,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     L.ev_begin = (const int *)(s.dev + off_beg);
     L.ev = (const FleetEvent *)(s.dev + off_ev);
     L.obs = (const float *)(s.dev + off_obs);
+    L.fix = n_fix ? (const double *)(s.dev + off_fix) : nullptr;      // (NULL selects the kernel without the pose phase)
     L.G = G;
     FLEET_HIP(f, rfleet_launch_step(f->dev, L, f->stream));
     f->time.swap(f->time_tmp);
@@ -289,6 +306,32 @@ int rfleet_get_poses(rfleet_t *f, double *t, double *mu3, double *sigma3x3)
         if (t) t[b] = f->time[b];
         if (mu3) memcpy(mu3 + 3 * (size_t)b, p.mu3, sizeof(double) * 3);
         if (sigma3x3) memcpy(sigma3x3 + 9 * (size_t)b, p.C9, sizeof(double) * 9);
+    }
+    return REKF_OK;
+}
+
+int rfleet_predict_poses(rfleet_t *f, const double *t, double *mu3, double *sigma3x3)
+{
+#pragma clang fp contract(off)
+    if (!f || !t || !mu3) return REKF_ERR_INVALID;
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    for (int b = 0; b < f->B; ++b) {
+        const FleetPoseSlot &p = f->pose_host[b];
+        const rekf_options &o = f->opts[b];
+        const double *vt = &f->vt[3 * (size_t)b];
+        double C[9];
+        memcpy(C, p.C9, sizeof(C));
+        Motion mo;
+        motion_terms_of((o.odom_model == REKF_ODOM_DIFF) ? 0 : 1, t[b] - f->time[b], vt[0], vt[1], vt[2], o.linear_velocity_cov,
+                        o.angular_velocity_cov, p.mu3[2], mo);                 // cc:100-150
+        corner_predict(C, 3, mo);
+        double *m = mu3 + 3 * (size_t)b;
+        m[0] = p.mu3[0] + mo.d[0];
+        m[1] = p.mu3[1] + mo.d[1];
+        const double th = p.mu3[2] + mo.d[2];
+        m[2] = atan2(sin(th), cos(th));
+        if (sigma3x3) memcpy(sigma3x3 + 9 * (size_t)b, C, sizeof(C));
     }
     return REKF_OK;
 }

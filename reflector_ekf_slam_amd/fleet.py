@@ -2,7 +2,8 @@
 
 ``ReflectorEKFSLAMFleet(options_list)`` holds B independent filters (at most 128 reflectors each).  ``submit(events)`` hands
 over any number of odometry / scan messages of any subset of members and enqueues one launch of k_fleet_step (one workgroup
-per member with events); ``poses()`` reads all poses back.  ``member(i)`` is a view with the snake_case filter interface of
+per member with events); ``poses()`` reads all poses back.  A scan may carry an absolute pose fix (the reference's USE_GPS
+deployment: ``predict_poses(times)`` -> scan matcher -> ``scan_event(..., pose_fix=matched_pose)``).  ``member(i)`` is a view with the snake_case filter interface of
 ``ReflectorEKFSLAM`` (each call a one-event submit), for code that drives one robot at a time.
 
 All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fallback.
@@ -17,7 +18,7 @@ import numpy as np
 from . import _lib
 from .ekf_slam import ReflectorMatchResult, RekfError, State
 
-RFLEET_ABI_VERSION = 1        # must equal RFLEET_ABI_VERSION of include/rfleet.h and rfleet_abi_version() of the built library
+RFLEET_ABI_VERSION = 2        # must equal RFLEET_ABI_VERSION of include/rfleet.h and rfleet_abi_version() of the built library
 MAX_LANDMARKS = 128
 MAX_OBS = 32
 EV_ODOM, EV_SCAN = 0, 1
@@ -26,7 +27,7 @@ EV_ODOM, EV_SCAN = 0, 1
 class RfleetEvent(C.Structure):
     """struct rfleet_event (include/rfleet.h)."""
     _fields_ = [("member", C.c_int), ("kind", C.c_int), ("t", C.c_double), ("v", C.c_double * 3),
-                ("xy", C.c_void_p), ("K", C.c_int)]
+                ("xy", C.c_void_p), ("K", C.c_int), ("has_pose_fix", C.c_int), ("pose_fix", C.c_double * 3)]
 
 
 _rfleet = None
@@ -48,6 +49,10 @@ def rfleet():
     if have != RFLEET_ABI_VERSION:
         raise _lib.LibraryMissing(f"{path} has ABI version {have}, this package speaks {RFLEET_ABI_VERSION}: rebuild it "
                                   "(python __graft_entry__.py); there is no CPU fallback")
+    L.rfleet_sizeof_event.restype = C.c_int
+    if L.rfleet_sizeof_event() != C.sizeof(RfleetEvent):
+        raise _lib.LibraryMissing(f"{path}: struct rfleet_event has {L.rfleet_sizeof_event()} bytes, this package packs "
+                                  f"{C.sizeof(RfleetEvent)}: rebuild it (python __graft_entry__.py)")
     L.rfleet_last_hip_error.restype = C.c_char_p
     L.rfleet_last_hip_error.argtypes = [vp]
     L.rfleet_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -55,6 +60,7 @@ def rfleet():
     L.rfleet_destroy.restype = None
     L.rfleet_submit.argtypes = [vp, vp, C.c_int]
     L.rfleet_get_poses.argtypes = [vp, vp, vp, vp]
+    L.rfleet_predict_poses.argtypes = [vp, vp, vp, vp]
     L.rfleet_get_n.argtypes = [vp, vp]
     L.rfleet_get_flags.argtypes = [vp, vp]
     L.rfleet_get_state.argtypes = [vp, C.c_int, vp, ip, vp, C.c_long, vp, C.c_long]
@@ -70,8 +76,11 @@ def odom_event(member, t, vx, vy, wz):
     return (int(member), EV_ODOM, float(t), (float(vx), float(vy), float(wz)), None)
 
 
-def scan_event(member, t, cloud):
-    return (int(member), EV_SCAN, float(t), (0.0, 0.0, 0.0), cloud)
+def scan_event(member, t, cloud, pose_fix=None):
+    """pose_fix: (x, y, yaw) of an absolute pose observation taken at the scan's time (reflector_ekf_slam_gps.cc:305-340), or None."""
+    if pose_fix is None:
+        return (int(member), EV_SCAN, float(t), (0.0, 0.0, 0.0), cloud)
+    return (int(member), EV_SCAN, float(t), (0.0, 0.0, 0.0), cloud, tuple(float(v) for v in pose_fix))
 
 
 class ReflectorEKFSLAMFleet:
@@ -123,8 +132,8 @@ class ReflectorEKFSLAMFleet:
     # -- the fleet interface --------------------------------------------------
     @staticmethod
     def pack(events):
-        """events: iterable of (member, kind, t, (vx, vy, wz), cloud or None) -- see ``odom_event`` / ``scan_event`` -- or
-        ``RfleetEvent``s.  -> (ctypes array, the float32 arrays it points into): reusable with ``submit_packed``."""
+        """events: iterable of (member, kind, t, (vx, vy, wz), cloud or None[, pose fix (x, y, yaw) or None]) -- see
+        ``odom_event`` / ``scan_event`` -- or ``RfleetEvent``s.  -> (ctypes array, the float32 arrays it points into): reusable with ``submit_packed``."""
         events = list(events)
         arr = (RfleetEvent * max(len(events), 1))()
         keep = []
@@ -132,7 +141,8 @@ class ReflectorEKFSLAMFleet:
             if isinstance(ev, RfleetEvent):
                 arr[i] = ev
                 continue
-            member, kind, t, v, cloud = ev
+            member, kind, t, v, cloud = ev[:5]
+            fix = ev[5] if len(ev) > 5 else None
             e = arr[i]
             e.member, e.kind, e.t = int(member), int(kind), float(t)
             e.v[0], e.v[1], e.v[2] = float(v[0]), float(v[1]), float(v[2])
@@ -144,6 +154,9 @@ class ReflectorEKFSLAMFleet:
                 keep.append(cloud)
                 e.xy = cloud.ctypes.data if cloud.size else None
                 e.K = cloud.size >> 1
+            if fix is not None:
+                e.has_pose_fix = 1
+                e.pose_fix[0], e.pose_fix[1], e.pose_fix[2] = float(fix[0]), float(fix[1]), float(fix[2])
         return arr, len(events), keep
 
     def submit_code(self, events) -> int:
@@ -168,6 +181,15 @@ class ReflectorEKFSLAMFleet:
         sg = np.zeros((self.B, 9))
         self._chk(self._L.rfleet_get_poses(self._h, t.ctypes.data, mu.ctypes.data, sg.ctypes.data), "rfleet_get_poses")
         return t, mu, sg.reshape(self.B, 3, 3).transpose(0, 2, 1).copy()
+
+    def predict_poses(self, times):
+        """PredictState's pose block of every member at ``times`` (a scalar or [B]): -> (mu [B, 3], sigma [B, 3, 3]), from each
+        member's state time with its last odometry velocity.  Non-mutating; synchronises, launches nothing."""
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(times, dtype=np.float64), (self.B,)))
+        mu = np.zeros((self.B, 3))
+        sg = np.zeros((self.B, 9))
+        self._chk(self._L.rfleet_predict_poses(self._h, t.ctypes.data, mu.ctypes.data, sg.ctypes.data), "rfleet_predict_poses")
+        return mu, sg.reshape(self.B, 3, 3).transpose(0, 2, 1).copy()
 
     def n(self) -> np.ndarray:
         out = np.zeros(self.B, np.int32)
@@ -231,9 +253,14 @@ class FleetMember:
         self.fleet.submit([odom_event(self.index, t, vx, vy, wz)])
 
     def handle_observation(self, t, cloud, gps_pose=None):
-        if gps_pose is not None:
-            raise ValueError("the fleet filter has no pose observation (include/rfleet.h: out of scope)")
-        self.fleet.submit([scan_event(self.index, t, cloud)])
+        self.fleet.submit([scan_event(self.index, t, cloud, gps_pose)])
+
+    def PredictState(self, t):
+        """-> (mu3, sigma 3 x 3): the pose block of PredictState(t).  Evaluates every member's (host arithmetic on B poses)."""
+        t_now = self.fleet.poses()[0]
+        t_now[self.index] = float(t)
+        mu, sg = self.fleet.predict_poses(t_now)
+        return mu[self.index].copy(), sg[self.index].copy()
 
     @property
     def n(self) -> int:

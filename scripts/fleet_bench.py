@@ -4,12 +4,15 @@
 * ``handles``: the same scans through B ReflectorEKFSLAM handles (max_landmarks=128, auto_grow=False) fed round-robin from
   this thread -- what bench.py's multi_session does and the only way to serve a fleet without the fleet filter.
 
-Both legs run in the same process, alternating, --reps repetitions each; every repetition restarts from the same built maps
+* ``fleet_pose_fix`` (opt-in, --pose-fix; B = 64 and 256): the fleet leg with an absolute pose fix on every scan (the
+  USE_GPS deployment: three more rows on each member's update), next to the plain fleet leg of the same size.
+
+All legs run in the same process, alternating, --reps repetitions each; every repetition restarts from the same built maps
 (set_state), warms up and then times --ticks ticks with the host clock around work that ends in a synchronisation.  Prints
 ONE JSON line (and writes it to --out) with the aggregate updates/s (min / median / max), us per tick, the largest
 |mu - handles' mu| per member at the end, and the SHA-256 of the fleet sources it was measured on.
 
-  python scripts/fleet_bench.py --out profiles/fleet_bench.json
+  python scripts/fleet_bench.py --pose-fix --out profiles/fleet_bench.json
   rocprofv3 --kernel-trace --stats -d DIR -- python scripts/fleet_bench.py --only-fleet 256 --reps 1     (k_fleet_step's own time)
 """
 from __future__ import annotations
@@ -30,6 +33,8 @@ if ROOT not in sys.path:
 SOURCES = ["include/rfleet.h", "reflector_ekf_slam_amd/csrc/fleet_dev.h", "reflector_ekf_slam_amd/csrc/fleet_kernels.hip",
            "reflector_ekf_slam_amd/csrc/rfleet_api.hip", "reflector_ekf_slam_amd/fleet.py", "scripts/fleet_bench.py"]
 N_SEEDS = 8
+POSE_FIX_SIZES = (64, 256)
+FIX_SIGMA = (0.05, 0.05, 0.017)
 
 
 def build_maps(ticks_total):
@@ -64,6 +69,26 @@ def build_maps(ticks_total):
     return sessions, snaps, steady
 
 
+def make_fixes(sessions, snaps, steady, total):
+    """One fix per seed and tick, as a scan matcher started from PredictState would hand it back: the pose predict_poses gives
+    at the scan's time plus seeded noise, drawn on a run of the eight maps that applies them."""
+    from reflector_ekf_slam_amd import ReflectorEKFSLAMFleet
+    from reflector_ekf_slam_amd import session as S
+    fl = ReflectorEKFSLAMFleet([S.options_for(s) for s in sessions], max_landmarks=128)
+    for i, st in enumerate(snaps):
+        fl.set_state(i, st.time, st.mu, st.sigma)
+    rng = np.random.default_rng(7900)
+    fixes = []
+    for k in range(total):
+        mu, _ = fl.predict_poses([steady[i][k][0] for i in range(N_SEEDS)])
+        fx = mu + rng.normal(size=mu.shape) * FIX_SIGMA
+        fixes.append(fx)
+        fl.submit([(i, 1, steady[i][k][0], (0.0, 0.0, 0.0), steady[i][k][1], tuple(fx[i])) for i in range(N_SEEDS)])
+    assert not fl.flags().any()
+    fl.close()
+    return fixes
+
+
 def stats(rates):
     r = sorted(rates)
     return {"min": r[0], "median": float(np.median(r)), "max": r[-1]}
@@ -77,6 +102,7 @@ def main():
     ap.add_argument("--fleet-sizes", type=int, nargs="*", default=[4, 64, 256])
     ap.add_argument("--handle-sizes", type=int, nargs="*", default=[4, 64])
     ap.add_argument("--only-fleet", type=int, default=0, help="run the fleet leg at this size only (profiling runs)")
+    ap.add_argument("--pose-fix", action="store_true", help="add the fleet leg with a pose fix on every scan (B = 64, 256)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if args.only_fleet:
@@ -89,6 +115,10 @@ def main():
     result = {"workload": "B members, each SessionConfig(n_landmarks=128, obs_per_scan=16), seeds 7000 + i mod 8; maps built, then one "
                           "steady-state scan per member per tick", "ticks": args.ticks, "warmup": args.warmup, "reps": args.reps,
               "unit": "updates/s (aggregate, one GPU, one host thread)", "fleet": {}, "handles": {}, "max_abs_mu_diff": {}}
+    fixes = None
+    if args.pose_fix:
+        fixes = make_fixes(sessions, snaps, steady, total)
+        result["fleet_pose_fix"] = {}
 
     for B in sorted(set(args.fleet_sizes) | set(args.handle_sizes)):
         fl = handles = None
@@ -96,10 +126,26 @@ def main():
             fl = ReflectorEKFSLAMFleet([S.options_for(sessions[b % N_SEEDS]) for b in range(B)], max_landmarks=128)
             packed = [fl.pack([(b, 1, steady[b % N_SEEDS][k][0], (0.0, 0.0, 0.0), steady[b % N_SEEDS][k][1]) for b in range(B)])
                       for k in range(total)]
+        packed_fix = None
+        if fl is not None and fixes is not None and B in POSE_FIX_SIZES:
+            packed_fix = [fl.pack([(b, 1, steady[b % N_SEEDS][k][0], (0.0, 0.0, 0.0), steady[b % N_SEEDS][k][1], tuple(fixes[k][b % N_SEEDS]))
+                                   for b in range(B)]) for k in range(total)]
         if B in args.handle_sizes:
             handles = [ReflectorEKFSLAM(S.options_for(sessions[b % N_SEEDS]), max_landmarks=128, device=0, auto_grow=False) for b in range(B)]
-        rf, rh = [], []
+        rf, rh, rp = [], [], []
         for _ in range(args.reps):
+            if packed_fix is not None:                       # (first: the fleet's final state is the plain leg's)
+                for b in range(B):
+                    st = snaps[b % N_SEEDS]
+                    fl.set_state(b, st.time, st.mu, st.sigma)
+                for k in range(args.warmup):
+                    fl.submit_packed(packed_fix[k])
+                fl.sync()
+                t0 = time.perf_counter()
+                for k in range(args.warmup, total):
+                    fl.submit_packed(packed_fix[k])
+                fl.sync()
+                rp.append(B * args.ticks / (time.perf_counter() - t0))
             if fl is not None:
                 for b in range(B):
                     st = snaps[b % N_SEEDS]
@@ -131,6 +177,10 @@ def main():
                 rh.append(B * args.ticks / (time.perf_counter() - t0))
         if fl is not None:
             result["fleet"][str(B)] = dict(stats(rf), us_per_tick=1e6 * B / float(np.median(rf)), flags_any=bool(fl.flags().any()))
+        if packed_fix is not None:
+            us_fix, us_plain = 1e6 * B / float(np.median(rp)), 1e6 * B / float(np.median(rf))
+            result["fleet_pose_fix"][str(B)] = dict(stats(rp), us_per_tick=us_fix, extra_us_per_tick_over_plain=us_fix - us_plain,
+                                                    flags_any=bool(fl.flags().any()))
         if handles is not None:
             result["handles"][str(B)] = dict(stats(rh), us_per_tick=1e6 * B / float(np.median(rh)))
         if fl is not None and handles is not None:
