@@ -2,7 +2,8 @@
 CPU references against each other) and tests/test_fleet_edges_gpu.py (k_fleet_step against the longdouble witness).
 
 A case is a plain record: the filter's options, ``max_landmarks``, a state (t, mu, P, vt) to write with ``set_state``, a list
-of events ``(kind, t, (vx, vy, wz), cloud or None)`` and what the case claims about itself: per scan the association lists
+of events ``(kind, t, (vx, vy, wz), cloud or None)``, with the pose fix of a scan or None as an optional fifth element
+(tests/fleet_pose_cases.py), and what the case claims about itself: per scan the association lists
 (``expect``) and per observation the margins |d1 - 0.6| and d2 - d1 of ReflectorMatch's state branch (``margins``).
 numpy only; nothing here needs a GPU.
 
@@ -45,11 +46,11 @@ GPU_FACTOR = 16.0
 MU_TOL, SIGMA_TOL = 1e-9, 1e-11          # the absolute tolerances of tests/test_fleet_gpu.py: the bound is never looser
 
 
-def gpu_bounds(mu_ref, P_ref):
-    """The GPU test's bounds on (max|dsigma| / max|sigma_ref|, max|dmu| / max(1, max|mu_ref|)): GPU_FACTOR x the FP64 floor, and
-    never looser than the absolute tolerances (which bind only where the covariance is large, e.g. far new reflectors)."""
+def gpu_bounds(mu_ref, P_ref, suite):
+    """The GPU test's bounds on (max|dsigma| / max|sigma_ref|, max|dmu| / max(1, max|mu_ref|)): GPU_FACTOR x the suite's FP64
+    floor, and never looser than the absolute tolerances (which bind only where the covariance is large, e.g. far new reflectors)."""
     smax, mmax = float(np.abs(P_ref).max()), max(1.0, float(np.abs(mu_ref).max()))
-    return min(GPU_FACTOR * FP64_FLOOR_SIGMA, SIGMA_TOL / smax), min(GPU_FACTOR * FP64_FLOOR_MU, MU_TOL / mmax)
+    return min(GPU_FACTOR * suite.floor_sigma, SIGMA_TOL / smax), min(GPU_FACTOR * suite.floor_mu, MU_TOL / mmax)
 
 
 # ---- helpers shared with tests/test_fleet_gpu.py ---------------------------------------------------------------------------
@@ -68,15 +69,20 @@ def events_of(sess, stop=None):
 
 
 def feed(filt, ev):
-    kind, t, v, cloud = ev
-    if kind == EV_ODOM:
-        filt.handle_odometry(t, *v)
+    """One event to a filter with the snake_case interface (oracle, numpy, witness, fleet member, single filter)."""
+    if ev[0] == EV_ODOM:
+        filt.handle_odometry(ev[1], *ev[2])
+    elif len(ev) == 4 or ev[4] is None:
+        filt.handle_observation(ev[1], ev[3])
     else:
-        filt.handle_observation(t, cloud)
+        filt.handle_observation(ev[1], ev[3], np.asarray(ev[4], np.float64))
 
 
-def fev(member, ev):
-    return (member, ev[0], ev[1], ev[2], ev[3])
+def fev(member, ev, with_fix=True):
+    """The event as ReflectorEKFSLAMFleet.pack takes it: a 5-tuple, or a 6-tuple when it carries a fix."""
+    if with_fix and len(ev) > 4 and ev[4] is not None:
+        return (member, *ev[:4], tuple(ev[4]))
+    return (member, *ev[:4])
 
 
 def margins(mu_pred, cloud):
@@ -134,6 +140,11 @@ def witness_of(case):
     return w
 
 
+# What differs between the fleet's test suites, for tests/fleet_harness.py: the measured floors and the witnesses (the first is
+# the one the GPU is held to).
+SUITE = NS(name="plain", floor_sigma=FP64_FLOOR_SIGMA, floor_mu=FP64_FLOOR_MU, witnesses={"witness": witness_of})
+
+
 def kept_cloud(case, k):
     """Scan k's cloud as a filter WITHOUT capacity limit has to see it: the observations the capacity guard drops removed."""
     cloud = case.events[k][3]
@@ -142,12 +153,13 @@ def kept_cloud(case, k):
 
 
 def reference_events(case):
-    """The case's events for a reference that knows no capacity (dropped observations removed) and no use_imu switch."""
+    """The case's events for a reference that knows no capacity (dropped observations removed) and no use_imu switch; a
+    fix stays."""
     out = []
     for k, ev in enumerate(case.events):
         if ev[0] == EV_ODOM and case.use_imu:
             continue
-        out.append((ev[0], ev[1], ev[2], kept_cloud(case, k) if ev[0] == EV_SCAN else None))
+        out.append((ev[0], ev[1], ev[2], kept_cloud(case, k) if ev[0] == EV_SCAN else None, *ev[4:]))
     return out
 
 

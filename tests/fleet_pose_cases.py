@@ -1,7 +1,7 @@
 """Cases of the fleet filter's pose fixes (the reference's USE_GPS branch, reflector_ekf_slam_gps.cc:305-340), shared by
 tests/test_fleet_pose_cpu.py (the cases and the CPU references against each other) and tests/test_fleet_pose_gpu.py
-(k_fleet_step against them).  Built on tests/fleet_cases.py: a case is that module's record with 5-tuple events
-``(kind, t, (vx, vy, wz), cloud or None, fix or None)``.
+(k_fleet_step against them).  Built on tests/fleet_cases.py: a case is that module's record, every event with its fifth
+element ``(kind, t, (vx, vy, wz), cloud or None, fix or None)``; feeding and packing them is that module's ``feed`` / ``fev``.
 
 A fix is the pose of ``predict_state(t)`` of oracle/ekf_numpy.py on the case's own events, plus seeded noise of
 (0.05 m, 0.05 m, 0.017 rad): what a scan matcher started from that pose hands back.
@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import copy
 import math
+from types import SimpleNamespace as NS
 
 import numpy as np
 
@@ -31,31 +32,6 @@ SESSION_MARGIN_MIN = 1e-6
 # below.  Recorded = measured, rounded up to two digits; the test fails when a re-measurement exceeds it or falls below half.
 FP64_FLOOR_SIGMA = 9.5e-12    # measured 9.498e-12 (pose_L32_MM32_N0_omni_fix scan 1, oracle)
 FP64_FLOOR_MU = 3.0e-16       # measured 2.962e-16 (capacity_room1_fix scan 1, numpy)
-GPU_FACTOR = FC.GPU_FACTOR
-
-
-def gpu_bounds(mu_ref, P_ref):
-    """As fleet_cases.gpu_bounds with this module's floor: GPU_FACTOR x the floor, capped by the fleet's absolute tolerances."""
-    smax, mmax = float(np.abs(P_ref).max()), max(1.0, float(np.abs(mu_ref).max()))
-    return min(GPU_FACTOR * FP64_FLOOR_SIGMA, FC.SIGMA_TOL / smax), min(GPU_FACTOR * FP64_FLOOR_MU, FC.MU_TOL / mmax)
-
-
-# ---- feeding ---------------------------------------------------------------------------------------------------------------
-def feed(filt, ev):
-    """One event to a filter with the snake_case interface (oracle, numpy, witness, fleet member, single filter)."""
-    if ev[0] == EV_ODOM:
-        filt.handle_odometry(ev[1], *ev[2])
-    elif ev[4] is None:
-        filt.handle_observation(ev[1], ev[3])
-    else:
-        filt.handle_observation(ev[1], ev[3], np.asarray(ev[4], np.float64))
-
-
-def fev(member, ev, with_fix=True):
-    """The event as ReflectorEKFSLAMFleet.pack takes it: a 5-tuple, or a 6-tuple when it carries a fix."""
-    if ev[0] == EV_SCAN and ev[4] is not None and with_fix:
-        return (member, ev[0], ev[1], ev[2], ev[3], tuple(ev[4]))
-    return (member, ev[0], ev[1], ev[2], ev[3])
 
 
 def pose_witness_of(case, form="joint"):
@@ -65,14 +41,8 @@ def pose_witness_of(case, form="joint"):
     return w
 
 
-def reference_events(case):
-    """As fleet_cases.reference_events (observations the capacity guard drops removed, no use_imu switch), fixes kept."""
-    out = []
-    for k, ev in enumerate(case.events):
-        if ev[0] == EV_ODOM and case.use_imu:
-            continue
-        out.append((ev[0], ev[1], ev[2], FC.kept_cloud(case, k) if ev[0] == EV_SCAN else None, ev[4]))
-    return out
+SUITE = NS(name="pose", floor_sigma=FP64_FLOOR_SIGMA, floor_mu=FP64_FLOOR_MU,
+           witnesses={"witness": pose_witness_of, "two_step": lambda case: pose_witness_of(case, "two_step")})
 
 
 def attach_fixes(case, seed, which=None, offset=None):
@@ -157,7 +127,7 @@ def heading_fix_cases():
         for k, ev in enumerate(events):
             if ev[0] == EV_SCAN:
                 case.margins[k] = FC.margins(ek.predict_state(ev[1])[0], ev[3])
-            feed(ek, ev)
+            FC.feed(ek, ev)
         out.append(case)
     return out
 
@@ -191,7 +161,6 @@ def sessions():
     global _sessions
     if _sessions is not None:
         return _sessions
-    from types import SimpleNamespace as NS
     from reflector_ekf_slam_amd import synth
     from reflector_ekf_slam_amd import session as S
     from tests.helpers import make_oracle, norm_match
@@ -214,7 +183,7 @@ def sessions():
                 events.append(tuple(ev) + (fix,))
                 margins[k] = FC.margins(mu_p, ev[3])
                 scan += 1
-            feed(o, events[-1])
+            FC.feed(o, events[-1])
             if ev[0] == EV_SCAN:
                 sp, _, nw = norm_match(o.last_match())
                 records[k] = (sp, nw, o.mu())

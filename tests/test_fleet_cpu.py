@@ -8,15 +8,10 @@ import json
 import os
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rfleet.h")
+from tests.fleet_harness import HEADER, ROOT, _lib
+
 FLEET_SOURCES = ["include/rfleet.h", "reflector_ekf_slam_amd/csrc/fleet_dev.h", "reflector_ekf_slam_amd/csrc/fleet_kernels.hip",
                  "reflector_ekf_slam_amd/csrc/rfleet_api.hip", "reflector_ekf_slam_amd/fleet.py", "scripts/fleet_bench.py"]
-
-
-def _lib():
-    from reflector_ekf_slam_amd import fleet
-    return fleet.rfleet()
 
 
 def test_every_declared_symbol_is_exported():

@@ -9,45 +9,10 @@ import numpy as np
 import pytest
 
 from tests import fleet_cases as FC
-from tests.helpers import norm_match
+from tests import fleet_harness as H
 from tests.witness import fleet_witness as FW
 
 pytestmark = pytest.mark.skipif(not FW.available(), reason="numpy.longdouble has no 64-bit mantissa on this platform")
-
-
-def rel_err(mu, P, mu_ref, P_ref):
-    """(max|dsigma| / max|sigma_ref|, max|dmu| / max(1, max|mu_ref|)) against the longdouble witness."""
-    ds = float(np.abs(np.asarray(P, np.longdouble) - P_ref).max() / np.abs(P_ref).max())
-    dm = float(np.abs(np.asarray(mu, np.longdouble) - mu_ref).max() / max(1.0, float(np.abs(mu_ref).max())))
-    return ds, dm
-
-
-def run_references(case):
-    """Feeds the case's reference events to the three CPU filters; -> per scan event k: (witness state, oracle state, numpy state)
-    and checks the association lists of all three against the case's claim."""
-    o, e, w = FC.oracle_of(case), FC.numpy_of(case), FC.witness_of(case)
-    out = {}
-    k_of = [k for k, ev in enumerate(case.events) if not (ev[0] == FC.EV_ODOM and case.use_imu)]
-    for k, ev in zip(k_of, FC.reference_events(case)):
-        for f in (o, e, w):
-            FC.feed(f, ev)
-        if ev[0] != FC.EV_SCAN:
-            continue
-        want_p, want_n = case.expect[k]
-        want_p, want_n = np.asarray(want_p, np.int32).reshape(-1, 2), np.asarray(want_n, np.int32).reshape(-1)
-        so, _, no = norm_match(o.last_match())
-        lists = {"oracle": FC.map_back(case, k, so, no), "numpy": FC.map_back(case, k, e.last_match[1], e.last_match[2]),
-                 "witness": FC.map_back(case, k, *w.last_match)}
-        for who, (p, nw) in lists.items():
-            assert np.array_equal(p, want_p) and np.array_equal(nw, want_n), (case.name, k, who, p.tolist(), nw.tolist())
-        # the references know no capacity: a claimed "new" must fit the member's map, a dropped one must meet a full map
-        L_after = (w.state()[0].shape[0] - 3) // 2
-        assert L_after <= case.max_landmarks, (case.name, k, L_after, case.max_landmarks)
-        if k in case.kept:
-            assert L_after == case.max_landmarks and len(case.kept[k]) < len(case.events[k][3]) and case.flags == FC.FLAG_CAPACITY
-        out[k] = (w.state(), o.state(), (e.mu.copy(), e.sigma.copy()))
-    o.close()
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +22,7 @@ def all_cases():
 
 @pytest.fixture(scope="module")
 def reference_runs(all_cases):
-    return {c.name: run_references(c) for c in all_cases}
+    return {c.name: H.run_references(c, FC.SUITE) for c in all_cases}
 
 
 def test_associations_agree_and_are_the_claimed_ones(all_cases, reference_runs):
@@ -174,31 +139,13 @@ def test_witness_is_pinned_by_mpmath():
     assert worst < 1e-17
 
 
-def measure_floor(all_cases, reference_runs):
-    ws, wm = (0.0, ""), (0.0, "")
-    for c in all_cases:
-        for k, (wit, orc, npy) in reference_runs[c.name].items():
-            for who, (mu, P) in (("oracle", orc), ("numpy", npy)):
-                es, em = rel_err(mu, P, *wit)
-                ws = max(ws, (es, f"{c.name} scan {k} ({who})"))
-                wm = max(wm, (em, f"{c.name} scan {k} ({who})"))
-    return ws, wm
-
-
 def test_fp64_floor(all_cases, reference_runs):
-    ws, wm = measure_floor(all_cases, reference_runs)
-    print(f"\nFP64 floor over {len(all_cases)} cases: sigma {ws[0]:.3e} at {ws[1]}; mu {wm[0]:.3e} at {wm[1]}")
-    print(f"recorded: sigma {FC.FP64_FLOOR_SIGMA:.3e} ({FC.FP64_FLOOR_SIGMA_CASE}), mu {FC.FP64_FLOOR_MU:.3e} ({FC.FP64_FLOOR_MU_CASE})")
-    assert ws[0] <= FC.FP64_FLOOR_SIGMA and wm[0] <= FC.FP64_FLOOR_MU
-    assert ws[0] >= FC.FP64_FLOOR_SIGMA / 2 and wm[0] >= FC.FP64_FLOOR_MU / 2, "the recorded floor is stale: far above what is measured"
-    # the GPU bound is never looser than the absolute tolerances of tests/test_fleet_gpu.py
+    H.measure_floor(all_cases, reference_runs, FC.SUITE)
+    print(f"recorded at: sigma {FC.FP64_FLOOR_SIGMA_CASE}, mu {FC.FP64_FLOOR_MU_CASE}")
     for c in all_cases:
-        for k, (wit, _, _) in reference_runs[c.name].items():
-            bs, bm = FC.gpu_bounds(*wit)
-            assert bs * float(np.abs(wit[1]).max()) <= FC.SIGMA_TOL * (1 + 1e-12) and bs <= FC.GPU_FACTOR * FC.FP64_FLOOR_SIGMA
-            assert bm * max(1.0, float(np.abs(wit[0]).max())) <= FC.MU_TOL * (1 + 1e-12) and bm <= FC.GPU_FACTOR * FC.FP64_FLOOR_MU
-            if c.kind == "sweep":                              # in the sweep the floor is what binds, not the absolute tolerance
-                assert bs == FC.GPU_FACTOR * FC.FP64_FLOOR_SIGMA and bm == FC.GPU_FACTOR * FC.FP64_FLOOR_MU, (c.name, k)
+        if c.kind == "sweep":                                  # in the sweep the floor is what binds, not the absolute tolerance
+            for k, (wits, _, _) in reference_runs[c.name].items():
+                assert FC.gpu_bounds(*wits[0], FC.SUITE) == (FC.GPU_FACTOR * FC.FP64_FLOOR_SIGMA, FC.GPU_FACTOR * FC.FP64_FLOOR_MU), (c.name, k)
 
 
 def pick(cs, pred):
@@ -223,7 +170,7 @@ def test_the_bound_can_fail(mutation):
     ev = c.events[0]
     good.handle_observation(ev[1], ev[3])
     bad.handle_observation(ev[1], ev[3], mutate=mutation, where=where)
-    es = float(np.abs(bad.sigma - good.sigma).max() / np.abs(good.sigma).max())
-    bound = FC.GPU_FACTOR * FC.FP64_FLOOR_SIGMA
+    es, _ = H.rel_err(bad.mu, bad.sigma, good.mu, good.sigma)
+    bound, _ = FC.gpu_bounds(good.mu, good.sigma, FC.SUITE)
     print(f"\n{mutation} on {c.name}: sigma moves by {es:.3e} = {es / bound:.3g} x the GPU bound {bound:.3e}")
     assert es >= 100 * bound

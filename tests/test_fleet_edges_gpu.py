@@ -3,7 +3,7 @@
 
 Association lists, n and flags must be identical; max|dsigma| / max|sigma_ref| and max|dmu| / max(1, max|mu_ref|) must stay
 within 16 x the FP64 noise floor that tests/test_fleet_edges_cpu.py measures between the CPU restatements and the witness
-(fleet_cases.gpu_bounds; never looser than the 1e-9 / 1e-11 of tests/test_fleet_gpu.py).  The kernel sums in another order
+(fleet_harness.check_member, fleet_cases.gpu_bounds; never looser than the 1e-9 / 1e-11 of tests/test_fleet_gpu.py).  The kernel sums in another order
 than either CPU restatement (4-deep MFMA chains, Gauss-Jordan without pivoting) at the same depth, so a single-digit factor
 is what rounding explains; the planted defects of the CPU module exceed the bound by 1e7 and more."""
 from __future__ import annotations
@@ -16,65 +16,11 @@ import pytest
 from reflector_ekf_slam_amd import synth
 from reflector_ekf_slam_amd import session as S
 from tests import fleet_cases as FC
+from tests.fleet_harness import fleet_mod, make_fleet, run_lockstep
 from tests.helpers import make_gpu, make_oracle, norm_match
 from tests.witness import fleet_witness as FW
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not FW.available(), reason="numpy.longdouble has no 64-bit mantissa here")]
-
-
-def fleet_mod():
-    from reflector_ekf_slam_amd import fleet
-    return fleet
-
-
-def make_fleet(cases, max_landmarks=128):
-    fl = fleet_mod().ReflectorEKFSLAMFleet([FC.options_of(c) for c in cases], max_landmarks=max_landmarks)
-    for i, c in enumerate(cases):
-        fl.set_state(i, c.t, c.mu, c.P, c.vt)
-    return fl
-
-
-def check_member(fl, i, case, k, wit, flags=0):
-    """Member i after scan event k of its case against the witness `wit` (already fed the same events).  -> (sigma error,
-    mu error) as multiples of the FP64 floor."""
-    sp, mp, nw = norm_match(fl.last_match(i))
-    want_p, want_n = case.expect[k]
-    assert mp.shape[0] == 0
-    assert np.array_equal(sp, np.asarray(want_p, np.int32).reshape(-1, 2)), (case.name, k, sp.tolist(), want_p)
-    assert np.array_equal(nw, np.asarray(want_n, np.int32).reshape(-1)), (case.name, k, nw.tolist(), want_n)
-    mu_ref, P_ref = wit.state()
-    st = fl.get_state(i)
-    assert st.mu.shape[0] == mu_ref.shape[0] == int(fl.n()[i]), (case.name, k, st.mu.shape, mu_ref.shape)
-    assert int(fl.flags()[i]) == flags, (case.name, k, int(fl.flags()[i]))
-    assert np.array_equal(st.sigma, st.sigma.T), (case.name, k, "sigma is not exactly symmetric as returned")
-    es = float(np.abs(st.sigma.astype(np.longdouble) - P_ref).max() / np.abs(P_ref).max())
-    em = float(np.abs(st.mu.astype(np.longdouble) - mu_ref).max() / max(1.0, float(np.abs(mu_ref).max())))
-    bs, bm = FC.gpu_bounds(mu_ref, P_ref)
-    assert bs * float(np.abs(P_ref).max()) <= FC.SIGMA_TOL * (1 + 1e-12) and bm * max(1.0, float(np.abs(mu_ref).max())) <= FC.MU_TOL * (1 + 1e-12)
-    assert es <= bs, f"{case.name} scan {k}: sigma off by {es:.3e} = {es / FC.FP64_FLOOR_SIGMA:.1f} x the FP64 floor (bound {bs:.3e})"
-    assert em <= bm, f"{case.name} scan {k}: mu off by {em:.3e} = {em / FC.FP64_FLOOR_MU:.1f} x the FP64 floor (bound {bm:.3e})"
-    return es / FC.FP64_FLOOR_SIGMA, em / FC.FP64_FLOOR_MU
-
-
-def run_lockstep(cases, max_landmarks=128):
-    """All cases as members of ONE fleet; tick k submits event k of every member in one call; every scan is checked."""
-    fl = make_fleet(cases, max_landmarks)
-    wits = [FC.witness_of(c) for c in cases]
-    refs = [FC.reference_events(c) for c in cases]
-    worst_s, worst_m = (0.0, ""), (0.0, "")
-    try:
-        for k in range(max(len(c.events) for c in cases)):
-            fl.submit([FC.fev(i, c.events[k]) for i, c in enumerate(cases) if k < len(c.events)])
-            for i, c in enumerate(cases):
-                if k >= len(c.events):
-                    continue
-                FC.feed(wits[i], refs[i][k])
-                if c.events[k][0] == FC.EV_SCAN:
-                    fs, fm = check_member(fl, i, c, k, wits[i], getattr(c, "flags", 0))
-                    worst_s, worst_m = max(worst_s, (fs, f"{c.name} scan {k}")), max(worst_m, (fm, f"{c.name} scan {k}"))
-    finally:
-        fl.close()
-    return worst_s, worst_m
 
 
 def test_shape_sweep_in_one_fleet():
@@ -82,7 +28,7 @@ def test_shape_sweep_in_one_fleet():
     scan (one more reflector: a stale row written past n by the first scan would show here)."""
     cases = FC.sweep_cases()
     assert all(c.max_landmarks == 128 and len(c.events) == 2 for c in cases)
-    worst_s, worst_m = run_lockstep(cases)
+    worst_s, worst_m = run_lockstep(cases, FC.SUITE)
     print(f"\nsweep of {len(cases)} members: worst sigma error {worst_s[0]:.2f} x the FP64 floor ({worst_s[1]}), "
           f"worst mu error {worst_m[0]:.2f} x ({worst_m[1]}); the bound is {FC.GPU_FACTOR:.0f} x")
 
@@ -91,7 +37,7 @@ def test_crafted_cases():
     """Gate to the last float32 ulp, exact ties, small and full maps, duplicates, the heading wrap with time going backwards."""
     cases = [c for c in FC.crafted_cases() if c.max_landmarks == 128]
     assert len(cases) >= 17
-    worst_s, worst_m = run_lockstep(cases)
+    worst_s, worst_m = run_lockstep(cases, FC.SUITE)
     print(f"\n{len(cases)} crafted cases: worst sigma error {worst_s[0]:.2f} x the FP64 floor ({worst_s[1]}), "
           f"worst mu error {worst_m[0]:.2f} x ({worst_m[1]})")
 
@@ -103,7 +49,7 @@ def test_capacity_partial_and_full(room):
     c = next(c for c in FC.capacity_cases() if c.room == room)
     n_max = 3 + 2 * c.max_landmarks
     assert c.flags == FC.FLAG_CAPACITY
-    run_lockstep([c], max_landmarks=c.max_landmarks)
+    run_lockstep([c], FC.SUITE, max_landmarks=c.max_landmarks)
     fl = make_fleet([c], c.max_landmarks)
     g = make_gpu(c.model, c.t, c.mu[:3], FC.LIN_COV, FC.ANG_COV, FC.OBS_COV, max_landmarks=c.max_landmarks)
     g.set_state(c.t, c.mu, c.P, c.vt)

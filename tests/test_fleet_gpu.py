@@ -11,6 +11,7 @@ import pytest
 from reflector_ekf_slam_amd import synth
 from reflector_ekf_slam_amd import session as S
 from tests.fleet_cases import events_of, feed, fev, margins, same_bits, state_bits
+from tests.fleet_harness import fleet_mod
 from tests.helpers import make_gpu, make_oracle, norm_match
 
 pytestmark = pytest.mark.gpu
@@ -21,11 +22,6 @@ FLAG_CAPACITY = 1
 # (landmarks, observations per scan, odometry model), seeds 7000 + index
 HETERO = [(128, 16, synth.DIFF), (128, 16, synth.OMNI), (64, 8, synth.DIFF), (96, 32, synth.DIFF), (32, 8, synth.OMNI),
           (128, 32, synth.DIFF)]
-
-
-def fleet_mod():
-    from reflector_ekf_slam_amd import fleet
-    return fleet
 
 
 def oracle_for(sess):

@@ -3,7 +3,7 @@ on every scan, the shape cases of tests/fleet_pose_cases.py against the longdoub
 pattern, parity with the single filter's gps_pose3, the MM == 0 quirk and the argument checks.
 
 Tolerances: MU_TOL = 1e-9 / SIGMA_TOL = 1e-11 of tests/test_fleet_gpu.py against the oracle and the single filter; against the
-witness 16 x the FP64 floor tests/test_fleet_pose_cpu.py measures on these cases (fleet_pose_cases.gpu_bounds)."""
+witness 16 x the FP64 floor tests/test_fleet_pose_cpu.py measures on these cases (fleet_harness.check_member with fleet_pose_cases.SUITE)."""
 from __future__ import annotations
 
 import math
@@ -13,17 +13,13 @@ import pytest
 
 from tests import fleet_cases as FC
 from tests import fleet_pose_cases as PC
+from tests.fleet_harness import fleet_mod, make_fleet, run_lockstep
 from tests.helpers import make_gpu, make_oracle, norm_match
 from tests.witness import fleet_pose_witness as PW
 
 pytestmark = pytest.mark.gpu
 needs_ld = pytest.mark.skipif(not PW.available(), reason="numpy.longdouble has no 64-bit mantissa here")
 PREDICT_MU_TOL, PREDICT_SIGMA_TOL = 1e-12, 1e-13      # tests/test_ekf_gpu.py::test_predict_state_full_omni_with_landmarks
-
-
-def fleet_mod():
-    from reflector_ekf_slam_amd import fleet
-    return fleet
 
 
 def session_fleet(ss, copies=1):
@@ -37,7 +33,7 @@ def sessions_run():
     fl = session_fleet(ss)
     worst_mu, bad, scans = 0.0, [], 0
     for k in range(max(len(s.events) for s in ss)):
-        fl.submit([PC.fev(i, s.events[k]) for i, s in enumerate(ss) if k < len(s.events)])
+        fl.submit([FC.fev(i, s.events[k]) for i, s in enumerate(ss) if k < len(s.events)])
         for i, s in enumerate(ss):
             if k >= len(s.events) or s.events[k][0] != FC.EV_SCAN:
                 continue
@@ -74,63 +70,21 @@ def test_sessions_match_the_oracle_on_every_scan(sessions_run):
     assert not r["flags"].any()
 
 
-def check_member(fl, i, case, k, wit):
-    sp, mp, nw = norm_match(fl.last_match(i))
-    want_p, want_n = case.expect[k]
-    assert mp.shape[0] == 0
-    assert np.array_equal(sp, np.asarray(want_p, np.int32).reshape(-1, 2)), (case.name, k, sp.tolist(), want_p)
-    assert np.array_equal(nw, np.asarray(want_n, np.int32).reshape(-1)), (case.name, k, nw.tolist(), want_n)
-    mu_ref, P_ref = wit.state()
-    st = fl.get_state(i)
-    assert st.mu.shape[0] == mu_ref.shape[0] == int(fl.n()[i]), (case.name, k, st.mu.shape, mu_ref.shape)
-    assert int(fl.flags()[i]) == getattr(case, "flags", 0), (case.name, k, int(fl.flags()[i]))
-    assert np.array_equal(st.sigma, st.sigma.T), (case.name, k)
-    es = float(np.abs(st.sigma.astype(np.longdouble) - P_ref).max() / np.abs(P_ref).max())
-    em = float(np.abs(st.mu.astype(np.longdouble) - mu_ref).max() / max(1.0, float(np.abs(mu_ref).max())))
-    bs, bm = PC.gpu_bounds(mu_ref, P_ref)
-    print(f"  {case.name} scan {k}: sigma {es / PC.FP64_FLOOR_SIGMA:.2f} x the floor, mu {em / PC.FP64_FLOOR_MU:.2f} x")
-    assert es <= bs, f"{case.name} scan {k}: sigma off by {es:.3e} = {es / PC.FP64_FLOOR_SIGMA:.1f} x the FP64 floor (bound {bs:.3e})"
-    assert em <= bm, f"{case.name} scan {k}: mu off by {em:.3e} = {em / PC.FP64_FLOOR_MU:.1f} x the FP64 floor (bound {bm:.3e})"
-    return es / PC.FP64_FLOOR_SIGMA, em / PC.FP64_FLOOR_MU
-
-
-def run_lockstep(cases, max_landmarks=128):
-    fl = fleet_mod().ReflectorEKFSLAMFleet([FC.options_of(c) for c in cases], max_landmarks=max_landmarks)
-    for i, c in enumerate(cases):
-        fl.set_state(i, c.t, c.mu, c.P, c.vt)
-    wits = [PC.pose_witness_of(c) for c in cases]
-    refs = [PC.reference_events(c) for c in cases]
-    worst_s, worst_m = (0.0, ""), (0.0, "")
-    try:
-        for k in range(max(len(c.events) for c in cases)):
-            fl.submit([PC.fev(i, c.events[k]) for i, c in enumerate(cases) if k < len(c.events)])
-            for i, c in enumerate(cases):
-                if k >= len(c.events):
-                    continue
-                PC.feed(wits[i], refs[i][k])
-                if c.events[k][0] == FC.EV_SCAN:
-                    fs, fm = check_member(fl, i, c, k, wits[i])
-                    worst_s, worst_m = max(worst_s, (fs, f"{c.name} scan {k}")), max(worst_m, (fm, f"{c.name} scan {k}"))
-    finally:
-        fl.close()
-    return worst_s, worst_m
-
-
 @needs_ld
 def test_shape_cases_in_one_fleet():
     """0, 5, 15, 17, 63, 65 and 67 rows of the joint system, n mod 16 in {3, 15, 1}, both models, and the heading cases (yaw across
     +-pi, a fix behind a Predict with negative dt), all members of ONE fleet."""
     cases = PC.shape_cases() + PC.heading_fix_cases()
-    worst_s, worst_m = run_lockstep(cases)
+    worst_s, worst_m = run_lockstep(cases, PC.SUITE)
     print(f"\n{len(cases)} pose cases: worst sigma error {worst_s[0]:.2f} x the FP64 floor ({worst_s[1]}), "
-          f"worst mu error {worst_m[0]:.2f} x ({worst_m[1]}); the bound is {PC.GPU_FACTOR:.0f} x")
+          f"worst mu error {worst_m[0]:.2f} x ({worst_m[1]}); the bound is {FC.GPU_FACTOR:.0f} x")
 
 
 @needs_ld
 @pytest.mark.parametrize("room", [1, 2])
 def test_fix_scan_that_fills_the_map(room):
     c = next(c for c in PC.capacity_fix_cases() if c.room == room)
-    run_lockstep([c], max_landmarks=c.max_landmarks)
+    run_lockstep([c], PC.SUITE, max_landmarks=c.max_landmarks)
 
 
 def test_call_pattern_and_neighbours_do_not_change_the_bits(sessions_run):
@@ -139,12 +93,12 @@ def test_call_pattern_and_neighbours_do_not_change_the_bits(sessions_run):
     # one submit per event, alone
     fl = F.ReflectorEKFSLAMFleet([ss[0].options], max_landmarks=32)
     for ev in ss[0].events:
-        fl.submit([PC.fev(0, ev)])
+        fl.submit([FC.fev(0, ev)])
     assert FC.same_bits(FC.state_bits(fl, 0), ref[0]), "a fleet of one, one event per submit, gives other bits"
     fl.close()
     # every event of every member in ONE submit
     fl = session_fleet(ss)
-    fl.submit([PC.fev(i, ev) for i, s in enumerate(ss) for ev in s.events])
+    fl.submit([FC.fev(i, ev) for i, s in enumerate(ss) for ev in s.events])
     for i in range(len(ss)):
         assert FC.same_bits(FC.state_bits(fl, i), ref[i]), f"member {i}: one submit for the whole session gives other bits"
     fl.close()
@@ -152,7 +106,7 @@ def test_call_pattern_and_neighbours_do_not_change_the_bits(sessions_run):
     fl = session_fleet(ss, copies=2)
     rng = np.random.default_rng(11)
     for k in range(max(len(s.events) for s in ss)):
-        tick = [PC.fev(2 * i + c, s.events[k], with_fix=(c == 0)) for i, s in enumerate(ss) for c in (0, 1) if k < len(s.events)]
+        tick = [FC.fev(2 * i + c, s.events[k], with_fix=(c == 0)) for i, s in enumerate(ss) for c in (0, 1) if k < len(s.events)]
         fl.submit([tick[q] for q in rng.permutation(len(tick))])
     for i in range(len(ss)):
         assert FC.same_bits(FC.state_bits(fl, 2 * i), ref[i]), f"member {i}: shuffling and fix-less neighbours changed the bits"
@@ -161,7 +115,7 @@ def test_call_pattern_and_neighbours_do_not_change_the_bits(sessions_run):
     fl.close()
     # has_pose_fix = 0 with garbage in pose_fix: the bits of a plain scan
     fl = F.ReflectorEKFSLAMFleet([ss[2].options], max_landmarks=32)
-    arr, count, keep = F.ReflectorEKFSLAMFleet.pack([PC.fev(0, ev) for ev in ss[2].events])
+    arr, count, keep = F.ReflectorEKFSLAMFleet.pack([FC.fev(0, ev) for ev in ss[2].events])
     for q in range(count):
         assert arr[q].has_pose_fix == 0
         arr[q].pose_fix[0], arr[q].pose_fix[1], arr[q].pose_fix[2] = math.nan, 1e300, -math.inf
@@ -179,8 +133,8 @@ def test_against_the_single_filter(which):
     g = make_gpu(cfg.odom_model, s.sess.init_time, s.sess.init_pose, cfg.sigma_v ** 2, cfg.sigma_w ** 2, cfg.sigma_obs ** 2, max_landmarks=32)
     worst = 0.0
     for ev in s.events:
-        PC.feed(m, ev)
-        PC.feed(g, ev)
+        FC.feed(m, ev)
+        FC.feed(g, ev)
         if ev[0] == FC.EV_SCAN:
             a, b = norm_match(m.last_match()), norm_match(g.last_match())
             assert all(np.array_equal(x, y) for x, y in zip(a, b)), ev[1]
@@ -200,11 +154,8 @@ def test_fix_without_a_match_is_ignored():
     reflectors appended in both."""
     cases = [c for c in PC.shape_cases() if c.MM == 0]
     assert len(cases) >= 4 and any(c.mu.shape[0] == 3 for c in cases)
-    fl = fleet_mod().ReflectorEKFSLAMFleet([FC.options_of(c) for c in cases for _ in (0, 1)], max_landmarks=128)
-    for i, c in enumerate(cases):
-        for q in (0, 1):
-            fl.set_state(2 * i + q, c.t, c.mu, c.P, c.vt)
-    fl.submit([PC.fev(2 * i + q, c.events[0], with_fix=(q == 0)) for i, c in enumerate(cases) for q in (0, 1)])
+    fl = make_fleet([c for c in cases for _ in (0, 1)])
+    fl.submit([FC.fev(2 * i + q, c.events[0], with_fix=(q == 0)) for i, c in enumerate(cases) for q in (0, 1)])
     n = fl.n()
     for i, c in enumerate(cases):
         assert n[2 * i] == n[2 * i + 1] == c.mu.shape[0] + 2 * c.N2 and c.N2 > 0

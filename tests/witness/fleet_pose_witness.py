@@ -15,8 +15,6 @@ longdouble round-off.  The heading is normalised once, after the whole update.  
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 
 from tests.witness.fleet_witness import LDKIT, WitnessEKF, available, chol_inverse  # noqa: F401
@@ -51,22 +49,6 @@ class PoseWitnessEKF(WitnessEKF):
         super().__init__(*a, **kw)
         assert form in ("joint", "two_step")
         self.form = form
-
-    def _reflector_rows(self, obs, pairs):
-        kit, LD = self.kit, self.kit.T
-        N, m = self.mu.shape[0], 2 * len(pairs)
-        th = float(self.mu[2])
-        c, s = LD(math.cos(th)), LD(math.sin(th))
-        H, dz = kit.zeros((m, N)), kit.zeros(m)
-        for i, (l, g) in enumerate(pairs):
-            dx, dy = self.mu[3 + 2 * g] - self.mu[0], self.mu[4 + 2 * g] - self.mu[1]
-            dz[2 * i] = LD(float(obs[l, 0])) - (dx * c + dy * s)
-            dz[2 * i + 1] = LD(float(obs[l, 1])) - (-dx * s + dy * c)
-            H[2 * i, 0:3] = [-c, -s, -dx * s + dy * c]
-            H[2 * i + 1, 0:3] = [s, -c, -dx * c - dy * s]
-            H[2 * i, 3 + 2 * g], H[2 * i, 4 + 2 * g] = c, s
-            H[2 * i + 1, 3 + 2 * g], H[2 * i + 1, 4 + 2 * g] = -s, c
-        return H, dz
 
     def _pose_rows(self, fix, mutate):
         kit, LD = self.kit, self.kit.T
@@ -128,34 +110,3 @@ class PoseWitnessEKF(WitnessEKF):
             self.mu[2] = kit.wrap(self.mu[2])
         if new:
             self._append(obs, new)
-
-    def _append(self, obs, new):
-        """cc:311-364, as WitnessEKF.handle_observation states it."""
-        kit, LD = self.kit, self.kit.T
-        N, N2 = self.mu.shape[0], len(new)
-        Me = N + 2 * N2
-        xe = kit.zeros(Me)
-        xe[:N] = self.mu
-        Sg = kit.zeros((Me, Me))
-        Sg[:N, :N] = self.sigma
-        th = float(self.mu[2])
-        c, s = LD(math.cos(th)), LD(math.sin(th))
-        Gz = kit.zeros((2, 2))
-        Gz[0, 0], Gz[0, 1], Gz[1, 0], Gz[1, 1] = c, -s, s, c
-        Gp = kit.zeros((2 * N2, 3))
-        for i, l in enumerate(new):
-            gx, gy = self.to_global(obs[l])
-            xe[N + 2 * i], xe[N + 2 * i + 1] = LD(float(gx)), LD(float(gy))
-            rx, ry = LD(float(obs[l, 0])), LD(float(obs[l, 1]))
-            Gp[2 * i] = [LD(1), LD(0), -rx * s - ry * c]
-            Gp[2 * i + 1] = [LD(0), LD(1), rx * c - ry * s]
-        Smx = Gp @ self.sigma[0:3, :]
-        RQR = Gz @ (self.q * kit.eye(2)) @ Gz.T
-        Smm = Gp @ self.sigma[0:3, 0:3] @ Gp.T
-        for i in range(N2):
-            for j in range(N2):
-                Smm[2 * i: 2 * i + 2, 2 * j: 2 * j + 2] += RQR
-        Sg[N:, :N] = Smx
-        Sg[:N, N:] = Smx.T
-        Sg[N:, N:] = Smm
-        self.mu, self.sigma = xe, Sg

@@ -189,7 +189,7 @@ class WitnessEKF:
     # -- HandleObservationMessage (cc:229-368) ----------------------------------------------------------------------------
     def handle_observation(self, t, obs, mutate=None, where=None):
         obs = np.asarray(obs, np.float32).reshape(-1, 2)
-        kit, LD = self.kit, self.kit.T
+        kit = self.kit
         self.predict(float(t) - self.time)
         self.time = float(t)
         self.last_match = ([], [])
@@ -197,21 +197,9 @@ class WitnessEKF:
             return
         pairs, new = self.match(obs)
         self.last_match = (pairs, new)
-        MM, N = len(pairs), self.mu.shape[0]
-        if MM > 0:
-            m = 2 * MM
-            th = float(self.mu[2])
-            c, s = LD(math.cos(th)), LD(math.sin(th))
-            H = kit.zeros((m, N))
-            dz = kit.zeros(m)
-            for i, (l, g) in enumerate(pairs):
-                dx, dy = self.mu[3 + 2 * g] - self.mu[0], self.mu[4 + 2 * g] - self.mu[1]
-                dz[2 * i] = LD(float(obs[l, 0])) - (dx * c + dy * s)
-                dz[2 * i + 1] = LD(float(obs[l, 1])) - (-dx * s + dy * c)
-                H[2 * i, 0:3] = [-c, -s, -dx * s + dy * c]
-                H[2 * i + 1, 0:3] = [s, -c, -dx * c - dy * s]
-                H[2 * i, 3 + 2 * g], H[2 * i, 4 + 2 * g] = c, s
-                H[2 * i + 1, 3 + 2 * g], H[2 * i + 1, 4 + 2 * g] = -s, c
+        if pairs:
+            H, dz = self._reflector_rows(obs, pairs)
+            m = H.shape[0]
             W = self.sigma @ H.T
             if mutate == "w_row_shift":
                 i, j = where
@@ -223,33 +211,55 @@ class WitnessEKF:
             self.mu[2] = self.kit.wrap(self.mu[2])
             self.sigma = self.sigma - self._downdate(Kt, W, m, mutate, where)
         if new:
-            N2 = len(new)
-            Me = N + 2 * N2
-            xe = kit.zeros(Me)
-            xe[:N] = self.mu
-            Sg = kit.zeros((Me, Me))
-            Sg[:N, :N] = self.sigma
-            th = float(self.mu[2])
-            c, s = LD(math.cos(th)), LD(math.sin(th))
-            Gz = kit.zeros((2, 2))
-            Gz[0, 0], Gz[0, 1], Gz[1, 0], Gz[1, 1] = c, -s, s, c
-            Gp = kit.zeros((2 * N2, 3))
-            for i, l in enumerate(new):
-                gx, gy = self.to_global(obs[l])
-                xe[N + 2 * i], xe[N + 2 * i + 1] = LD(float(gx)), LD(float(gy))
-                rx, ry = LD(float(obs[l, 0])), LD(float(obs[l, 1]))
-                Gp[2 * i] = [LD(1), LD(0), -rx * s - ry * c]
-                Gp[2 * i + 1] = [LD(0), LD(1), rx * c - ry * s]
-            Smx = Gp @ self.sigma[0:3, :]
-            RQR = Gz @ (self.q * kit.eye(2)) @ Gz.T
-            Smm = Gp @ self.sigma[0:3, 0:3] @ Gp.T
-            for i in range(N2):
-                for j in range(N2):
-                    Smm[2 * i: 2 * i + 2, 2 * j: 2 * j + 2] += RQR          # Gz Qt Gz^T with the stacked Gz (cc:349-354)
-            Sg[N:, :N] = Smx
-            Sg[:N, N:] = Smx.T
-            Sg[N:, N:] = Smm
-            self.mu, self.sigma = xe, Sg
+            self._append(obs, new)
+
+    def _reflector_rows(self, obs, pairs):
+        """H and the innovation dz of the matched observations at the current mean (cc:246-305)."""
+        kit, LD = self.kit, self.kit.T
+        N, m = self.mu.shape[0], 2 * len(pairs)
+        th = float(self.mu[2])
+        c, s = LD(math.cos(th)), LD(math.sin(th))
+        H, dz = kit.zeros((m, N)), kit.zeros(m)
+        for i, (l, g) in enumerate(pairs):
+            dx, dy = self.mu[3 + 2 * g] - self.mu[0], self.mu[4 + 2 * g] - self.mu[1]
+            dz[2 * i] = LD(float(obs[l, 0])) - (dx * c + dy * s)
+            dz[2 * i + 1] = LD(float(obs[l, 1])) - (-dx * s + dy * c)
+            H[2 * i, 0:3] = [-c, -s, -dx * s + dy * c]
+            H[2 * i + 1, 0:3] = [s, -c, -dx * c - dy * s]
+            H[2 * i, 3 + 2 * g], H[2 * i, 4 + 2 * g] = c, s
+            H[2 * i + 1, 3 + 2 * g], H[2 * i + 1, 4 + 2 * g] = -s, c
+        return H, dz
+
+    def _append(self, obs, new):
+        """The new observations become reflectors of the state (cc:311-364)."""
+        kit, LD = self.kit, self.kit.T
+        N, N2 = self.mu.shape[0], len(new)
+        Me = N + 2 * N2
+        xe = kit.zeros(Me)
+        xe[:N] = self.mu
+        Sg = kit.zeros((Me, Me))
+        Sg[:N, :N] = self.sigma
+        th = float(self.mu[2])
+        c, s = LD(math.cos(th)), LD(math.sin(th))
+        Gz = kit.zeros((2, 2))
+        Gz[0, 0], Gz[0, 1], Gz[1, 0], Gz[1, 1] = c, -s, s, c
+        Gp = kit.zeros((2 * N2, 3))
+        for i, l in enumerate(new):
+            gx, gy = self.to_global(obs[l])
+            xe[N + 2 * i], xe[N + 2 * i + 1] = LD(float(gx)), LD(float(gy))
+            rx, ry = LD(float(obs[l, 0])), LD(float(obs[l, 1]))
+            Gp[2 * i] = [LD(1), LD(0), -rx * s - ry * c]
+            Gp[2 * i + 1] = [LD(0), LD(1), rx * c - ry * s]
+        Smx = Gp @ self.sigma[0:3, :]
+        RQR = Gz @ (self.q * kit.eye(2)) @ Gz.T
+        Smm = Gp @ self.sigma[0:3, 0:3] @ Gp.T
+        for i in range(N2):
+            for j in range(N2):
+                Smm[2 * i: 2 * i + 2, 2 * j: 2 * j + 2] += RQR          # Gz Qt Gz^T with the stacked Gz (cc:349-354)
+        Sg[N:, :N] = Smx
+        Sg[:N, N:] = Smx.T
+        Sg[N:, N:] = Smm
+        self.mu, self.sigma = xe, Sg
 
     @staticmethod
     def _downdate(Kt, W, m, mutate, where):
