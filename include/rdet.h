@@ -14,6 +14,11 @@
  * error code, never exit() (the reference exit(-1)s on malformed scans,
  * laser_reflector_detect.cc:27-38), not thread-safe, one HIP stream per handle.  Both
  * handle_* calls are synchronous because the reference interface returns the Observation.
+ *
+ * rdet2d_batch_* is the 2D detector for a fleet host: B members (robots), each with its own options,
+ * sensor_to_base_link and pose extrapolator, and ONE kernel launch per tick that detects one scan
+ * of every member that has one (one workgroup per scan, no workgroup waits for another).  submit
+ * enqueues and returns, collect waits and hands the results back in the order of the call.
  */
 #ifndef RDET_H_
 #define RDET_H_
@@ -69,6 +74,58 @@ int rdet2d_handle_scan(rdet2d_t *h, double stamp, float angle_min, float angle_m
 /* GetRangeData (laser_reflector_detect.h:24): origin + de-skewed returns of the last scan. */
 int rdet2d_get_range_data(rdet2d_t *h, float origin_xy[2], float *returns_xy, int cap_points,
                           int *n_returns);
+
+/* ---- the 2D detector for many robots: one launch per tick (csrc/det2d_batch.hip) ----------------
+ * Member m of a batch handle is one LaserReflectorDetect: options opts[m], sensor_to_base_link
+ * s2b_xyyaw[m], its own odometry.  Results are bit for bit those of B rdet2d handles. */
+typedef struct rdet2d_batch rdet2d_batch_t;
+
+/* one sensor_msgs::LaserScan of one member (the fields HandleLaserScan reads) */
+typedef struct rdet2d_scan {
+    int member;                       /* 0 .. B-1 */
+    double stamp;
+    float angle_min, angle_max, angle_increment, scan_time, range_min, range_max;
+    const float *ranges, *intensities;
+    int N;
+} rdet2d_scan;
+
+/* B >= 1 members, scans of at most max_beams (<= 8192 are detected) beams.  Refused before any HIP
+ * call: null pointers, B < 1, max_beams < 1. */
+int rdet2d_batch_create(const rdet2d_options *opts, const double *s2b_xyyaw, int B, int max_beams,
+                        int device, rdet2d_batch_t **out);
+void rdet2d_batch_destroy(rdet2d_batch_t *b);
+int rdet2d_batch_set_sensor_to_base_link(rdet2d_batch_t *b, int member, const double xyyaw[3]);
+int rdet2d_batch_handle_odometry(rdet2d_batch_t *b, int member, double t, const double pos_xy[2],
+                                 const double quat_zw[2], double vx, double vy, double wz);
+
+/* The member's slice of the device-visible staging area (max_beams floats each).  A scan whose
+ * ranges / intensities pointers are these is read in place by the kernel: a driver may receive
+ * straight into them.  They stay valid for the life of the handle; do not write them between
+ * submit and collect. */
+int rdet2d_batch_staging(rdet2d_batch_t *b, int member, float **ranges, float **intensities);
+
+/* At most one scan per member.  Everything is validated first: a member out of range or named
+ * twice, N < 0, N > 0 with a null pointer, count < 0, null scans with count > 0, a submit that has
+ * not been collected (RDET_ERR_INVALID), N > max_beams or N > 8192 (RDET_ERR_CAPACITY) refuse the
+ * WHOLE call and change nothing (no odometry trimmed).  A call may mix lidars.  A malformed message (range_min < 0, range_max <= range_min,
+ * angle_increment < 0 with angle_max <= angle_min) is data: that scan's status becomes
+ * RDET_ERR_BAD_SCAN with K = 0, the others run.  Enqueues one launch and returns. */
+int rdet2d_batch_submit(rdet2d_batch_t *b, const rdet2d_scan *scans, int count);
+
+/* Waits for the launch; status / K / obs_time (= stamp) / centres of scan i of the submit at
+ * index i (centres at centers_xy + 2 * max_centers * i).  max_centers is capped at
+ * RDET_MAX_CENTERS; a scan with more centres than max_centers gets RDET_ERR_BUFFER and K = 0.
+ * centers_xy may be null when max_centers is 0, obs_time may be null.  RDET_ERR_INVALID when
+ * nothing is submitted, RDET_ERR_HIP (text: rdet2d_batch_last_hip_error) on a device error. */
+int rdet2d_batch_collect(rdet2d_batch_t *b, int *status, int *K, float *centers_xy, int max_centers,
+                         double *obs_time);
+
+/* GetRangeData of the member's last detected scan (members that were not in a call keep theirs).
+ * RDET_ERR_INVALID between submit and collect. */
+int rdet2d_batch_get_range_data(rdet2d_batch_t *b, int member, float origin_xy[2],
+                                float *returns_xy, int cap_points, int *n_returns);
+int rdet2d_batch_sizeof_scan(void);
+const char *rdet2d_batch_last_hip_error(rdet2d_batch_t *b);
 
 /* reflector_detect::PointCloudOptions (point_cloud_reflector_detect.h:37-40) */
 typedef struct rdet3d_options {

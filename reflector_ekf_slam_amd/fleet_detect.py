@@ -1,0 +1,208 @@
+"""Fleet detector: the 2D reflector detector for many robots, ONE kernel launch per tick (rdet2d_batch_* of include/rdet.h).
+
+``LaserReflectorDetectFleet(options_list)`` holds B members, each a reflector_detect::LaserReflectorDetect with its own options,
+sensor_to_base_link and odometry.  ``submit(scans)`` takes at most one ``LaserScan`` per member and enqueues one launch of
+k_det2d_batch (one workgroup per scan); ``collect()`` waits and returns ``(status, Observation)`` per scan, in the order given.
+``scan_events`` turns a tick's result into the events ``ReflectorEKFSLAMFleet.submit`` takes.
+
+All arithmetic happens in the HIP kernel behind librdet.so; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib, fleet
+from .detect import MAX_CENTERS, LaserScan, RangeData, Rdet2dOptions, RdetError, _as_f32, _rdet
+from .ekf_slam import Observation, OdometryData
+
+MAX_BEAMS = 8192
+RDET_ERR_BAD_SCAN = -3
+
+
+class Rdet2dScan(C.Structure):
+    """struct rdet2d_scan (include/rdet.h)."""
+    _fields_ = [("member", C.c_int), ("stamp", C.c_double), ("angle_min", C.c_float), ("angle_max", C.c_float),
+                ("angle_increment", C.c_float), ("scan_time", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float),
+                ("ranges", C.c_void_p), ("intensities", C.c_void_p), ("N", C.c_int)]
+
+
+_ready = None
+
+
+def _batch_lib():
+    """librdet.so with the rdet2d_batch_* argtypes set.  Raises LibraryMissing when it was not built, or was built without them."""
+    global _ready
+    if _ready is not None:
+        return _ready
+    L = _rdet()
+    if not hasattr(L, "rdet2d_batch_create"):
+        raise _lib.LibraryMissing("librdet.so has no rdet2d_batch_*: rebuild it (python __graft_entry__.py); there is no CPU fallback")
+    vp, ip = C.c_void_p, C.POINTER(C.c_int)
+    L.rdet2d_batch_sizeof_scan.restype = C.c_int
+    if L.rdet2d_batch_sizeof_scan() != C.sizeof(Rdet2dScan):
+        raise _lib.LibraryMissing(f"librdet.so: struct rdet2d_scan has {L.rdet2d_batch_sizeof_scan()} bytes, this package packs "
+                                  f"{C.sizeof(Rdet2dScan)}: rebuild it (python __graft_entry__.py)")
+    L.rdet2d_batch_last_hip_error.restype = C.c_char_p
+    L.rdet2d_batch_last_hip_error.argtypes = [vp]
+    L.rdet2d_batch_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.rdet2d_batch_destroy.argtypes = [vp]
+    L.rdet2d_batch_destroy.restype = None
+    L.rdet2d_batch_set_sensor_to_base_link.argtypes = [vp, C.c_int, vp]
+    L.rdet2d_batch_handle_odometry.argtypes = [vp, C.c_int, C.c_double, vp, vp, C.c_double, C.c_double, C.c_double]
+    L.rdet2d_batch_staging.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.rdet2d_batch_submit.argtypes = [vp, vp, C.c_int]
+    L.rdet2d_batch_collect.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+    L.rdet2d_batch_get_range_data.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip]
+    _ready = L
+    return L
+
+
+def scan_events(scans, observations):
+    """The ``ReflectorEKFSLAMFleet.submit`` events of one tick: ``scans`` as given to ``submit`` ([(member, LaserScan), ...]),
+    ``observations`` as ``collect`` returned them ([(status, Observation), ...]).  One ``fleet.scan_event`` per scan with status 0;
+    nothing is truncated (a scan with more than RFLEET_MAX_OBS centres is the fleet filter's REKF_ERR_TOO_MANY_OBS: the caller's call)."""
+    scans, observations = list(scans), list(observations)
+    if len(scans) != len(observations):
+        raise ValueError("one observation per scan")
+    return [fleet.scan_event(member, obs.time_, obs.cloud_) for (member, _), (status, obs) in zip(scans, observations) if status == 0]
+
+
+class LaserReflectorDetectFleet:
+    """B reflector_detect::LaserReflectorDetect on one MI355X, one kernel launch per ``submit``."""
+
+    def __init__(self, options_list, max_beams: int = MAX_BEAMS, device: int = 0, sensor_to_base_link=None):
+        self._L = _batch_lib()
+        self._h = None
+        self.options = list(options_list)
+        B = len(self.options)
+        opts = (Rdet2dOptions * max(B, 1))()
+        for i, o in enumerate(self.options):
+            opts[i] = Rdet2dOptions(o.intensity_min, o.reflector_min_length, o.reflector_length_error, o.range_min, o.range_max)
+        if sensor_to_base_link is None:
+            s2b = np.zeros((B, 3))
+        else:
+            s2b = np.array(sensor_to_base_link, dtype=np.float64)
+            s2b = np.ascontiguousarray(np.broadcast_to(s2b, (B, 3))) if s2b.ndim == 1 else np.ascontiguousarray(s2b.reshape(B, 3))
+        h = C.c_void_p()
+        rc = self._L.rdet2d_batch_create(C.cast(opts, C.c_void_p), s2b.ctypes.data if B else None, B, int(max_beams), int(device), C.byref(h))
+        if rc != 0:
+            raise RdetError(rc, "rdet2d_batch_create")
+        self._h = h
+        self.B = B
+        self.max_beams = int(max_beams)
+        self._s2b = s2b
+        self._pending = None          # the submit that has not been collected: (records, arrays they point into, count)
+        self._staging = {}
+
+    # -- lifetime -----------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.rdet2d_batch_destroy(self._h)
+            self._h = None
+            self._staging = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.B
+
+    def _chk(self, rc, where):
+        if rc != 0:
+            detail = self._L.rdet2d_batch_last_hip_error(self._h).decode() if rc == -2 else ""
+            raise RdetError(rc, where + (": " + detail if detail else ""))
+
+    # -- per member ---------------------------------------------------------
+    def SetSensorToBaseLinkTransform(self, member: int, xyyaw):
+        """Takes the transform already projected with ``detect.project2d`` (x, y, yaw)."""
+        v = np.ascontiguousarray(xyyaw, dtype=np.float64).reshape(3)
+        self._chk(self._L.rdet2d_batch_set_sensor_to_base_link(self._h, int(member), v.ctypes.data), "SetSensorToBaseLinkTransform")
+        self._s2b[int(member)] = v
+
+    def HandleOdometryData(self, member: int, msg: OdometryData):
+        pos = (C.c_double * 2)(float(msg.position[0]), float(msg.position[1]))
+        q = (C.c_double * 2)(float(msg.orientation[3]), float(msg.orientation[0]))     # (z, w)
+        self._chk(self._L.rdet2d_batch_handle_odometry(self._h, int(member), float(msg.time), C.addressof(pos), C.addressof(q),
+                                                       float(msg.linear_velocity[0]), float(msg.linear_velocity[1]),
+                                                       float(msg.angular_velocity[2])), "HandleOdometryData")
+
+    def staging(self, member: int):
+        """(ranges, intensities): numpy views of the member's slice of the staging area (``max_beams`` float32 each).  A LaserScan
+        whose arrays are leading slices of these views is read in place by the kernel, without a copy."""
+        member = int(member)
+        if member not in self._staging:
+            r, i = C.c_void_p(), C.c_void_p()
+            self._chk(self._L.rdet2d_batch_staging(self._h, member, C.byref(r), C.byref(i)), "staging")
+            tp = C.c_float * self.max_beams
+            self._staging[member] = (np.ctypeslib.as_array(tp.from_address(r.value)), np.ctypeslib.as_array(tp.from_address(i.value)))
+        return self._staging[member]
+
+    def GetRangeData(self, member: int) -> RangeData:
+        n = C.c_int()
+        origin = (C.c_float * 2)()
+        self._chk(self._L.rdet2d_batch_get_range_data(self._h, int(member), C.addressof(origin), None, 0, C.byref(n)), "GetRangeData")
+        ret = np.zeros((max(n.value, 1), 2), np.float32)
+        self._chk(self._L.rdet2d_batch_get_range_data(self._h, int(member), C.addressof(origin), ret.ctypes.data, ret.shape[0], C.byref(n)),
+                  "GetRangeData")
+        return RangeData(np.array(origin[:], dtype=np.float32), ret[: n.value].copy())
+
+    # -- the fleet interface --------------------------------------------------
+    @staticmethod
+    def pack(scans):
+        """scans: iterable of (member, LaserScan).  -> (ctypes array of rdet2d_scan, count, the float32 arrays it points into)."""
+        scans = list(scans)
+        arr = (Rdet2dScan * max(len(scans), 1))()
+        keep = []
+        for i, (member, msg) in enumerate(scans):
+            ranges, inten = _as_f32(msg.ranges), _as_f32(msg.intensities)
+            if ranges.shape != inten.shape or ranges.ndim != 1:
+                raise ValueError("ranges and intensities are one-dimensional and of one length")
+            keep.append((ranges, inten))
+            s = arr[i]
+            s.member, s.stamp = int(member), float(msg.stamp)
+            s.angle_min, s.angle_max, s.angle_increment = float(msg.angle_min), float(msg.angle_max), float(msg.angle_increment)
+            s.scan_time, s.range_min, s.range_max = float(msg.scan_time), float(msg.range_min), float(msg.range_max)
+            s.N = ranges.shape[0]
+            s.ranges = ranges.ctypes.data if s.N else None
+            s.intensities = inten.ctypes.data if s.N else None
+        return arr, len(scans), keep
+
+    def submit_code(self, scans) -> int:
+        arr, count, keep = self.pack(scans)
+        rc = self._L.rdet2d_batch_submit(self._h, C.cast(arr, C.c_void_p), count)
+        if rc == 0:
+            self._pending = (arr, keep, count)
+        return rc
+
+    def submit(self, scans):
+        """One scan of any subset of members, at most one per member: ONE kernel launch; returns without waiting for it."""
+        self._chk(self.submit_code(scans), "rdet2d_batch_submit")
+
+    def collect_code(self, max_centers: int = MAX_CENTERS):
+        """-> (rc, [(status, Observation)]) of the submit that has not been collected."""
+        count = self._pending[2] if self._pending else 0
+        n = max(count, 1)
+        mc = max(0, min(int(max_centers), MAX_CENTERS))
+        status, K, t = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        cen = np.zeros((n, max(mc, 1), 2), np.float32)
+        rc = self._L.rdet2d_batch_collect(self._h, status.ctypes.data, K.ctypes.data, cen.ctypes.data, mc, t.ctypes.data)
+        if rc != 0:
+            return rc, []
+        self._pending = None
+        return 0, [(int(status[i]), Observation(float(t[i]), cen[i, : int(K[i])].copy())) for i in range(count)]
+
+    def collect(self, max_centers: int = MAX_CENTERS):
+        """Waits for the launch: [(status, Observation)] in the order of the submitted scans.  status 0, or the scan's own error
+        (-3: a malformed message, K = 0; -5: more centres than ``max_centers``; -4: more than 256 reflectors)."""
+        rc, out = self.collect_code(max_centers)
+        self._chk(rc, "rdet2d_batch_collect")
+        return out
+
+    def detect(self, scans, max_centers: int = MAX_CENTERS):
+        self.submit(scans)
+        return self.collect(max_centers)
