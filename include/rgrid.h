@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define RGRID_ABI_VERSION 3
+#define RGRID_ABI_VERSION 4
 
 enum {
     RGRID_OK = 0,
@@ -173,6 +173,51 @@ enum { RGRID_SCAN_INSERTED = 0, RGRID_SCAN_DROPPED_EMPTY = 1, RGRID_SCAN_FILTERE
 int rgrid_add_range_data(rgrid_t *h, const rgrid_map_builder_options *opt, const float origin_xy[2], const float *returns_xy,
                          int n_returns, const float *misses_xy, int n_misses, const double ekf_pose[3], double local_pose[3],
                          float *returns_in_local, int *status);
+
+/* ---- fleet scan matcher: RealTimeCorrelativeScanMatcher2D::Match for one scan of many robots, one launch per call
+ * (csrc/rgrid_batch.hip).  A batch handle owns one HIP stream, num_grids resident grids of up to max_cells cells that any
+ * number of scans may share, and staging for max_scans scans of up to max_points points each.  Every scan's pose_estimate,
+ * score, best3 and info3 are exactly what rgrid_match returns for that scan, that grid and those options. */
+typedef struct rgrid_batch rgrid_batch_t;
+typedef struct rgrid_batch_scan {      /* one scan of a call */
+    int grid;                          /* resident grid slot it is matched against */
+    int n;                             /* points */
+    const float *points_xy;            /* tracking frame, 2*n floats */
+    double initial_pose[3];            /* x, y, angle */
+} rgrid_batch_scan;
+
+/* max_rotations: rotated scans a single scan may need (2 * num_angular + 1); rgrid_match's limit of 1024 holds here too. */
+int rgrid_batch_create(int max_scans, int max_points, int num_grids, long max_cells, int max_rotations, int device,
+                       rgrid_batch_t **out);
+void rgrid_batch_destroy(rgrid_batch_t *b);
+
+/* rgrid_set_grid for slot `grid`.  RGRID_ERR_INVALID between a submit and its collect. */
+int rgrid_batch_set_grid(rgrid_batch_t *b, int grid, const uint16_t *cells, int num_x_cells, int num_y_cells,
+                         double resolution, double max_x, double max_y);
+
+/* Enqueues the match of scans[0 .. count) and returns without waiting.  The whole call is refused with RGRID_ERR_INVALID, and
+ * nothing is launched, for a null pointer, count outside [0, max_scans], a grid slot out of range or not yet set, or a submit
+ * that has not been collected.  What belongs to one scan is reported by collect in status[j] and leaves the other scans
+ * untouched: RGRID_ERR_EMPTY (n == 0), RGRID_ERR_CAPACITY (n > max_points, more rotated scans than max_rotations or 1024).
+ * The points are copied before the call returns. */
+int rgrid_batch_match_submit(rgrid_batch_t *b, const rgrid_match_options *opt, const rgrid_batch_scan *scans, int count);
+
+/* Waits for the handle's stream and hands out the results of the pending submit, in its order: status (count), pose_estimates
+ * (3 * count), scores (count), best3 / info3 (3 * count each, nullable) as rgrid_match defines them; entries of a scan whose
+ * status is not RGRID_OK are zero.  RGRID_ERR_INVALID without a pending submit. */
+int rgrid_batch_match_collect(rgrid_batch_t *b, int *status, double *pose_estimates, double *scores, int *best3, int *info3);
+
+/* Where the arg-max over a scan's rotated scans is taken: by the workgroup of that scan that finishes last, inside the one
+ * launch (the default), or by a second launch with one workgroup per scan.  The results are the same bits.
+ * RGRID_ERR_INVALID between a submit and its collect. */
+enum { RGRID_BATCH_REDUCE_ARRIVAL = 0, RGRID_BATCH_REDUCE_LAUNCH = 1 };
+int rgrid_batch_set_reduction(rgrid_batch_t *b, int mode);
+
+/* Host seconds the last submit spent before its launch (initial rotations, search parameters, rotation tables, packing). */
+double rgrid_batch_last_prepare_seconds(rgrid_batch_t *b);
+
+int rgrid_batch_sizeof_scan(void);
+const char *rgrid_batch_last_hip_error(rgrid_batch_t *b);
 
 const char *rgrid_strerror(int code);
 const char *rgrid_last_hip_error(rgrid_t *h);

@@ -2,10 +2,11 @@
 
 Only what the path needs: ``csrc/`` (HIP kernels + the C ABI of include/*.h), the
 host-side mirrors of the reference's two interfaces (``ekf_slam``, ``detect``), their
-fleet forms (``fleet``, ``fleet_detect``), the
+fleet forms (``fleet``, ``fleet_detect``), the fleet scan matcher (``fleet_match``), the
 synthetic session generator (``synth``) and the session driver (``session``).
 """
 from .ekf_slam import (DIFF, OMNI, EKFOptions, Map, Observation, OdometryData,  # noqa: F401
                        ReflectorEKFSLAM, ReflectorMatchResult, RekfError, State)
 from .fleet import ReflectorEKFSLAMFleet  # noqa: F401
 from .fleet_detect import LaserReflectorDetectFleet, scan_events  # noqa: F401
+from .fleet_match import ScanMatchFleet, pose_fixes  # noqa: F401

@@ -18,6 +18,7 @@
 // ballot-scan compaction; also the range gate of the adaptive filter).  The bisection over voxel sizes of the
 // adaptive filter (:47-73) stays on the host: a dozen dependent decisions on one integer each.
 #include "../../include/rgrid.h"
+#include "rgrid_dev.h"
 
 #include <hip/hip_runtime.h>
 
@@ -30,8 +31,6 @@
 #include <vector>
 
 namespace {
-
-struct BestRec { float score; int id; };
 
 // ---- voxel filter -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void kg_keys(const float *__restrict__ xy, int n, float res, int2 *__restrict__ key,
@@ -170,21 +169,6 @@ __global__ __launch_bounds__(256) void kg_discretize(MatchArgs A, const float *_
     // MapLimits::GetCellIndex (map_limits.h:47-55): (x index from y, y index from x), double arithmetic, lround
     idx[e] = make_int2((int)lround((A.max_y - (double)py) / A.resolution - 0.5),
                        (int)lround((A.max_x - (double)px) / A.resolution - 0.5));
-}
-
-__device__ static inline float value_to_probability(unsigned v16)
-{
-#pragma clang fp contract(off)
-    // probability_values.cc:11-20 (the table entry, recomputed: same two float operations), probability_values.h:53-57
-    const float kMinProbability = 0.1f, kMaxProbability = 1.f - kMinProbability;
-    const float lower = 1.f - kMaxProbability, upper = 1.f - kMinProbability;
-    const unsigned v = v16 & 32767u;
-    float cost = upper;
-    if (v != 0) {
-        const float kScale = (upper - lower) / (32768 - 2.f);
-        cost = (float)v * kScale + (lower - kScale);
-    }
-    return 1.f - cost;
 }
 
 // One workgroup per rotated scan, one lane per translation candidate of that scan.  The discretised point is the
@@ -781,21 +765,6 @@ void lookup_table(float probability, unsigned short *table)
         const float p = o / (o + 1.f);
         table[cell] = (unsigned short)(cost_to_value(1.f - p) + MARKER);
     }
-}
-
-// Project2D(Rigid3f::Rotation(AngleAxisf(angle, UnitZ))) as a (cos, sin) pair, restating Eigen 3.3 in float32:
-// Quaternionf(AngleAxisf) = (cos(a/2), 0, 0, sin(a/2)); GetYaw (transform.h:27-33) = atan2 of q * UnitX with
-// Eigen's  v + w*uv + vec x uv,  uv = 2 (vec x v); Rotation2Df(yaw) rotates with (cos yaw, sin yaw).  Host libm.
-void rotation_cs(float angle, float *c, float *s)
-{
-#pragma clang fp contract(off)
-    const float ha = 0.5f * angle;
-    const float w = std::cos(ha), z = std::sin(ha);
-    const float uvy = z + z;
-    const float dx = (1.f + w * 0.f) + (0.f * 0.f - z * uvy);
-    const float dy = (0.f + w * uvy) + (z * 0.f - 0.f * 0.f);
-    const float yaw = std::atan2(dy, dx);
-    *c = std::cos(yaw); *s = std::sin(yaw);
 }
 
 }  // namespace

@@ -1,0 +1,182 @@
+"""Fleet scan matcher: scan_matching::RealTimeCorrelativeScanMatcher2D::Match for one scan of many robots, ONE kernel launch per
+call (rgrid_batch_* of include/rgrid.h), against resident probability grids that any number of the scans may share.
+
+``ScanMatchFleet(max_scans)`` holds ``num_grids`` grid slots (``SetGrid``).  ``submit(scans)`` takes ``(grid_slot, initial_pose,
+points_xy)`` per scan and enqueues one launch of kgb_match (one workgroup per scan and rotated scan); ``collect()`` waits and
+returns one ``FleetMatchResult`` per scan, in the order given: the ``grid.MatchResult`` that ``GridFrontEnd.Match`` returns for
+that scan, bit for bit, plus a ``status``.  ``pose_fixes`` turns a tick's results into the ``pose_fix`` arguments of
+``fleet.scan_event``: the reference's USE_GPS deployment is ``fleet.predict_poses(times)`` -> ``matcher.match(...)`` ->
+``fleet.scan_event(member, t, cloud, pose_fix=...)`` -> ``fleet.submit``.
+
+All arithmetic happens in the HIP kernel behind librgrid.so; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .grid import MatchResult, RealTimeCorrelativeScanMatcherOptions, RgridError, _lib_rgrid, _MatchOptions
+
+RGRID_OK, RGRID_ERR_INVALID, RGRID_ERR_CAPACITY, RGRID_ERR_EMPTY = 0, -1, -4, -6
+REDUCE_ARRIVAL, REDUCE_LAUNCH = 0, 1        # rgrid_batch_set_reduction
+
+
+class RgridBatchScan(C.Structure):
+    """struct rgrid_batch_scan (include/rgrid.h)."""
+    _fields_ = [("grid", C.c_int), ("n", C.c_int), ("points_xy", C.c_void_p), ("initial_pose", C.c_double * 3)]
+
+
+@dataclass
+class FleetMatchResult(MatchResult):
+    status: int = 0                  # RGRID_OK, or the scan's own error: -6 empty cloud, -4 more points / rotated scans than the handle holds
+
+
+_ready = None
+
+
+def _batch_lib():
+    """librgrid.so with the rgrid_batch_* argtypes set.  Raises LibraryMissing when it was not built, or was built without them."""
+    global _ready
+    if _ready is not None:
+        return _ready
+    L = _lib_rgrid()
+    if not hasattr(L, "rgrid_batch_create"):
+        raise _lib.LibraryMissing("librgrid.so has no rgrid_batch_*: rebuild it (python __graft_entry__.py); there is no CPU fallback")
+    vp = C.c_void_p
+    L.rgrid_batch_sizeof_scan.restype = C.c_int
+    if L.rgrid_batch_sizeof_scan() != C.sizeof(RgridBatchScan):
+        raise _lib.LibraryMissing(f"librgrid.so: struct rgrid_batch_scan has {L.rgrid_batch_sizeof_scan()} bytes, this package packs "
+                                  f"{C.sizeof(RgridBatchScan)}: rebuild it (python __graft_entry__.py)")
+    L.rgrid_batch_last_hip_error.restype = C.c_char_p
+    L.rgrid_batch_last_hip_error.argtypes = [vp]
+    L.rgrid_batch_last_prepare_seconds.restype = C.c_double
+    L.rgrid_batch_last_prepare_seconds.argtypes = [vp]
+    L.rgrid_batch_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.POINTER(vp)]
+    L.rgrid_batch_destroy.argtypes = [vp]
+    L.rgrid_batch_destroy.restype = None
+    L.rgrid_batch_set_grid.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
+    L.rgrid_batch_set_reduction.argtypes = [vp, C.c_int]
+    L.rgrid_batch_match_submit.argtypes = [vp, C.POINTER(_MatchOptions), vp, C.c_int]
+    L.rgrid_batch_match_collect.argtypes = [vp, vp, vp, vp, vp, vp]
+    _ready = L
+    return L
+
+
+def pose_fixes(results):
+    """Per scan ``(x, y, yaw)`` of the matched pose, or None when its status is not OK: the ``pose_fix`` of ``fleet.scan_event``."""
+    return [tuple(float(v) for v in r.pose_estimate) if r.status == RGRID_OK else None for r in results]
+
+
+class ScanMatchFleet:
+    """One batch handle of include/rgrid.h: the real-time correlative scan matcher for up to ``max_scans`` scans per launch."""
+
+    def __init__(self, max_scans: int, max_points: int = 8192, num_grids: int = 1, max_cells: int = 1024 * 1024,
+                 max_rotations: int = 256, device: int = 0):
+        self._L = _batch_lib()
+        self._h = None
+        h = C.c_void_p()
+        rc = self._L.rgrid_batch_create(int(max_scans), int(max_points), int(num_grids), int(max_cells), int(max_rotations),
+                                        int(device), C.byref(h))
+        if rc != 0:
+            raise RgridError(rc, "rgrid_batch_create")
+        self._h = h
+        self.max_scans, self.max_points, self.num_grids = int(max_scans), int(max_points), int(num_grids)
+        self._pending = None          # the submit that has not been collected: its scan count
+
+    # -- lifetime -----------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.rgrid_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, where):
+        if rc != 0:
+            raise RgridError(rc, where, self._L.rgrid_batch_last_hip_error(self._h).decode() if rc == -2 else
+                             self._L.rgrid_strerror(rc).decode())
+
+    # -- grids ----------------------------------------------------------------
+    def SetGrid_code(self, slot: int, cells, resolution: float, max_xy) -> int:
+        g = np.ascontiguousarray(cells, dtype=np.uint16)
+        if g.ndim != 2:
+            raise ValueError("cells is a (num_y_cells, num_x_cells) array")
+        return self._L.rgrid_batch_set_grid(self._h, int(slot), g.ctypes.data, g.shape[1], g.shape[0], float(resolution),
+                                            float(max_xy[0]), float(max_xy[1]))
+
+    def SetGrid(self, slot: int, cells, resolution: float, max_xy):
+        """``GridFrontEnd.SetGrid`` for grid slot ``slot``: uint16 (num_y_cells, num_x_cells) correspondence-cost values,
+        MapLimits resolution and max corner.  Not between a submit and its collect."""
+        self._chk(self.SetGrid_code(slot, cells, resolution, max_xy), "rgrid_batch_set_grid")
+
+    def set_reduction(self, mode: int):
+        """REDUCE_ARRIVAL (default): the arg-max over a scan's rotated scans inside the one launch; REDUCE_LAUNCH: in a second one."""
+        self._chk(self._L.rgrid_batch_set_reduction(self._h, int(mode)), "rgrid_batch_set_reduction")
+
+    # -- the fleet interface --------------------------------------------------
+    @staticmethod
+    def pack(scans):
+        """scans: iterable of (grid_slot, initial_pose, points_xy).  -> (ctypes array of rgrid_batch_scan, count, the arrays it points into)."""
+        scans = list(scans)
+        arr = (RgridBatchScan * max(len(scans), 1))()
+        keep = []
+        for i, (slot, pose, points) in enumerate(scans):
+            pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+            keep.append(pts)
+            s = arr[i]
+            s.grid, s.n = int(slot), pts.shape[0]
+            s.points_xy = pts.ctypes.data if s.n else None
+            s.initial_pose[0], s.initial_pose[1], s.initial_pose[2] = float(pose[0]), float(pose[1]), float(pose[2])
+        return arr, len(scans), keep
+
+    def submit_packed_code(self, packed, options: RealTimeCorrelativeScanMatcherOptions | None = None) -> int:
+        """``submit_code`` for what ``pack`` returned (reusable: the points are copied by the call)."""
+        o = options or RealTimeCorrelativeScanMatcherOptions()
+        co = _MatchOptions(o.linear_search_window, o.angular_search_window, o.translation_delta_cost_weight,
+                           o.rotation_delta_cost_weight)
+        rc = self._L.rgrid_batch_match_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1])
+        if rc == 0:
+            self._pending = packed[1]
+        return rc
+
+    def submit_code(self, scans, options: RealTimeCorrelativeScanMatcherOptions | None = None) -> int:
+        return self.submit_packed_code(self.pack(scans), options)
+
+    def submit(self, scans, options: RealTimeCorrelativeScanMatcherOptions | None = None):
+        """One scan per entry, any grid slot each, the same options for all: ONE kernel launch; returns without waiting for it."""
+        self._chk(self.submit_code(scans, options), "rgrid_batch_match_submit")
+
+    def collect_code(self):
+        """-> (rc, [FleetMatchResult]) of the submit that has not been collected."""
+        count = self._pending or 0
+        n = max(count, 1)
+        status, pose, score = np.zeros(n, np.int32), np.zeros((n, 3)), np.zeros(n)
+        best, info = np.zeros((n, 3), np.int32), np.zeros((n, 3), np.int32)
+        rc = self._L.rgrid_batch_match_collect(self._h, status.ctypes.data, pose.ctypes.data, score.ctypes.data, best.ctypes.data,
+                                               info.ctypes.data)
+        if rc != 0:
+            return rc, []
+        self._pending = None
+        return 0, [FleetMatchResult(float(score[i]), pose[i].copy(), tuple(int(v) for v in best[i]), tuple(int(v) for v in info[i]),
+                                    int(status[i])) for i in range(count)]
+
+    def collect(self):
+        """Waits for the launch: one FleetMatchResult per submitted scan, in order."""
+        rc, out = self.collect_code()
+        self._chk(rc, "rgrid_batch_match_collect")
+        return out
+
+    def match(self, scans, options: RealTimeCorrelativeScanMatcherOptions | None = None):
+        self.submit(scans, options)
+        return self.collect()
+
+    def last_prepare_seconds(self) -> float:
+        """Host time the last submit spent before its launch: initial rotations, search parameters, rotation tables, packing."""
+        return float(self._L.rgrid_batch_last_prepare_seconds(self._h))

@@ -25,7 +25,7 @@ class _MatchOptions(C.Structure):
 
 
 _rgrid = None
-RGRID_ABI_VERSION = 3            # include/rgrid.h
+RGRID_ABI_VERSION = 4            # include/rgrid.h
 
 
 def _lib_rgrid():
