@@ -109,7 +109,8 @@ int rgrid_get_grid(rgrid_t *h, uint16_t *cells, long cap);
  * initial_pose = (x, y, rotation angle); points in the tracking frame; pose_estimate = (x, y, angle) of the best
  * candidate (first maximum in the reference's candidate order); returns its score in *score.
  * best3 (nullable) = (scan_index, x_index_offset, y_index_offset); info3 (nullable) = (num_scans,
- * num_linear_perturbations, num_candidates). */
+ * num_linear_perturbations, num_candidates).  RGRID_ERR_CAPACITY, before any launch, also for a search window that is
+ * negative or NaN or whose candidate count no int holds: the check rgrid_batch_match_submit makes per scan. */
 int rgrid_match(rgrid_t *h, const rgrid_match_options *opt, const double initial_pose[3], const float *points_xy,
                 int n, double pose_estimate[3], double *score, int best3[3], int info3[3]);
 

@@ -800,15 +800,6 @@ struct rgrid {
     std::string hip_error;
 };
 
-#define G_TRY(h, expr)                                                              \
-    do {                                                                            \
-        hipError_t e_ = (expr);                                                     \
-        if (e_ != hipSuccess) {                                                     \
-            if (h) (h)->hip_error = std::string(#expr) + ": " + hipGetErrorString(e_); \
-            return RGRID_ERR_HIP;                                                   \
-        }                                                                           \
-    } while (0)
-
 namespace {
 
 // VoxelFilter(res).Filter on the device buffer `src` (n points) into `dst`; *m = survivors (synchronises)
@@ -1258,52 +1249,26 @@ int rgrid_match(rgrid_t *h, const rgrid_match_options *opt, const double initial
     if (n == 0) return RGRID_ERR_EMPTY;
     if (n > h->max_points) return RGRID_ERR_CAPACITY;
     G_TRY(h, hipSetDevice(h->device));
-    // initial rotation of the cloud (real_time_correlative_scan_matcher_2d.cc:91-97), host float32
-    float c0, s0;
-    rotation_cs((float)initial_pose[2], &c0, &s0);
-    float max_scan_range = 3.f * (float)h->resolution;                                   // correlative_scan_matcher_2d.cc:18-24
-    for (int i = 0; i < n; ++i) {
-        const float x = points_xy[2 * i], y = points_xy[2 * i + 1];
-        const float rx = c0 * x - s0 * y, ry = s0 * x + c0 * y;
-        h->h_pts[2 * i] = rx; h->h_pts[2 * i + 1] = ry;
-        const float range = std::sqrt(rx * rx + ry * ry);
-        if (range > max_scan_range) max_scan_range = range;
-    }
-    const double res = h->resolution;
-    const double kSafetyMargin = 1. - 1e-3;
-    const double step = kSafetyMargin * std::acos(1. - (res * res) / (2. * (double)(max_scan_range * max_scan_range)));   // :25-28
-    const int num_angular = (int)std::ceil(opt->angular_search_window / step);            // :29-31
-    const int num_scans = 2 * num_angular + 1;
-    const int num_linear = (int)std::ceil(opt->linear_search_window / res);               // :33-34
-    const long long W = 2LL * num_linear + 1, ncand = (long long)num_scans * W * W;
-    if (num_scans > 1024 || ncand > h->max_candidates) return RGRID_ERR_CAPACITY;
-    std::vector<float> cs(2 * (size_t)num_scans);
-    double delta_theta = -num_angular * step;                                             // :90-94 (accumulated in double)
-    for (int s = 0; s < num_scans; ++s, delta_theta += step) rotation_cs((float)delta_theta, &cs[2 * s], &cs[2 * s + 1]);
+    MatchPlan P;
+    if (plan_match(opt, h->resolution, initial_pose, points_xy, n, h->h_pts, &P) != RGRID_OK || P.num_scans > 1024 || P.ncand > h->max_candidates)
+        return RGRID_ERR_CAPACITY;
+    std::vector<float> cs(2 * (size_t)P.num_scans);
+    rotation_table(P, cs.data());
     G_TRY(h, hipMemcpyAsync(h->d_in, h->h_pts, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
     G_TRY(h, hipMemcpyAsync(h->d_cs, cs.data(), sizeof(float) * cs.size(), hipMemcpyHostToDevice, h->stream));
     MatchArgs A;
-    A.n = n; A.num_scans = num_scans; A.num_linear = num_linear; A.nx = h->nx; A.ny = h->ny;
+    A.n = n; A.num_scans = P.num_scans; A.num_linear = P.num_linear; A.nx = h->nx; A.ny = h->ny;
     A.tx = (float)initial_pose[0]; A.ty = (float)initial_pose[1];
-    A.resolution = res; A.max_x = h->max_x; A.max_y = h->max_y;
-    A.num_angular_d = (double)num_angular; A.step = step;
+    A.resolution = P.res; A.max_x = h->max_x; A.max_y = h->max_y;
+    A.num_angular_d = (double)P.num_angular; A.step = P.step;
     A.wt = opt->translation_delta_cost_weight; A.wr = opt->rotation_delta_cost_weight;
-    const int nb_d = (num_scans * n + 255) / 256, nb_s = num_scans;
+    const int nb_d = (P.num_scans * n + 255) / 256, nb_s = P.num_scans;
     hipLaunchKernelGGL(kg_discretize, dim3(nb_d), dim3(256), 0, h->stream, A, h->d_in, h->d_cs, h->d_idx);
     hipLaunchKernelGGL(kg_score, dim3(nb_s), dim3(128), 0, h->stream, A, h->d_idx, h->d_cells, h->d_bb);
     hipLaunchKernelGGL(kg_best, dim3(1), dim3(256), 0, h->stream, h->d_bb, nb_s, h->d_best);
     G_TRY(h, hipMemcpyAsync(h->h_best, h->d_best, sizeof(BestRec), hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));                                            // cs stays alive until here
-    const int id = h->h_best->id;
-    const int scan = id / (int)(W * W), r = id - scan * (int)(W * W);
-    const int xo = r / (int)W - num_linear, yo = r - (r / (int)W) * (int)W - num_linear;
-    const double x = -yo * res, y = -xo * res, orientation = (scan - num_angular) * step;
-    pose_estimate[0] = initial_pose[0] + x;                                               // :106-110
-    pose_estimate[1] = initial_pose[1] + y;
-    pose_estimate[2] = initial_pose[2] + orientation;
-    *score = (double)h->h_best->score;
-    if (best3) { best3[0] = scan; best3[1] = xo; best3[2] = yo; }
-    if (info3) { info3[0] = num_scans; info3[1] = num_linear; info3[2] = (int)ncand; }
+    decode_best(P, initial_pose, *h->h_best, pose_estimate, score, best3, info3);
     return RGRID_OK;
 }
 

@@ -2,9 +2,9 @@
 // (rgrid_batch_* of include/rgrid.h), against resident probability grids that any number of the scans may share.
 //
 // Every scan of a call is one scan_matching::RealTimeCorrelativeScanMatcher2D::Match (reference
-// src/scan_matching/real_time_correlative_scan_matcher_2d.cc:84-118) and gives the bits rgrid_match gives: the host does per
-// scan what rgrid_match does before its launches (the float32 initial rotation, max_scan_range, the search parameters, one
-// (cos, sin) pair per rotated scan from the host's libm), the device does what kg_discretize, kg_score and kg_best do -- in
+// src/scan_matching/real_time_correlative_scan_matcher_2d.cc:84-118) and gives the bits rgrid_match gives: the host plans each
+// scan and decodes its winner through the functions rgrid_match calls (plan_match, rotation_table, decode_best of rgrid_dev.h:
+// one text), the device does what kg_discretize, kg_score and kg_best do (a text of its own) -- in
 //   kgb_match   ONE workgroup per (scan, rotated scan): a call of B default-option scans is about 107 B workgroups.  The
 //               workgroup discretises its own rotated scan into LDS (kg_discretize's arithmetic, 8 B per point), then scores its
 //               (2 num_linear + 1)^2 translation candidates as kg_score does: one lane per candidate, passes of 128, the float32
@@ -203,9 +203,8 @@ struct GridSlot {
 // what collect needs of a submitted scan
 struct Pending {
     int status, rec;
-    int num_scans, num_linear, num_angular;
-    long long ncand;
-    double step, res, pose[3];
+    MatchPlan plan;
+    double pose[3];
 };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -236,15 +235,6 @@ struct rgrid_batch {
     std::string hip_error;
 };
 
-#define GB_TRY(h, expr)                                                             \
-    do {                                                                            \
-        hipError_t e_ = (expr);                                                     \
-        if (e_ != hipSuccess) {                                                     \
-            if (h) (h)->hip_error = std::string(#expr) + ": " + hipGetErrorString(e_); \
-            return RGRID_ERR_HIP;                                                   \
-        }                                                                           \
-    } while (0)
-
 extern "C" {
 
 int rgrid_batch_sizeof_scan(void) { return (int)sizeof(rgrid_batch_scan); }
@@ -273,8 +263,8 @@ int rgrid_batch_create(int max_scans, int max_points, int num_grids, long max_ce
     b->sub.resize(nS);
     b->pack.resize(seg_bytes);
     int rc = [&]() -> int {
-        GB_TRY(b, hipSetDevice(device));
-        GB_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        G_TRY(b, hipSetDevice(device));
+        G_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
         for (int k = 0; k < KGB_SEGMENTS; ++k) {
             b->h_seg[k] = (k == 0 || b->seg_in_vram) ? (unsigned char *)host_visible::alloc(seg_bytes) : nullptr;
             if (b->h_seg[k]) {
@@ -283,22 +273,22 @@ int rgrid_batch_create(int max_scans, int max_points, int num_grids, long max_ce
             } else {
                 if (k > 0 && b->seg_in_vram) { b->hip_error = "host-visible device memory: second segment refused"; return RGRID_ERR_HIP; }
                 void *dv = nullptr;
-                GB_TRY(b, hipHostMalloc((void **)&b->h_seg[k], seg_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-                GB_TRY(b, hipHostGetDevicePointer(&dv, b->h_seg[k], 0)); b->dv_seg[k] = (const unsigned char *)dv;
+                G_TRY(b, hipHostMalloc((void **)&b->h_seg[k], seg_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+                G_TRY(b, hipHostGetDevicePointer(&dv, b->h_seg[k], 0)); b->dv_seg[k] = (const unsigned char *)dv;
             }
         }
         void *dv = nullptr;
-        GB_TRY(b, hipHostMalloc((void **)&b->h_out, sizeof(BestRec) * nS, hipHostMallocMapped | hipHostMallocCoherent));
-        GB_TRY(b, hipHostGetDevicePointer(&dv, b->h_out, 0)); b->dv_out = (BestRec *)dv;
+        G_TRY(b, hipHostMalloc((void **)&b->h_out, sizeof(BestRec) * nS, hipHostMallocMapped | hipHostMallocCoherent));
+        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_out, 0)); b->dv_out = (BestRec *)dv;
         std::memset(b->h_out, 0, sizeof(BestRec) * nS);
-        GB_TRY(b, hipMalloc((void **)&b->d_cells, sizeof(unsigned short) * (size_t)num_grids * (size_t)max_cells));
-        GB_TRY(b, hipMalloc((void **)&b->d_bb, sizeof(unsigned long long) * nS * nR));
-        GB_TRY(b, hipMalloc((void **)&b->d_arrived, sizeof(int) * nS));
-        GB_TRY(b, hipMemsetAsync(b->d_arrived, 0, sizeof(int) * nS, b->stream));
+        G_TRY(b, hipMalloc((void **)&b->d_cells, sizeof(unsigned short) * (size_t)num_grids * (size_t)max_cells));
+        G_TRY(b, hipMalloc((void **)&b->d_bb, sizeof(unsigned long long) * nS * nR));
+        G_TRY(b, hipMalloc((void **)&b->d_arrived, sizeof(int) * nS));
+        G_TRY(b, hipMemsetAsync(b->d_arrived, 0, sizeof(int) * nS, b->stream));
         // the rotated scan's indices in LDS: 8 B per point, 64 KB at 8192 points
         const int lds_max = (int)(sizeof(int2) * (nP + KGB_PF));
-        GB_TRY(b, hipFuncSetAttribute((const void *)kgb_match<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        GB_TRY(b, hipFuncSetAttribute((const void *)kgb_match<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        G_TRY(b, hipFuncSetAttribute((const void *)kgb_match<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        G_TRY(b, hipFuncSetAttribute((const void *)kgb_match<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         return RGRID_OK;
     }();
     if (rc != RGRID_OK) { std::fprintf(stderr, "rgrid_batch_create: %s\n", b->hip_error.c_str()); rgrid_batch_destroy(b); return rc; }
@@ -332,10 +322,10 @@ int rgrid_batch_set_grid(rgrid_batch_t *b, int grid, const uint16_t *cells, int 
     if (!b || !cells || grid < 0 || grid >= b->num_grids || num_x_cells < 1 || num_y_cells < 1 || !(resolution > 0.) || b->outstanding)
         return RGRID_ERR_INVALID;
     if ((long long)num_x_cells * num_y_cells > (long long)b->max_cells) return RGRID_ERR_CAPACITY;
-    GB_TRY(b, hipSetDevice(b->device));
-    GB_TRY(b, hipMemcpyAsync(b->d_cells + (size_t)grid * (size_t)b->max_cells, cells, sizeof(uint16_t) * (size_t)num_x_cells * num_y_cells,
-                             hipMemcpyHostToDevice, b->stream));
-    GB_TRY(b, hipStreamSynchronize(b->stream));
+    G_TRY(b, hipSetDevice(b->device));
+    G_TRY(b, hipMemcpyAsync(b->d_cells + (size_t)grid * (size_t)b->max_cells, cells, sizeof(uint16_t) * (size_t)num_x_cells * num_y_cells,
+                            hipMemcpyHostToDevice, b->stream));
+    G_TRY(b, hipStreamSynchronize(b->stream));
     GridSlot &g = b->grids[(size_t)grid];
     g.set = true; g.nx = num_x_cells; g.ny = num_y_cells; g.resolution = resolution; g.max_x = max_x; g.max_y = max_y;
     return RGRID_OK;
@@ -364,54 +354,31 @@ int rgrid_batch_match_submit(rgrid_batch_t *b, const rgrid_match_options *opt, c
         if (s.n == 0) { P.status = RGRID_ERR_EMPTY; continue; }
         if (s.n > b->max_points || b->max_rotations > KGB_MAX_ROT) { P.status = RGRID_ERR_CAPACITY; continue; }
         const int n = s.n;
-        // initial rotation of the cloud (real_time_correlative_scan_matcher_2d.cc:91-97), host float32 -- as rgrid_match
-        float c0, s0;
-        rotation_cs((float)s.initial_pose[2], &c0, &s0);
-        float max_scan_range = 3.f * (float)g.resolution;                                   // correlative_scan_matcher_2d.cc:18-24
+        // the search plan rgrid_match makes; on top of it this handle's own limits: its rotations, a linear window of 16383 cells
         float *pts = f2 + 2 * (size_t)nf2;
-        for (int i = 0; i < n; ++i) {
-            const float x = s.points_xy[2 * i], y = s.points_xy[2 * i + 1];
-            const float rx = c0 * x - s0 * y, ry = s0 * x + c0 * y;
-            pts[2 * i] = rx; pts[2 * i + 1] = ry;
-            const float range = std::sqrt(rx * rx + ry * ry);
-            if (range > max_scan_range) max_scan_range = range;
-        }
-        const double res = g.resolution;
-        const double kSafetyMargin = 1. - 1e-3;
-        const double step = kSafetyMargin * std::acos(1. - (res * res) / (2. * (double)(max_scan_range * max_scan_range)));   // :25-28
-        const double num_angular_d = std::ceil(opt->angular_search_window / step);          // :29-31
-        const double num_linear_d = std::ceil(opt->linear_search_window / res);             // :33-34
-        // (a window that no int holds is a capacity error here; rgrid_match converts first)
-        if (!(num_angular_d >= 0. && 2. * num_angular_d + 1. <= (double)rot_cap) || !(num_linear_d >= 0. && num_linear_d <= 16383.)) {
+        MatchPlan &M = P.plan;
+        if (plan_match(opt, g.resolution, s.initial_pose, s.points_xy, n, pts, &M) != RGRID_OK || M.num_scans > rot_cap || M.num_linear > 16383) {
             P.status = RGRID_ERR_CAPACITY;
             continue;
         }
-        const int num_angular = (int)num_angular_d;
-        const int num_scans = 2 * num_angular + 1;
-        const int num_linear = (int)num_linear_d;
-        const long long W = 2LL * num_linear + 1, ncand = (long long)num_scans * W * W;
-        if (ncand > 0x7fffffffLL) { P.status = RGRID_ERR_CAPACITY; continue; }             // candidate ids are ints
+        const int num_scans = M.num_scans;
         const int pts_off = nf2;
         nf2 += n;
-        float *cs = f2 + 2 * (size_t)nf2;
-        double delta_theta = -num_angular * step;                                           // :90-94 (accumulated in double)
-        for (int r = 0; r < num_scans; ++r, delta_theta += step) rotation_cs((float)delta_theta, &cs[2 * r], &cs[2 * r + 1]);
+        rotation_table(M, f2 + 2 * (size_t)nf2);
         const int cs_off = nf2;
         nf2 += num_scans;
         BatchRec &A = recs[nrec];
-        A.resolution = res; A.max_x = g.max_x; A.max_y = g.max_y;
-        A.num_angular_d = (double)num_angular; A.step = step;
+        A.resolution = M.res; A.max_x = g.max_x; A.max_y = g.max_y;
+        A.num_angular_d = (double)M.num_angular; A.step = M.step;
         A.wt = opt->translation_delta_cost_weight; A.wr = opt->rotation_delta_cost_weight;
         A.cells_off = (long long)s.grid * (long long)b->max_cells;
-        A.n = n; A.num_scans = num_scans; A.num_linear = num_linear; A.nx = g.nx; A.ny = g.ny;
+        A.n = n; A.num_scans = num_scans; A.num_linear = M.num_linear; A.nx = g.nx; A.ny = g.ny;
         A.pts_off = pts_off; A.cs_off = cs_off;
         A.tx = (float)s.initial_pose[0]; A.ty = (float)s.initial_pose[1];
         for (int r = 0; r < num_scans; ++r) wgmap[nwg + r] = make_int2(nrec, r);
         nwg += num_scans;
         if (n > n_max) n_max = n;
         P.status = RGRID_OK; P.rec = nrec;
-        P.num_scans = num_scans; P.num_linear = num_linear; P.num_angular = num_angular; P.ncand = ncand;
-        P.step = step; P.res = res;
         std::memcpy(P.pose, s.initial_pose, sizeof(double) * 3);
         ++nrec;
     }
@@ -421,7 +388,7 @@ int rgrid_batch_match_submit(rgrid_batch_t *b, const rgrid_match_options *opt, c
         b->prepare_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
         return RGRID_OK;
     }
-    GB_TRY(b, hipSetDevice(b->device));
+    G_TRY(b, hipSetDevice(b->device));
     // the image into the call's segment: three forward copies, nothing is read back from it
     const int k = (int)(b->n_submit++ % KGB_SEGMENTS);
     std::memcpy(b->h_seg[k], recs, sizeof(BatchRec) * (size_t)nrec);
@@ -440,7 +407,7 @@ int rgrid_batch_match_submit(rgrid_batch_t *b, const rgrid_match_options *opt, c
         hipLaunchKernelGGL(kgb_match<false>, dim3((unsigned)nwg), dim3(KGB_THREADS), lds, b->stream, Bf);
         hipLaunchKernelGGL(kgb_best, dim3((unsigned)nrec), dim3(KGB_THREADS), 0, b->stream, Bf);
     }
-    GB_TRY(b, hipGetLastError());
+    G_TRY(b, hipGetLastError());
     b->outstanding = true;
     return RGRID_OK;
 }
@@ -451,8 +418,8 @@ int rgrid_batch_match_collect(rgrid_batch_t *b, int *status, double *pose_estima
     const int count = b->sub_count;
     if (count > 0 && (!status || !pose_estimates || !scores)) return RGRID_ERR_INVALID;
     b->outstanding = false;
-    GB_TRY(b, hipSetDevice(b->device));
-    GB_TRY(b, hipStreamSynchronize(b->stream));
+    G_TRY(b, hipSetDevice(b->device));
+    G_TRY(b, hipStreamSynchronize(b->stream));
     for (int j = 0; j < count; ++j) {
         const Pending &P = b->sub[(size_t)j];
         status[j] = P.status;
@@ -461,19 +428,8 @@ int rgrid_batch_match_collect(rgrid_batch_t *b, int *status, double *pose_estima
         if (best3) best3[3 * j] = best3[3 * j + 1] = best3[3 * j + 2] = 0;
         if (info3) info3[3 * j] = info3[3 * j + 1] = info3[3 * j + 2] = 0;
         if (P.status != RGRID_OK) continue;
-        // as rgrid_match after its synchronisation
-        const BestRec &o = b->h_out[P.rec];
-        const int W = 2 * P.num_linear + 1;
-        const int id = o.id;
-        const int scan = id / (W * W), r = id - scan * (W * W);
-        const int xo = r / W - P.num_linear, yo = r - (r / W) * W - P.num_linear;
-        const double x = -yo * P.res, y = -xo * P.res, orientation = (scan - P.num_angular) * P.step;
-        pose_estimates[3 * j] = P.pose[0] + x;                                              // :106-110
-        pose_estimates[3 * j + 1] = P.pose[1] + y;
-        pose_estimates[3 * j + 2] = P.pose[2] + orientation;
-        scores[j] = (double)o.score;
-        if (best3) { best3[3 * j] = scan; best3[3 * j + 1] = xo; best3[3 * j + 2] = yo; }
-        if (info3) { info3[3 * j] = P.num_scans; info3[3 * j + 1] = P.num_linear; info3[3 * j + 2] = (int)P.ncand; }
+        decode_best(P.plan, P.pose, b->h_out[P.rec], &pose_estimates[3 * j], &scores[j], best3 ? &best3[3 * j] : nullptr,
+                    info3 ? &info3[3 * j] : nullptr);
     }
     return RGRID_OK;
 }

@@ -175,6 +175,13 @@ def test_per_scan_status_and_whole_call_refusals(fm):
     assert fm.SetGrid_code(0, cells, res05, max_xy) == INVALID                     # ... and no grid changes under a launch
     assert all(MC.same_bits(a, b) for a, b in zip(fm.collect(), want))
     still_works()
+    # windows whose counts no int holds, negative or NaN windows: rgrid_match's answer, for every scan of the call (options are per call)
+    far = (0, np.zeros(3), np.array([[30.0, 30.0], [31.0, 29.0]], np.float32))
+    for window in (dict(linear_search_window=1e12), dict(linear_search_window=-0.1), dict(angular_search_window=-0.1),
+                   dict(angular_search_window=float("nan"))):
+        res = fm.match([good[0], far], M.RealTimeCorrelativeScanMatcherOptions(**window))
+        assert [r.status for r in res] == [CAPACITY, CAPACITY], window
+        still_works()
     big = M.ScanMatchFleet(max_scans=1, max_points=64, max_cells=480 * 480, max_rotations=2000)
     big.SetGrid(0, cells, res05, max_xy)
     assert big.match(good[:1])[0].status == CAPACITY                               # max_rotations > 1024: rgrid_match's limit

@@ -104,6 +104,7 @@ def test_match_options_windows_and_errors(gf, oracle_lib):
     o = RealTimeCorrelativeScanMatcherOptions(linear_search_window=0.35, angular_search_window=math.radians(6.0),
                                               translation_delta_cost_weight=2.0, rotation_delta_cost_weight=5.0)
     r = gf.Match(true + [0.2, -0.1, 0.03], pts, o)
+    score_first = r.score
     score, pose, best, info = oracle_match(true + [0.2, -0.1, 0.03], pts, cells, 0.1, max_xy, 0.35, math.radians(6.0), 2.0, 5.0)
     assert r.info == info and r.best == best and abs(r.score - score) <= 1.2e-7 * score
     assert info[1] == 4                                                            # ceil(0.35 / 0.1)
@@ -116,6 +117,15 @@ def test_match_options_windows_and_errors(gf, oracle_lib):
     with pytest.raises(RgridError) as e:                                           # more rotated scans than the handle holds
         gf.Match(np.zeros(3), np.array([[5000.0, 5000.0]], np.float32))
     assert e.value.code == -4
+    # windows whose counts no int holds, negative or NaN windows: the capacity error of the shared search plan, before any launch
+    far = np.array([[30.0, 30.0], [31.0, 29.0]], np.float32)
+    for window in (dict(linear_search_window=1e12), dict(linear_search_window=-0.1), dict(angular_search_window=-0.1),
+                   dict(angular_search_window=float("nan"))):
+        with pytest.raises(RgridError) as e:
+            gf.Match(np.zeros(3), far, RealTimeCorrelativeScanMatcherOptions(**window))
+        assert e.value.code == -4, window
+    again = gf.Match(true + [0.2, -0.1, 0.03], pts, o)                             # ... and the handle is as it was
+    assert again.best == best and again.info == info and again.score == score_first   # (a float32, exactly)
 
 
 def test_insert_matches_oracle_cell_for_cell_and_feeds_the_matcher(gf, oracle_lib):
