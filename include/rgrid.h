@@ -187,12 +187,15 @@ typedef struct rgrid_batch_scan {      /* one scan of a call */
     double initial_pose[3];            /* x, y, angle */
 } rgrid_batch_scan;
 
-/* max_rotations: rotated scans a single scan may need (2 * num_angular + 1); rgrid_match's limit of 1024 holds here too. */
+/* max_rotations: rotated scans a single scan may need (2 * num_angular + 1); rgrid_match's limit of 1024 holds here too.
+ * RGRID_ERR_CAPACITY when one staging segment -- 280 * max_scans + 8 * max_scans * (2 * R + 2 * max_points) bytes plus alignment,
+ * R = min(max_rotations, 1024): the records, rotation tables and rotated points of a match AND the records and raw points of a
+ * refinement, reserved for every handle -- would exceed 2^31 - 1 bytes, or max_points exceeds 16384. */
 int rgrid_batch_create(int max_scans, int max_points, int num_grids, long max_cells, int max_rotations, int device,
                        rgrid_batch_t **out);
 void rgrid_batch_destroy(rgrid_batch_t *b);
 
-/* rgrid_set_grid for slot `grid`.  RGRID_ERR_INVALID between a submit and its collect. */
+/* rgrid_set_grid for slot `grid`.  RGRID_ERR_INVALID between a submit (of any kind) and its collect. */
 int rgrid_batch_set_grid(rgrid_batch_t *b, int grid, const uint16_t *cells, int num_x_cells, int num_y_cells,
                          double resolution, double max_x, double max_y);
 
@@ -214,10 +217,49 @@ int rgrid_batch_match_collect(rgrid_batch_t *b, int *status, double *pose_estima
 enum { RGRID_BATCH_REDUCE_ARRIVAL = 0, RGRID_BATCH_REDUCE_LAUNCH = 1 };
 int rgrid_batch_set_reduction(rgrid_batch_t *b, int mode);
 
-/* Host seconds the last submit spent before its launch (initial rotations, search parameters, rotation tables, packing). */
+/* Host seconds the last submit, of whichever kind, spent before its launch (initial rotations, search parameters, rotation
+ * tables, packing). */
 double rgrid_batch_last_prepare_seconds(rgrid_batch_t *b);
 
+/* ---- fleet refinement: CeresScanMatcher2D::Match for one scan of many robots, one launch per call (kgb_refine, one workgroup
+ * per scan, csrc/rgrid_batch.hip).  Every scan's pose_estimate and summary are exactly what rgrid_refine_match returns for that
+ * scan, that grid and those options.  A handle has ONE pending submit at a time, of any kind, and each kind has its own collect:
+ * a collect of another kind than the pending submit is RGRID_ERR_INVALID and leaves the submit pending.  The ABI version stays 4:
+ * a caller that may meet an older library looks for these symbols. */
+typedef struct rgrid_batch_refine_scan {   /* one scan of a refine call */
+    int grid;                              /* resident grid slot it is refined against */
+    int n;                                 /* points */
+    const float *points_xy;                /* tracking frame, 2*n floats */
+    double target_translation[2];          /* the prediction's translation */
+    double initial_pose[3];                /* the correlative matcher's answer */
+} rgrid_batch_refine_scan;
+
+/* Enqueues the refinement of scans[0 .. count) and returns without waiting.  Refused as a whole with RGRID_ERR_INVALID, nothing
+ * launched and the handle still usable, for what rgrid_batch_match_submit refuses as a whole, a pending submit of any kind, and
+ * the options rgrid_refine_match refuses (a weight not > 0, max_num_iterations < 0).  Per scan, in collect's status[j]:
+ * RGRID_ERR_EMPTY (n == 0), RGRID_ERR_CAPACITY (n > max_points); such a scan gets no workgroup.  The points are copied before
+ * the call returns. */
+int rgrid_batch_refine_submit(rgrid_batch_t *b, const rgrid_refine_options *opt, const rgrid_batch_refine_scan *scans, int count);
+
+/* Waits and hands out the pending refine submit's results in its order: status (count), pose_estimates (3 * count), summaries
+ * (count, nullable); entries of a scan whose status is not RGRID_OK are zero. */
+int rgrid_batch_refine_collect(rgrid_batch_t *b, int *status, double *pose_estimates, rgrid_refine_summary *summaries);
+
+/* MapBuilder::ScanMatch (map_builder.cc:34-55) for a batch: the correlative match, then the refinement started from the match's
+ * pose estimate with target_translation = initial_pose[0:2] -- two launches on the handle's stream (three with
+ * RGRID_BATCH_REDUCE_LAUNCH) and NO host synchronisation between them: the refinement decodes each scan's winning candidate on
+ * the device.  Whole-call refusals: those of both submits above.  Per-scan statuses: rgrid_batch_match_submit's; a scan whose
+ * status is not RGRID_OK is neither matched nor refined. */
+int rgrid_batch_scan_match_submit(rgrid_batch_t *b, const rgrid_match_options *mopt, const rgrid_refine_options *ropt,
+                                  const rgrid_batch_scan *scans, int count);
+
+/* Both stages' results: status, coarse_poses, scores, best3, info3 as rgrid_batch_match_collect gives them (best3 / info3
+ * nullable), pose_estimates (3 * count) and summaries (count, nullable) as rgrid_batch_refine_collect gives them. */
+int rgrid_batch_scan_match_collect(rgrid_batch_t *b, int *status, double *coarse_poses, double *scores, int *best3, int *info3,
+                                   double *pose_estimates, rgrid_refine_summary *summaries);
+
 int rgrid_batch_sizeof_scan(void);
+int rgrid_batch_sizeof_refine_scan(void);
 const char *rgrid_batch_last_hip_error(rgrid_batch_t *b);
 
 const char *rgrid_strerror(int code);

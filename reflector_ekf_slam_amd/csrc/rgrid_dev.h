@@ -120,20 +120,30 @@ void rotation_table(const MatchPlan &plan, float *cs_out)
     for (int s = 0; s < plan.num_scans; ++s, delta_theta += plan.step) rotation_cs((float)delta_theta, &cs_out[2 * s], &cs_out[2 * s + 1]);
 }
 
-// What Match does after its candidate loop (:106-110): the winning candidate id -> (scan, x offset, y offset) -> the pose estimate;
-// best3 and info3 may be null
-void decode_best(const MatchPlan &plan, const double initial_pose[3], const BestRec &best, double pose_estimate[3], double *score, int *best3, int *info3)
+// The winning candidate id -> sxy = (scan, x offset, y offset) -> the pose estimate (:106-110).  Integer division, int -> double,
+// one multiply and one add per component, no libm: the host (decode_best) and the device (kgb_refine, which starts the refinement
+// from the match's winner without a host round trip) get the same bits from this one text.
+__host__ __device__ static inline void decode_candidate(int num_linear, int num_angular, double res, double step, const double initial_pose[3],
+                                                        int id, int sxy[3], double pose_estimate[3])
 {
 #pragma clang fp contract(off)
-    const int W = 2 * plan.num_linear + 1;
-    const int scan = best.id / (W * W), r = best.id - scan * (W * W);
-    const int xo = r / W - plan.num_linear, yo = r - (r / W) * W - plan.num_linear;
-    const double x = -yo * plan.res, y = -xo * plan.res, orientation = (scan - plan.num_angular) * plan.step;
+    const int W = 2 * num_linear + 1;
+    const int scan = id / (W * W), r = id - scan * (W * W);
+    const int xo = r / W - num_linear, yo = r - (r / W) * W - num_linear;
+    const double x = -yo * res, y = -xo * res, orientation = (scan - num_angular) * step;
     pose_estimate[0] = initial_pose[0] + x;
     pose_estimate[1] = initial_pose[1] + y;
     pose_estimate[2] = initial_pose[2] + orientation;
+    sxy[0] = scan; sxy[1] = xo; sxy[2] = yo;
+}
+
+// What Match does after its candidate loop (:106-110); best3 and info3 may be null
+void decode_best(const MatchPlan &plan, const double initial_pose[3], const BestRec &best, double pose_estimate[3], double *score, int *best3, int *info3)
+{
+    int sxy[3];
+    decode_candidate(plan.num_linear, plan.num_angular, plan.res, plan.step, initial_pose, best.id, sxy, pose_estimate);
     *score = (double)best.score;
-    if (best3) { best3[0] = scan; best3[1] = xo; best3[2] = yo; }
+    if (best3) { best3[0] = sxy[0]; best3[1] = sxy[1]; best3[2] = sxy[2]; }
     if (info3) { info3[0] = plan.num_scans; info3[1] = plan.num_linear; info3[2] = (int)plan.ncand; }
 }
 

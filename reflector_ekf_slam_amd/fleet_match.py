@@ -8,6 +8,13 @@ that scan, bit for bit, plus a ``status``.  ``pose_fixes`` turns a tick's result
 ``fleet.scan_event``: the reference's USE_GPS deployment is ``fleet.predict_poses(times)`` -> ``matcher.match(...)`` ->
 ``fleet.scan_event(member, t, cloud, pose_fix=...)`` -> ``fleet.submit``.
 
+The second step of the reference's ``MapBuilder::ScanMatch`` (map_builder.cc:34-55), ``CeresScanMatcher2D::Match``, is here for a
+batch too: ``refine(scans)`` takes ``(grid_slot, target_translation, initial_pose, points_xy)`` per scan and runs ONE launch of
+kgb_refine (one workgroup per scan), each result the bits of ``GridFrontEnd.RefineMatch``; ``scan_match(scans)`` takes what
+``match`` takes and chains both steps on the handle's stream without a host wait between them, returning per scan a
+``FleetScanMatchResult`` with ``.coarse`` (the match) and ``.fine`` (the refinement).  ``pose_fixes`` of those yields the refined
+poses: the fix the reference's node fuses.  A handle has one pending submit at a time, of any kind.
+
 All arithmetic happens in the HIP kernel behind librgrid.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -18,7 +25,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .grid import MatchResult, RealTimeCorrelativeScanMatcherOptions, RgridError, _lib_rgrid, _MatchOptions
+from .grid import (CeresScanMatcherOptions2D, MatchResult, RealTimeCorrelativeScanMatcherOptions, RefineResult, RgridError, _lib_rgrid,
+                   _MatchOptions, _RefineOptions, _RefineSummary)
 
 RGRID_OK, RGRID_ERR_INVALID, RGRID_ERR_CAPACITY, RGRID_ERR_EMPTY = 0, -1, -4, -6
 REDUCE_ARRIVAL, REDUCE_LAUNCH = 0, 1        # rgrid_batch_set_reduction
@@ -29,12 +37,39 @@ class RgridBatchScan(C.Structure):
     _fields_ = [("grid", C.c_int), ("n", C.c_int), ("points_xy", C.c_void_p), ("initial_pose", C.c_double * 3)]
 
 
+class RgridBatchRefineScan(C.Structure):
+    """struct rgrid_batch_refine_scan (include/rgrid.h)."""
+    _fields_ = [("grid", C.c_int), ("n", C.c_int), ("points_xy", C.c_void_p), ("target_translation", C.c_double * 2),
+                ("initial_pose", C.c_double * 3)]
+
+
 @dataclass
 class FleetMatchResult(MatchResult):
     status: int = 0                  # RGRID_OK, or the scan's own error: -6 empty cloud, -4 more points / rotated scans than the handle holds
 
 
+@dataclass
+class FleetRefineResult(RefineResult):
+    status: int = 0                  # RGRID_OK, -6 empty cloud, -4 more points than the handle holds (all other fields zero then)
+
+
+@dataclass
+class FleetScanMatchResult:
+    """MapBuilder::ScanMatch for one scan: the correlative match and the refinement started from it."""
+    coarse: FleetMatchResult
+    fine: FleetRefineResult
+
+    @property
+    def pose_estimate(self):
+        return self.fine.pose_estimate
+
+    @property
+    def status(self):
+        return self.coarse.status
+
+
 _ready = None
+_refine_ready = None
 
 
 def _batch_lib():
@@ -65,8 +100,50 @@ def _batch_lib():
     return L
 
 
+def _refine_lib():
+    """``_batch_lib()`` with the argtypes of the refine and match-plus-refine calls set.  Raises LibraryMissing when the built library
+    has no such calls (the ABI version does not tell: they are looked up by name); the match calls keep working then."""
+    global _refine_ready
+    if _refine_ready is not None:
+        return _refine_ready
+    L = _batch_lib()
+    names = ("rgrid_batch_refine_submit", "rgrid_batch_refine_collect", "rgrid_batch_scan_match_submit",
+             "rgrid_batch_scan_match_collect", "rgrid_batch_sizeof_refine_scan")
+    missing = [n for n in names if not hasattr(L, n)]
+    if missing:
+        raise _lib.LibraryMissing(f"librgrid.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
+    L.rgrid_batch_sizeof_refine_scan.restype = C.c_int
+    if L.rgrid_batch_sizeof_refine_scan() != C.sizeof(RgridBatchRefineScan):
+        raise _lib.LibraryMissing(f"librgrid.so: struct rgrid_batch_refine_scan has {L.rgrid_batch_sizeof_refine_scan()} bytes, this package "
+                                  f"packs {C.sizeof(RgridBatchRefineScan)}: rebuild it (python __graft_entry__.py)")
+    vp = C.c_void_p
+    L.rgrid_batch_refine_submit.argtypes = [vp, C.POINTER(_RefineOptions), vp, C.c_int]
+    L.rgrid_batch_refine_collect.argtypes = [vp, vp, vp, vp]
+    L.rgrid_batch_scan_match_submit.argtypes = [vp, C.POINTER(_MatchOptions), C.POINTER(_RefineOptions), vp, C.c_int]
+    L.rgrid_batch_scan_match_collect.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    _refine_ready = L
+    return L
+
+
+def _refine_options(o):
+    o = o or CeresScanMatcherOptions2D()
+    return _RefineOptions(o.occupied_space_weight, o.translation_weight, o.rotation_weight, int(o.max_num_iterations),
+                          1 if o.use_nonmonotonic_steps else 0)
+
+
+def _match_options(o):
+    o = o or RealTimeCorrelativeScanMatcherOptions()
+    return _MatchOptions(o.linear_search_window, o.angular_search_window, o.translation_delta_cost_weight, o.rotation_delta_cost_weight)
+
+
+def _refine_results(count, status, pose, summ):
+    return [FleetRefineResult(pose[i].copy(), float(summ[i].initial_cost), float(summ[i].final_cost), int(summ[i].iterations),
+                              int(summ[i].termination), int(status[i])) for i in range(count)]
+
+
 def pose_fixes(results):
-    """Per scan ``(x, y, yaw)`` of the matched pose, or None when its status is not OK: the ``pose_fix`` of ``fleet.scan_event``."""
+    """Per scan ``(x, y, yaw)`` of the matched pose -- the refined one for ``scan_match``'s results -- or None when its status is
+    not OK: the ``pose_fix`` of ``fleet.scan_event``."""
     return [tuple(float(v) for v in r.pose_estimate) if r.status == RGRID_OK else None for r in results]
 
 
@@ -177,6 +254,103 @@ class ScanMatchFleet:
         self.submit(scans, options)
         return self.collect()
 
+    # -- CeresScanMatcher2D::Match for a batch -----------------------------------
+    @staticmethod
+    def pack_refine(scans):
+        """scans: iterable of (grid_slot, target_translation, initial_pose, points_xy).  -> (ctypes array of rgrid_batch_refine_scan,
+        count, the arrays it points into)."""
+        scans = list(scans)
+        arr = (RgridBatchRefineScan * max(len(scans), 1))()
+        keep = []
+        for i, (slot, target, pose, points) in enumerate(scans):
+            pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+            keep.append(pts)
+            s = arr[i]
+            s.grid, s.n = int(slot), pts.shape[0]
+            s.points_xy = pts.ctypes.data if s.n else None
+            s.target_translation[0], s.target_translation[1] = float(target[0]), float(target[1])
+            s.initial_pose[0], s.initial_pose[1], s.initial_pose[2] = float(pose[0]), float(pose[1]), float(pose[2])
+        return arr, len(scans), keep
+
+    def submit_refine_packed_code(self, packed, options: CeresScanMatcherOptions2D | None = None) -> int:
+        co = _refine_options(options)
+        rc = _refine_lib().rgrid_batch_refine_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1])
+        if rc == 0:
+            self._pending = packed[1]
+        return rc
+
+    def submit_refine_code(self, scans, options: CeresScanMatcherOptions2D | None = None) -> int:
+        return self.submit_refine_packed_code(self.pack_refine(scans), options)
+
+    def submit_refine(self, scans, options: CeresScanMatcherOptions2D | None = None):
+        """One scan per entry, any grid slot each, the same options for all: ONE launch of kgb_refine; returns without waiting."""
+        self._chk(self.submit_refine_code(scans, options), "rgrid_batch_refine_submit")
+
+    def collect_refine_code(self):
+        """-> (rc, [FleetRefineResult]) of the refine submit that has not been collected."""
+        count = self._pending or 0
+        n = max(count, 1)
+        status, pose, summ = np.zeros(n, np.int32), np.zeros((n, 3)), (_RefineSummary * n)()
+        rc = _refine_lib().rgrid_batch_refine_collect(self._h, status.ctypes.data, pose.ctypes.data, C.cast(summ, C.c_void_p))
+        if rc != 0:
+            return rc, []
+        self._pending = None
+        return 0, _refine_results(count, status, pose, summ)
+
+    def collect_refine(self):
+        rc, out = self.collect_refine_code()
+        self._chk(rc, "rgrid_batch_refine_collect")
+        return out
+
+    def refine(self, scans, options: CeresScanMatcherOptions2D | None = None):
+        self.submit_refine(scans, options)
+        return self.collect_refine()
+
+    # -- MapBuilder::ScanMatch for a batch: match, then refine, no host wait between them ---
+    def submit_scan_match_packed_code(self, packed, match_options: RealTimeCorrelativeScanMatcherOptions | None = None,
+                                      refine_options: CeresScanMatcherOptions2D | None = None) -> int:
+        """``submit_scan_match_code`` for what ``pack`` returned."""
+        cm, cr = _match_options(match_options), _refine_options(refine_options)
+        rc = _refine_lib().rgrid_batch_scan_match_submit(self._h, C.byref(cm), C.byref(cr), C.cast(packed[0], C.c_void_p), packed[1])
+        if rc == 0:
+            self._pending = packed[1]
+        return rc
+
+    def submit_scan_match_code(self, scans, match_options=None, refine_options=None) -> int:
+        return self.submit_scan_match_packed_code(self.pack(scans), match_options, refine_options)
+
+    def submit_scan_match(self, scans, match_options: RealTimeCorrelativeScanMatcherOptions | None = None,
+                          refine_options: CeresScanMatcherOptions2D | None = None):
+        """scans as ``submit`` takes them: the match's launch and the refinement's, back to back on the handle's stream; the
+        refinement starts from each scan's matched pose with target_translation = initial_pose[:2] (map_builder.cc:49-53)."""
+        self._chk(self.submit_scan_match_code(scans, match_options, refine_options), "rgrid_batch_scan_match_submit")
+
+    def collect_scan_match_code(self):
+        """-> (rc, [FleetScanMatchResult]) of the match-plus-refine submit that has not been collected."""
+        count = self._pending or 0
+        n = max(count, 1)
+        status, coarse, score = np.zeros(n, np.int32), np.zeros((n, 3)), np.zeros(n)
+        best, info = np.zeros((n, 3), np.int32), np.zeros((n, 3), np.int32)
+        pose, summ = np.zeros((n, 3)), (_RefineSummary * n)()
+        rc = _refine_lib().rgrid_batch_scan_match_collect(self._h, status.ctypes.data, coarse.ctypes.data, score.ctypes.data,
+                                                          best.ctypes.data, info.ctypes.data, pose.ctypes.data, C.cast(summ, C.c_void_p))
+        if rc != 0:
+            return rc, []
+        self._pending = None
+        fine = _refine_results(count, status, pose, summ)
+        return 0, [FleetScanMatchResult(FleetMatchResult(float(score[i]), coarse[i].copy(), tuple(int(v) for v in best[i]),
+                                                         tuple(int(v) for v in info[i]), int(status[i])), fine[i]) for i in range(count)]
+
+    def collect_scan_match(self):
+        rc, out = self.collect_scan_match_code()
+        self._chk(rc, "rgrid_batch_scan_match_collect")
+        return out
+
+    def scan_match(self, scans, match_options: RealTimeCorrelativeScanMatcherOptions | None = None,
+                   refine_options: CeresScanMatcherOptions2D | None = None):
+        self.submit_scan_match(scans, match_options, refine_options)
+        return self.collect_scan_match()
+
     def last_prepare_seconds(self) -> float:
-        """Host time the last submit spent before its launch: initial rotations, search parameters, rotation tables, packing."""
+        """Host time the last submit (of any kind) spent before its launch: initial rotations, search parameters, rotation tables, packing."""
         return float(self._L.rgrid_batch_last_prepare_seconds(self._h))
