@@ -258,8 +258,46 @@ int rgrid_batch_scan_match_submit(rgrid_batch_t *b, const rgrid_match_options *m
 int rgrid_batch_scan_match_collect(rgrid_batch_t *b, int *status, double *coarse_poses, double *scores, int *best3, int *info3,
                                    double *pose_estimates, rgrid_refine_summary *summaries);
 
+/* ---- fleet inserter: ProbabilityGridRangeDataInserter2D::Insert with its GrowAsNeeded (MapBuilder::InsertIntoSubmap,
+ * map_builder.cc:110-120) for one scan of many robots, each into its own resident slot, ONE launch per call (kgb_insert, one
+ * workgroup per scan, csrc/rgrid_batch.hip).  The specification is the pair of single calls: after collect, slot scans[j].grid
+ * holds the cells (bit for bit) and the limits that an rgrid_t holding the same grid, created with the batch's max_cells, holds
+ * after rgrid_grow_as_needed(...) followed by rgrid_insert(...), and status[j] is the first code of that pair that is not RGRID_OK:
+ *   RGRID_ERR_INVALID   a non-finite coordinate (slot untouched);
+ *   RGRID_ERR_CAPACITY  growth beyond max_cells (slot untouched); n_returns or n_misses above max_points, or an end point outside
+ *                       the grid after growth (slot grown as the pair grows it, nothing inserted);
+ *   RGRID_OK            otherwise, a scan with neither returns nor misses included.
+ * Other scans of the call are unaffected.  The map stays on the device: a later match, refine or scan_match submit reads the
+ * inserted cells and the grown limits.  The ABI version stays 4: a caller that may meet an older library looks for these symbols. */
+typedef struct rgrid_insert_options { float hit_probability, miss_probability; int insert_free_space; } rgrid_insert_options;
+typedef struct rgrid_batch_insert_scan {   /* 40 bytes on LP64 */
+    int grid;                              /* resident slot the scan is inserted into */
+    int n_returns, n_misses;
+    const float *returns_xy, *misses_xy;   /* frame of the grid, 2*n floats each, NULL when n == 0 */
+    float origin_xy[2];
+} rgrid_batch_insert_scan;
+
+/* Enqueues the insertion of scans[0 .. count) and returns without waiting; the points are copied before the call returns.  Refused
+ * as a whole with RGRID_ERR_INVALID, nothing launched and the handle still usable: a null b, opt or scans, count outside
+ * [0, max_scans], a slot out of range or not yet set, a negative point count, a null pointer with a positive count, a probability
+ * not strictly inside (0, 1), a pending submit of any kind, and TWO SCANS NAMING THE SAME SLOT -- the reference inserts one after
+ * the other with FinishUpdate in between, two insertions into one grid in one launch have no reference meaning: robots that share a
+ * map insert in consecutive calls.  The two lookup tables stay on the device and are rebuilt only when the probabilities change. */
+int rgrid_batch_insert_submit(rgrid_batch_t *b, const rgrid_insert_options *opt, const rgrid_batch_insert_scan *scans, int count);
+
+/* Waits and hands out status (count) of the pending insert submit, in its order.  RGRID_ERR_INVALID without one, or while a submit
+ * of another kind is pending (which stays pending). */
+int rgrid_batch_insert_collect(rgrid_batch_t *b, int *status);
+
+/* rgrid_get_limits / rgrid_get_grid for slot `grid` (any pointer of get_limits may be NULL; get_grid: RGRID_ERR_BUFFER when cap is
+ * below num_x_cells * num_y_cells).  RGRID_ERR_INVALID for a slot not yet set and between a submit (of any kind) and its collect. */
+int rgrid_batch_get_limits(rgrid_batch_t *b, int grid, int *num_x_cells, int *num_y_cells, double *resolution, double *max_x,
+                           double *max_y);
+int rgrid_batch_get_grid(rgrid_batch_t *b, int grid, uint16_t *cells, long cap);
+
 int rgrid_batch_sizeof_scan(void);
 int rgrid_batch_sizeof_refine_scan(void);
+int rgrid_batch_sizeof_insert_scan(void);
 const char *rgrid_batch_last_hip_error(rgrid_batch_t *b);
 
 const char *rgrid_strerror(int code);

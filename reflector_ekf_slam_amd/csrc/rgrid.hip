@@ -253,31 +253,8 @@ __global__ __launch_bounds__(256) void kg_best(const BestRec *__restrict__ block
 }
 
 // ---- range-data inserter --------------------------------------------------------------------------
-// ApplyLookupTable (probability_grid.cc:38-53): a cell without the update marker takes table[cell] (which carries the
-// marker).  Concurrent lanes may race on one cell, but within a phase (hits, then misses: separate launches) every
-// writer stores the SAME value table[original], and a reader sees either the original or the marked value: the plain
-// 16-bit load/store pair gives the reference's result without atomics.
-struct InsertArgs {
-    int nx, ny, n_ret, n_miss;
-    double max_x, max_y, rs;           // rs = resolution / 1000 (superscaled limits, :48-53)
-    float ox, oy;
-};
-constexpr int SUBPX = 1000;
-constexpr unsigned MARKER = 32768u;
-
-__device__ static inline void apply_table(unsigned short *cells, int nx, int cx, int cy, const unsigned short *__restrict__ table)
-{
-    unsigned short *c = cells + (size_t)nx * cy + cx;
-    const unsigned short v = *c;
-    if (v < MARKER) *c = table[v];
-}
-__device__ static inline bool super_index(const InsertArgs &A, float px, float py, int &ix, int &iy)
-{
-    // superscaled MapLimits::GetCellIndex (map_limits.h:47-55): x index from y, y index from x
-    ix = (int)lround((A.max_y - (double)py) / A.rs - 0.5);
-    iy = (int)lround((A.max_x - (double)px) / A.rs - 0.5);
-    return ix >= 0 && iy >= 0 && (long long)ix < (long long)A.nx * SUBPX && (long long)iy < (long long)A.ny * SUBPX;
-}
+// InsertArgs, apply_table and super_index are rgrid_dev.h's (shared with kgb_insert of rgrid_batch.hip), with the note on the
+// races inside a phase.
 
 // end points of all rays (returns first, then misses); *bad = 1 if anything lies outside the grid
 __global__ __launch_bounds__(256) void kg_ends(InsertArgs A, const float *__restrict__ ret, const float *__restrict__ mis,
@@ -501,33 +478,6 @@ void texture_table(unsigned short *table)
         const int delta = 128 - li;
         const unsigned alpha = (unsigned)(delta > 0 ? 0 : -delta) & 255u, value = (unsigned)(delta > 0 ? delta : 0) & 255u;
         table[v] = (unsigned short)(value | ((value || alpha) ? alpha : 1u) << 8);
-    }
-}
-
-// ComputeLookupTableToApplyCorrespondenceCostOdds(Odds(probability)) (probability_values.cc:76-96), host float32
-void lookup_table(float probability, unsigned short *table)
-{
-#pragma clang fp contract(off)
-    const float kMinProbability = 0.1f, kMaxProbability = 1.f - kMinProbability;
-    const float lower = 1.f - kMaxProbability, upper = 1.f - kMinProbability;
-    auto cost_to_value = [&](float c) -> unsigned short {                        // BoundedFloatToValue (probability_values.h:15-29)
-        float cl = c;
-        if (cl > upper) cl = upper;
-        if (cl < lower) cl = lower;
-        return (unsigned short)((int)std::lround((cl - lower) * (32766.f / (upper - lower))) + 1);
-    };
-    const float odds = probability / (1.f - probability);
-    {
-        const float p = odds / (odds + 1.f);
-        table[0] = (unsigned short)(cost_to_value(1.f - p) + MARKER);
-    }
-    const float kScale = (upper - lower) / (32768 - 2.f);
-    for (int cell = 1; cell != 32768; ++cell) {
-        const float cost = cell * kScale + (lower - kScale);                     // kValueToCorrespondenceCost[cell]
-        const float pc = 1.f - cost;
-        const float o = odds * (pc / (1.f - pc));
-        const float p = o / (o + 1.f);
-        table[cell] = (unsigned short)(cost_to_value(1.f - p) + MARKER);
     }
 }
 
@@ -931,47 +881,17 @@ int rgrid_insert(rgrid_t *h, const float origin_xy[2], const float *returns_xy, 
     return *h->h_count ? RGRID_ERR_CAPACITY : RGRID_OK;
 }
 
-namespace {
-// Grid2D::GrowLimits(point) on the limits only (grid_2d.cc:64-75,93); false if the grown grid exceeds `max_cells`
-bool grow_limits_for(float px, float py, double res, long long max_cells, int &nx, int &ny, double &max_x, double &max_y, int &off_x, int &off_y)
-{
-#pragma clang fp contract(off)
-    for (;;) {
-        const long ix = std::lround((max_y - (double)py) / res - 0.5), iy = std::lround((max_x - (double)px) / res - 0.5);
-        if (ix >= 0 && iy >= 0 && ix < nx && iy < ny) return true;
-        if (4ll * nx * ny > max_cells) return false;
-        const int xo = nx / 2, yo = ny / 2;
-        max_x = max_x + res * (double)yo;
-        max_y = max_y + res * (double)xo;
-        nx *= 2; ny *= 2; off_x += xo; off_y += yo;
-    }
-}
-}  // namespace
-
 int rgrid_grow_as_needed(rgrid_t *h, const float origin_xy[2], const float *returns_xy, int n_returns, const float *misses_xy,
                          int n_misses)
 {
     if (!h || !origin_xy || n_returns < 0 || n_misses < 0 || (n_returns > 0 && !returns_xy) || (n_misses > 0 && !misses_xy))
         return RGRID_ERR_INVALID;
     if (!h->have_grid) return RGRID_ERR_INVALID;
-    // Eigen::AlignedBox2f(origin).extend(every return and miss)  (probability_grid_range_data_inserter_2d.cc:23-33)
-    float lo[2] = {origin_xy[0], origin_xy[1]}, hi[2] = {origin_xy[0], origin_xy[1]};
-    auto extend = [&](const float *p, int n) {
-        for (int i = 0; i < 2 * n; ++i) {
-            const float v = p[i];
-            if (!std::isfinite(v)) return false;
-            if (v < lo[i & 1]) lo[i & 1] = v;
-            if (v > hi[i & 1]) hi[i & 1] = v;
-        }
-        return true;
-    };
-    if (!std::isfinite(lo[0]) || !std::isfinite(lo[1]) || !extend(returns_xy, n_returns) || !extend(misses_xy, n_misses)) return RGRID_ERR_INVALID;
-    const float pad = 1e-6f;                                                        // kPadding (:25)
+    // the bounding box and Grid2D::GrowLimits for its corners, on the limits only (plan_growth of rgrid_dev.h)
     int nx = h->nx, ny = h->ny, off_x = 0, off_y = 0;
     double max_x = h->max_x, max_y = h->max_y;
-    if (!grow_limits_for(lo[0] - pad, lo[1] - pad, h->resolution, h->max_cells, nx, ny, max_x, max_y, off_x, off_y) ||
-        !grow_limits_for(hi[0] + pad, hi[1] + pad, h->resolution, h->max_cells, nx, ny, max_x, max_y, off_x, off_y))
-        return RGRID_ERR_CAPACITY;
+    const int rc = plan_growth(origin_xy, returns_xy, n_returns, misses_xy, n_misses, h->resolution, h->max_cells, nx, ny, max_x, max_y, off_x, off_y);
+    if (rc != RGRID_OK) return rc;
     if (nx == h->nx && ny == h->ny) return RGRID_OK;
     G_TRY(h, hipSetDevice(h->device));
     hipLaunchKernelGGL(kg_grow, dim3((nx + 255) / 256, ny), dim3(256), 0, h->stream, h->d_cells, h->nx, h->ny, h->d_cells2, nx, ny, off_x, off_y);

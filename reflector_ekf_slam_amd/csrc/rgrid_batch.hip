@@ -273,6 +273,185 @@ __global__ __launch_bounds__(1024) void kgb_refine(RefineBufs B)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// ProbabilityGridRangeDataInserter2D::Insert for a batch (GrowAsNeeded, the hit and miss tables, FinishUpdate:
+// probability_grid_range_data_inserter_2d.cc:20-114, MapBuilder::InsertIntoSubmap, map_builder.cc:110-120): ONE workgroup per
+// scan does, in its own grid slot, what rgrid_grow_as_needed + rgrid_insert do with kg_grow, kg_ends, kg_hits, kg_rays and
+// kg_finish.  A call names a slot at most once, so the workgroup owns its grid for the whole launch and the order the reference
+// needs -- growth, hits, misses, finish -- is a workgroup barrier: no workgroup waits for another.  DESIGN.md 10.4.
+#define KGI_THREADS 1024
+#define KGI_WAVES (KGI_THREADS / 64)
+#define KGI_GROW_PER 8                    // cells a thread holds in registers per step of the in-place move
+
+// One runnable scan of an insert call; an array of these lies at the start of the call's segment.
+struct InsertRec {
+    InsertArgs A;                         // limits AFTER the growth the host decided, counts, origin
+    long long cells_off;                  // its grid's first cell in the grid pool
+    int old_nx, old_ny, off_x, off_y;     // the grid as it lies there now and where its cell (0, 0) goes; no growth: old_nx == A.nx
+    int ret_off, mis_off;                 // float2 index of its returns in the float2 area, of its misses in the raw area
+};
+static_assert(sizeof(InsertRec) <= sizeof(BatchRec), "the insert records lie where a match's records lie");
+
+struct InsertBufs {
+    const unsigned char *seg;             // the call's segment: InsertRec[nrec] | ... | returns at f2_off | ... | misses at raw_off
+    int f2_off, raw_off;
+    unsigned short *cells;                // grid pool: read AND written, phase after phase -- no __restrict__, no const
+    const unsigned short *hit, *miss;     // the handle's two lookup tables
+    int *bad;                             // [max_scans], pinned host memory: 1 = an end point outside the grid, nothing inserted
+    int free_space;
+};
+
+// the workgroup's cell stores have been acknowledged, then the barrier: the next phase's loads, from any wave, see them
+__device__ static inline void cells_barrier()
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(KGI_THREADS) void kgb_insert(InsertBufs B)
+{
+#pragma clang fp contract(off)
+    __shared__ int s_pref[KGI_WAVES][65], s_lo[KGI_WAVES][64], s_step[KGI_WAVES][64];
+    __shared__ int s_box[KGI_WAVES][4];
+    const InsertRec &R = reinterpret_cast<const InsertRec *>(B.seg)[blockIdx.x];
+    const InsertArgs A = R.A;
+    unsigned short *cells = B.cells + R.cells_off;
+    const float *ret = reinterpret_cast<const float *>(B.seg + B.f2_off) + 2 * (size_t)R.ret_off;
+    const float *mis = reinterpret_cast<const float *>(B.seg + B.raw_off) + 2 * (size_t)R.mis_off;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = A.n_ret + A.n_miss;
+    // ---- kg_ends' flag: is the origin or any end point outside the (grown) grid?  Along the way, the box of cells they span.
+    int bx_i, by_i;
+    bool out = !super_index(A, A.ox, A.oy, bx_i, by_i);                            // the origin (:54-55)
+    int x0 = bx_i / SUBPX, x1 = x0, y0 = by_i / SUBPX, y1 = y0;
+    for (int i = tid; i < n; i += KGI_THREADS) {
+        const float *p = (i < A.n_ret) ? ret + 2 * i : mis + 2 * (i - A.n_ret);
+        int ix, iy;
+        out |= !super_index(A, p[0], p[1], ix, iy);
+        const int cx = ix / SUBPX, cy = iy / SUBPX;
+        x0 = min(x0, cx); x1 = max(x1, cx); y0 = min(y0, cy); y1 = max(y1, cy);
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        x0 = min(x0, __shfl_xor(x0, off, 64)); x1 = max(x1, __shfl_xor(x1, off, 64));
+        y0 = min(y0, __shfl_xor(y0, off, 64)); y1 = max(y1, __shfl_xor(y1, off, 64));
+    }
+    if (lane == 0) { s_box[wave][0] = x0; s_box[wave][1] = x1; s_box[wave][2] = y0; s_box[wave][3] = y1; }
+    const bool bad = __syncthreads_or(out);
+    for (int w = 0; w < KGI_WAVES; ++w) {
+        x0 = min(x0, s_box[w][0]); x1 = max(x1, s_box[w][1]); y0 = min(y0, s_box[w][2]); y1 = max(y1, s_box[w][3]);
+    }
+    // the same in every lane: kept in scalar registers through the phases (the kernel runs at 128 VGPRs)
+    x0 = __builtin_amdgcn_readfirstlane(x0); x1 = __builtin_amdgcn_readfirstlane(x1);
+    y0 = __builtin_amdgcn_readfirstlane(y0); y1 = __builtin_amdgcn_readfirstlane(y1);
+    bx_i = __builtin_amdgcn_readfirstlane(bx_i); by_i = __builtin_amdgcn_readfirstlane(by_i);
+    // ---- kg_grow in place (Grid2D::GrowLimits, grid_2d.cc:81-91).  Old cell (x, y) goes to (y + off_y) * nnx + x + off_x, never
+    // below its old index y * nx + x: walking the old cells in DESCENDING chunks -- all threads read, barrier, all write, barrier --
+    // a write lands only on a cell that has been read already (its own chunk's or a higher one's) or on one beyond the old grid.
+    if (R.old_nx != A.nx) {
+        const int onx = R.old_nx, ony = R.old_ny, nnx = A.nx, nny = A.ny, off_x = R.off_x, off_y = R.off_y;
+        const int total = onx * ony, chunk = KGI_THREADS * KGI_GROW_PER;
+        for (int hi = total; hi > 0; hi -= chunk) {
+            unsigned short v[KGI_GROW_PER];
+#pragma unroll
+            for (int u = 0; u < KGI_GROW_PER; ++u) {
+                const int k = hi - chunk + u * KGI_THREADS + tid;
+                v[u] = k >= 0 ? cells[k] : (unsigned short)0;
+            }
+            cells_barrier();                                                       // (the loads have arrived too: vmcnt counts both)
+#pragma unroll
+            for (int u = 0; u < KGI_GROW_PER; ++u) {
+                const int k = hi - chunk + u * KGI_THREADS + tid;
+                if (k >= 0) {
+                    const int y = k / onx, x = k - y * onx;
+                    cells[(y + off_y) * nnx + (x + off_x)] = v[u];
+                }
+            }
+            cells_barrier();
+        }
+        for (int y = wave; y < nny; y += KGI_WAVES) {                              // unknown (0) outside the window
+            const bool row_in = y >= off_y && y < off_y + ony;
+            for (int x = lane; x < nnx; x += 64)
+                if (!(row_in && x >= off_x && x < off_x + onx)) cells[y * nnx + x] = 0;
+        }
+        cells_barrier();
+    }
+    if (bad) {                                                                     // rgrid_insert's RGRID_ERR_CAPACITY: grown, nothing inserted
+        if (tid == 0) B.bad[blockIdx.x] = 1;
+        return;
+    }
+    // ---- kg_hits (:59-62)
+    for (int i = tid; i < A.n_ret; i += KGI_THREADS) {
+        int ix, iy;
+        super_index(A, ret[2 * i], ret[2 * i + 1], ix, iy);
+        apply_table(cells, A.nx, ix / SUBPX, iy / SUBPX, B.hit);
+    }
+    cells_barrier();
+    // ---- kg_rays: one WAVE per ray, the waves stride over origin -> return and origin -> miss.  The walk is kg_rays' text
+    // (rgrid.hip, where the closed form is derived), with the end point computed here and `continue` for its `return`.
+    if (B.free_space) {
+        for (int i = wave; i < n; i += KGI_WAVES) {
+            const float *p = (i < A.n_ret) ? ret + 2 * i : mis + 2 * (i - A.n_ret);
+            int ex_i, ey_i;
+            super_index(A, p[0], p[1], ex_i, ey_i);
+            ex_i = __builtin_amdgcn_readfirstlane(ex_i); ey_i = __builtin_amdgcn_readfirstlane(ey_i);   // the wave's ray: scalar from here on
+            const long long S = SUBPX;
+            long long bx = bx_i, by = by_i, ex = ex_i, ey = ey_i;
+            if (bx > ex) { long long t = bx; bx = ex; ex = t; t = by; by = ey; ey = t; }   // ordered by x (:24-27)
+            const int X0 = (int)(bx / S), X1 = (int)(ex / S);
+            if (X0 == X1) {                                                           // one pixel column (:35-47)
+                const int ya = (int)((by < ey ? by : ey) / S), yb = (int)((by < ey ? ey : by) / S);
+                for (int y = ya + lane; y <= yb; y += 64) apply_table(cells, A.nx, X0, y, B.miss);
+                continue;
+            }
+            const long long dx = ex - bx, dy = ey - by, den = 2 * S * dx;
+            const long long A0 = (2 * (by % S) + 1) * dx + (by / S) * den;            // absolute ordinate of the begin point (:64)
+            const long long first_pixel = 2 * S - 2 * (bx % S) - 1, last_pixel = 2 * (ex % S) + 1;
+            const bool up = dy > 0;
+            auto a_out = [&](int X) -> long long {                                    // ordinate at the right border of column X
+                return A0 + dy * (first_pixel + 2 * S * (long long)(X - X0) + ((X == X1) ? last_pixel - 2 * S : 0));
+            };
+            auto fdiv = [&](long long a) -> long long { return a / den; };            // a >= 0 inside the grid
+            auto cdiv = [&](long long a) -> long long { return (a + den - 1) / den; };
+            for (int Xc = X0; Xc <= X1; Xc += 64) {
+                const int X = Xc + lane;
+                int lo = 0, cnt = 0, step = 1;
+                if (X <= X1) {
+                    const long long ao = a_out(X);
+                    int r_in, r_out;
+                    if (up) { r_in = (X == X0) ? (int)(by / S) : (int)fdiv(a_out(X - 1)); r_out = (int)cdiv(ao) - 1; cnt = r_out - r_in + 1; }
+                    else { r_in = (X == X0) ? (int)(by / S) : (int)cdiv(a_out(X - 1)) - 1; r_out = (int)fdiv(ao); cnt = r_in - r_out + 1; step = -1; }
+                    if (cnt < 1) cnt = 1;                                             // the column's entry pixel is always visited
+                    lo = r_in;
+                }
+                int incl = cnt;                                                       // exclusive prefix sum of cnt over the wave
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
+                s_pref[wave][lane + 1] = incl; s_lo[wave][lane] = lo; s_step[wave][lane] = step;
+                if (lane == 0) s_pref[wave][0] = 0;
+                __builtin_amdgcn_wave_barrier();
+                const int total = s_pref[wave][64];
+                for (int q = lane; q < total; q += 64) {
+                    int a = 0, b = 63;                                                // column c with pref[c] <= q < pref[c+1]
+                    while (a < b) { const int mid = (a + b + 1) >> 1; if (s_pref[wave][mid] <= q) a = mid; else b = mid - 1; }
+                    const int row = s_lo[wave][a] + s_step[wave][a] * (q - s_pref[wave][a]);
+                    apply_table(cells, A.nx, Xc + a, row, B.miss);
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+    }
+    cells_barrier();
+    // ---- kg_finish (Grid2D::FinishUpdate, grid_2d.cc:20-29) over the box the origin and the end points span: every ray lies
+    // inside it, and the grid came in finished
+    for (int y = y0 + wave; y <= y1; y += KGI_WAVES)
+        for (int x = x0 + lane; x <= x1; x += 64) {
+            unsigned short *c = cells + (size_t)A.nx * y + x;
+            const unsigned short v = *c;
+            if (v >= MARKER) *c = (unsigned short)(v - MARKER);
+        }
+    if (tid == 0) B.bad[blockIdx.x] = 0;
+}
+
 struct GridSlot {
     bool set = false;
     int nx = 0, ny = 0;
@@ -289,7 +468,7 @@ struct Pending {
 // what a packed match launches with
 struct MatchWork { int nrec, nwg, nf2, n_max; };
 
-enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3 };                   // the pending submit
+enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3, KIND_INSERT = 4 };  // the pending submit
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -329,6 +508,12 @@ struct rgrid_batch {
     int *d_arrived = nullptr;
     BestRec *h_out = nullptr, *dv_out = nullptr;
     RefineOut *h_rout = nullptr, *dv_rout = nullptr;
+    // the inserter: the two lookup tables (uint16[32768] each) and the probabilities they were built for, a flag per record
+    unsigned short *d_hit = nullptr, *d_miss = nullptr;
+    float tab_hit_p = -1.f, tab_miss_p = -1.f;
+    int *h_bad = nullptr, *dv_bad = nullptr;
+    std::vector<unsigned long long> slot_call;   // the insert submit that named a slot last (a call names a slot once)
+    unsigned long long n_insert = 0;
     std::vector<GridSlot> grids;
     bool outstanding = false;
     int kind = 0;                          // KIND_* of the outstanding submit
@@ -455,6 +640,8 @@ int rgrid_batch_sizeof_scan(void) { return (int)sizeof(rgrid_batch_scan); }
 
 int rgrid_batch_sizeof_refine_scan(void) { return (int)sizeof(rgrid_batch_refine_scan); }
 
+int rgrid_batch_sizeof_insert_scan(void) { return (int)sizeof(rgrid_batch_insert_scan); }
+
 const char *rgrid_batch_last_hip_error(rgrid_batch_t *b) { return b ? b->hip_error.c_str() : ""; }
 
 double rgrid_batch_last_prepare_seconds(rgrid_batch_t *b) { return b ? b->prepare_seconds : 0.; }
@@ -477,6 +664,7 @@ int rgrid_batch_create(int max_scans, int max_points, int num_grids, long max_ce
     b->max_rotations = max_rotations; b->device = device;
     b->wgmap_off = wgmap_off; b->f2_off = f2_off; b->rrec_off = rrec_off; b->raw_off = raw_off; b->seg_bytes = seg_bytes;
     b->grids.resize((size_t)num_grids);
+    b->slot_call.assign((size_t)num_grids, 0ull);
     b->sub.resize(nS);
     b->pack.resize(raw_off);               // (the raw points go straight into the segment)
     int rc = [&]() -> int {
@@ -501,6 +689,10 @@ int rgrid_batch_create(int max_scans, int max_points, int num_grids, long max_ce
         G_TRY(b, hipHostMalloc((void **)&b->h_rout, sizeof(RefineOut) * nS, hipHostMallocMapped | hipHostMallocCoherent));
         G_TRY(b, hipHostGetDevicePointer(&dv, b->h_rout, 0)); b->dv_rout = (RefineOut *)dv;
         std::memset(b->h_rout, 0, sizeof(RefineOut) * nS);
+        G_TRY(b, hipHostMalloc((void **)&b->h_bad, sizeof(int) * nS, hipHostMallocMapped | hipHostMallocCoherent));
+        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_bad, 0)); b->dv_bad = (int *)dv;
+        std::memset(b->h_bad, 0, sizeof(int) * nS);
+        G_TRY(b, hipMalloc((void **)&b->d_hit, 2 * 32768)); G_TRY(b, hipMalloc((void **)&b->d_miss, 2 * 32768));
         G_TRY(b, hipMalloc((void **)&b->d_cells, sizeof(unsigned short) * (size_t)num_grids * (size_t)max_cells));
         G_TRY(b, hipMalloc((void **)&b->d_bb, sizeof(unsigned long long) * nS * nR));
         G_TRY(b, hipMalloc((void **)&b->d_arrived, sizeof(int) * nS));
@@ -521,11 +713,12 @@ void rgrid_batch_destroy(rgrid_batch_t *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    (void)hipFree(b->d_cells); (void)hipFree(b->d_bb); (void)hipFree(b->d_arrived);
+    (void)hipFree(b->d_cells); (void)hipFree(b->d_bb); (void)hipFree(b->d_arrived); (void)hipFree(b->d_hit); (void)hipFree(b->d_miss);
     for (int k = 0; k < KGB_SEGMENTS; ++k)
         if (b->h_seg[k]) { if (b->seg_in_vram) (void)hipFree(b->h_seg[k]); else (void)hipHostFree(b->h_seg[k]); }
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->h_rout) (void)hipHostFree(b->h_rout);
+    if (b->h_bad) (void)hipHostFree(b->h_bad);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -727,6 +920,128 @@ int rgrid_batch_scan_match_collect(rgrid_batch_t *b, int *status, double *coarse
         if (P.status != RGRID_OK) continue;
         decode_best(P.plan, P.pose, b->h_out[P.rec], &coarse_poses[3 * j], &scores[j], best3 ? &best3[3 * j] : nullptr,
                     info3 ? &info3[3 * j] : nullptr);
+    }
+    return RGRID_OK;
+}
+
+int rgrid_batch_get_limits(rgrid_batch_t *b, int grid, int *num_x_cells, int *num_y_cells, double *resolution, double *max_x, double *max_y)
+{
+    if (!b || grid < 0 || grid >= b->num_grids || !b->grids[(size_t)grid].set || b->outstanding) return RGRID_ERR_INVALID;
+    const GridSlot &g = b->grids[(size_t)grid];
+    if (num_x_cells) *num_x_cells = g.nx;
+    if (num_y_cells) *num_y_cells = g.ny;
+    if (resolution) *resolution = g.resolution;
+    if (max_x) *max_x = g.max_x;
+    if (max_y) *max_y = g.max_y;
+    return RGRID_OK;
+}
+
+int rgrid_batch_get_grid(rgrid_batch_t *b, int grid, uint16_t *cells, long cap)
+{
+    if (!b || !cells || grid < 0 || grid >= b->num_grids || !b->grids[(size_t)grid].set || b->outstanding) return RGRID_ERR_INVALID;
+    const GridSlot &g = b->grids[(size_t)grid];
+    const long long ncells = (long long)g.nx * g.ny;
+    if (cap < ncells) return RGRID_ERR_BUFFER;
+    G_TRY(b, hipSetDevice(b->device));
+    G_TRY(b, hipMemcpyAsync(cells, b->d_cells + (size_t)grid * (size_t)b->max_cells, sizeof(uint16_t) * (size_t)ncells, hipMemcpyDeviceToHost,
+                            b->stream));
+    G_TRY(b, hipStreamSynchronize(b->stream));
+    return RGRID_OK;
+}
+
+int rgrid_batch_insert_submit(rgrid_batch_t *b, const rgrid_insert_options *opt, const rgrid_batch_insert_scan *scans, int count)
+{
+    if (!b || !opt || !scans || count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
+    if (!(opt->hit_probability > 0.f && opt->hit_probability < 1.f) || !(opt->miss_probability > 0.f && opt->miss_probability < 1.f))
+        return RGRID_ERR_INVALID;
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_insert_scan &s = scans[j];
+        if (s.grid < 0 || s.grid >= b->num_grids || !b->grids[(size_t)s.grid].set || s.n_returns < 0 || s.n_misses < 0 ||
+            (s.n_returns > 0 && !s.returns_xy) || (s.n_misses > 0 && !s.misses_xy))
+            return RGRID_ERR_INVALID;
+    }
+    // a slot at most once per call: two insertions into one grid in one launch have no reference meaning (FinishUpdate lies between)
+    ++b->n_insert;
+    for (int j = 0; j < count; ++j) {
+        unsigned long long &seen = b->slot_call[(size_t)scans[j].grid];
+        if (seen == b->n_insert) return RGRID_ERR_INVALID;
+        seen = b->n_insert;
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    G_TRY(b, hipSetDevice(b->device));
+    if (opt->hit_probability != b->tab_hit_p || opt->miss_probability != b->tab_miss_p) {   // the tables only depend on the two options
+        std::vector<unsigned short> t(32768);
+        lookup_table(opt->hit_probability, t.data());
+        G_TRY(b, hipMemcpy(b->d_hit, t.data(), 2 * 32768, hipMemcpyHostToDevice));
+        lookup_table(opt->miss_probability, t.data());
+        G_TRY(b, hipMemcpy(b->d_miss, t.data(), 2 * 32768, hipMemcpyHostToDevice));
+        b->tab_hit_p = opt->hit_probability; b->tab_miss_p = opt->miss_probability;
+    }
+    const int k = (int)(b->n_submit % KGB_SEGMENTS);
+    InsertRec *recs = reinterpret_cast<InsertRec *>(b->pack.data());
+    float *ret = reinterpret_cast<float *>(b->h_seg[k] + b->f2_off), *mis = reinterpret_cast<float *>(b->h_seg[k] + b->raw_off);
+    int nrec = 0, nret = 0, nmis = 0;
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_insert_scan &s = scans[j];
+        GridSlot &g = b->grids[(size_t)s.grid];
+        Pending &P = b->sub[(size_t)j];
+        std::memset(&P, 0, sizeof(P));
+        P.rec = -1;
+        // rgrid_grow_as_needed: on the host, from the points that are copied anyway; the move itself is the workgroup's first phase
+        int nx = g.nx, ny = g.ny, off_x = 0, off_y = 0;
+        double max_x = g.max_x, max_y = g.max_y;
+        P.status = plan_growth(s.origin_xy, s.returns_xy, s.n_returns, s.misses_xy, s.n_misses, g.resolution, (long long)b->max_cells, nx, ny,
+                               max_x, max_y, off_x, off_y);
+        if (P.status != RGRID_OK) continue;                                        // the slot stays as it is
+        // rgrid_insert: more points than the handle stages.  The pair has grown the grid by then, so this scan's workgroup grows it too
+        const bool fits = s.n_returns <= b->max_points && s.n_misses <= b->max_points;
+        if (!fits) P.status = RGRID_ERR_CAPACITY;
+        if (!fits && nx == g.nx && ny == g.ny) continue;
+        InsertRec &R = recs[nrec];
+        std::memset(&R, 0, sizeof(R));
+        R.A.nx = nx; R.A.ny = ny; R.A.n_ret = fits ? s.n_returns : 0; R.A.n_miss = fits ? s.n_misses : 0;
+        R.A.max_x = max_x; R.A.max_y = max_y; R.A.rs = g.resolution / SUBPX;
+        R.A.ox = s.origin_xy[0]; R.A.oy = s.origin_xy[1];
+        R.cells_off = (long long)s.grid * (long long)b->max_cells;
+        R.old_nx = g.nx; R.old_ny = g.ny; R.off_x = off_x; R.off_y = off_y;
+        R.ret_off = nret; R.mis_off = nmis;
+        if (R.A.n_ret > 0) std::memcpy(ret + 2 * (size_t)nret, s.returns_xy, sizeof(float) * 2 * (size_t)R.A.n_ret);   // forward, straight into the segment
+        if (R.A.n_miss > 0) std::memcpy(mis + 2 * (size_t)nmis, s.misses_xy, sizeof(float) * 2 * (size_t)R.A.n_miss);
+        nret += R.A.n_ret; nmis += R.A.n_miss;
+        g.nx = nx; g.ny = ny; g.max_x = max_x; g.max_y = max_y;                    // what later submits' records are filled from
+        P.rec = nrec;
+        ++nrec;
+    }
+    b->sub_count = count;
+    if (nrec == 0) {
+        b->outstanding = true; b->kind = KIND_INSERT;
+        b->prepare_seconds = seconds_since(t_begin);
+        return RGRID_OK;
+    }
+    ++b->n_submit;
+    std::memcpy(b->h_seg[k], recs, sizeof(InsertRec) * (size_t)nrec);
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
+    b->prepare_seconds = seconds_since(t_begin);
+    InsertBufs If;
+    If.seg = b->dv_seg[k]; If.f2_off = (int)b->f2_off; If.raw_off = (int)b->raw_off;
+    If.cells = b->d_cells; If.hit = b->d_hit; If.miss = b->d_miss; If.bad = b->dv_bad; If.free_space = opt->insert_free_space ? 1 : 0;
+    hipLaunchKernelGGL(kgb_insert, dim3((unsigned)nrec), dim3(KGI_THREADS), 0, b->stream, If);
+    G_TRY(b, hipGetLastError());
+    b->outstanding = true; b->kind = KIND_INSERT;
+    return RGRID_OK;
+}
+
+int rgrid_batch_insert_collect(rgrid_batch_t *b, int *status)
+{
+    if (!b || !b->outstanding || b->kind != KIND_INSERT) return RGRID_ERR_INVALID;
+    const int count = b->sub_count;
+    if (count > 0 && !status) return RGRID_ERR_INVALID;
+    b->outstanding = false;
+    G_TRY(b, hipSetDevice(b->device));
+    G_TRY(b, hipStreamSynchronize(b->stream));
+    for (int j = 0; j < count; ++j) {
+        const Pending &P = b->sub[(size_t)j];
+        status[j] = (P.status == RGRID_OK && b->h_bad[P.rec]) ? RGRID_ERR_CAPACITY : P.status;   // an end point outside the grid after growth
     }
     return RGRID_OK;
 }

@@ -7,6 +7,7 @@
 // discretisation's index formula and the first-maximum comparison are written out inside kg_discretize / kg_score / kg_best --
 // calling them through the two functions below changed kg_score's instruction schedule -- and cell_index_of / best_before restate
 // them for rgrid_batch.hip.  tests/test_fleet_match_gpu.py holds the two matchers together bit for bit.
+// The two range-data inserters (rgrid_insert / rgrid_grow_as_needed and kgb_insert) share the text at the end of this file.
 #pragma once
 #include "../../include/rgrid.h"
 
@@ -145,6 +146,108 @@ void decode_best(const MatchPlan &plan, const double initial_pose[3], const Best
     *score = (double)best.score;
     if (best3) { best3[0] = sxy[0]; best3[1] = sxy[1]; best3[2] = sxy[2]; }
     if (info3) { info3[0] = plan.num_scans; info3[1] = plan.num_linear; info3[2] = (int)plan.ncand; }
+}
+
+// ---- range-data inserter: what rgrid_insert / rgrid_grow_as_needed (rgrid.hip) and rgrid_batch_insert_submit (rgrid_batch.hip)
+// share.  Host side, ONE text: the lookup tables and GrowAsNeeded's decision.  Device side: the record of one insertion, the table
+// application and the superscaled cell index (kg_ends, kg_hits, kg_rays and kgb_insert call the same three texts; the ray walk is
+// kg_rays' own and restated in kgb_insert).
+//
+// ApplyLookupTable (probability_grid.cc:38-53): a cell without the update marker takes table[cell] (which carries the
+// marker).  Concurrent lanes may race on one cell, but within a phase (hits, then misses: separate launches, or one workgroup's
+// barrier between them) every writer stores the SAME value table[original], and a reader sees either the original or the marked
+// value: the plain 16-bit load/store pair gives the reference's result without atomics.
+struct InsertArgs {
+    int nx, ny, n_ret, n_miss;
+    double max_x, max_y, rs;           // rs = resolution / 1000 (superscaled limits, :48-53)
+    float ox, oy;
+};
+constexpr int SUBPX = 1000;
+constexpr unsigned MARKER = 32768u;
+
+__device__ static inline void apply_table(unsigned short *cells, int nx, int cx, int cy, const unsigned short *__restrict__ table)
+{
+    unsigned short *c = cells + (size_t)nx * cy + cx;
+    const unsigned short v = *c;
+    if (v < MARKER) *c = table[v];
+}
+__device__ static inline bool super_index(const InsertArgs &A, float px, float py, int &ix, int &iy)
+{
+    // superscaled MapLimits::GetCellIndex (map_limits.h:47-55): x index from y, y index from x
+    ix = (int)lround((A.max_y - (double)py) / A.rs - 0.5);
+    iy = (int)lround((A.max_x - (double)px) / A.rs - 0.5);
+    return ix >= 0 && iy >= 0 && (long long)ix < (long long)A.nx * SUBPX && (long long)iy < (long long)A.ny * SUBPX;
+}
+
+// ComputeLookupTableToApplyCorrespondenceCostOdds(Odds(probability)) (probability_values.cc:76-96), host float32
+void lookup_table(float probability, unsigned short *table)
+{
+#pragma clang fp contract(off)
+    const float kMinProbability = 0.1f, kMaxProbability = 1.f - kMinProbability;
+    const float lower = 1.f - kMaxProbability, upper = 1.f - kMinProbability;
+    auto cost_to_value = [&](float c) -> unsigned short {                        // BoundedFloatToValue (probability_values.h:15-29)
+        float cl = c;
+        if (cl > upper) cl = upper;
+        if (cl < lower) cl = lower;
+        return (unsigned short)((int)std::lround((cl - lower) * (32766.f / (upper - lower))) + 1);
+    };
+    const float odds = probability / (1.f - probability);
+    {
+        const float p = odds / (odds + 1.f);
+        table[0] = (unsigned short)(cost_to_value(1.f - p) + MARKER);
+    }
+    const float kScale = (upper - lower) / (32768 - 2.f);
+    for (int cell = 1; cell != 32768; ++cell) {
+        const float cost = cell * kScale + (lower - kScale);                     // kValueToCorrespondenceCost[cell]
+        const float pc = 1.f - cost;
+        const float o = odds * (pc / (1.f - pc));
+        const float p = o / (o + 1.f);
+        table[cell] = (unsigned short)(cost_to_value(1.f - p) + MARKER);
+    }
+}
+
+// Grid2D::GrowLimits(point) on the limits only (grid_2d.cc:64-75,93); false if the grown grid exceeds `max_cells`
+bool grow_limits_for(float px, float py, double res, long long max_cells, int &nx, int &ny, double &max_x, double &max_y, int &off_x, int &off_y)
+{
+#pragma clang fp contract(off)
+    for (;;) {
+        const long ix = std::lround((max_y - (double)py) / res - 0.5), iy = std::lround((max_x - (double)px) / res - 0.5);
+        if (ix >= 0 && iy >= 0 && ix < nx && iy < ny) return true;
+        if (4ll * nx * ny > max_cells) return false;
+        const int xo = nx / 2, yo = ny / 2;
+        max_x = max_x + res * (double)yo;
+        max_y = max_y + res * (double)xo;
+        nx *= 2; ny *= 2; off_x += xo; off_y += yo;
+    }
+}
+
+// The limits of a grid after GrowAsNeeded (probability_grid_range_data_inserter_2d.cc:20-38): nx, ny, max_x, max_y go in as the
+// grid has them and come out grown, (off_x, off_y) is where the old cell (0, 0) lies in the grown grid -- several doublings are one
+// move.  RGRID_ERR_INVALID for a non-finite coordinate (the reference would loop forever), RGRID_ERR_CAPACITY when the grown grid
+// would exceed max_cells; the limits are untouched then.
+int plan_growth(const float origin_xy[2], const float *returns_xy, int n_returns, const float *misses_xy, int n_misses, double res,
+                long long max_cells, int &nx, int &ny, double &max_x, double &max_y, int &off_x, int &off_y)
+{
+    // Eigen::AlignedBox2f(origin).extend(every return and miss)  (:23-33)
+    float lo[2] = {origin_xy[0], origin_xy[1]}, hi[2] = {origin_xy[0], origin_xy[1]};
+    auto extend = [&](const float *p, int n) {
+        for (int i = 0; i < 2 * n; ++i) {
+            const float v = p[i];
+            if (!std::isfinite(v)) return false;
+            if (v < lo[i & 1]) lo[i & 1] = v;
+            if (v > hi[i & 1]) hi[i & 1] = v;
+        }
+        return true;
+    };
+    if (!std::isfinite(lo[0]) || !std::isfinite(lo[1]) || !extend(returns_xy, n_returns) || !extend(misses_xy, n_misses)) return RGRID_ERR_INVALID;
+    const float pad = 1e-6f;                                                        // kPadding (:25)
+    int gnx = nx, gny = ny, gox = 0, goy = 0;
+    double gmx = max_x, gmy = max_y;
+    if (!grow_limits_for(lo[0] - pad, lo[1] - pad, res, max_cells, gnx, gny, gmx, gmy, gox, goy) ||
+        !grow_limits_for(hi[0] + pad, hi[1] + pad, res, max_cells, gnx, gny, gmx, gmy, gox, goy))
+        return RGRID_ERR_CAPACITY;
+    nx = gnx; ny = gny; max_x = gmx; max_y = gmy; off_x = gox; off_y = goy;
+    return RGRID_OK;
 }
 
 }  // namespace

@@ -15,6 +15,11 @@ kgb_refine (one workgroup per scan), each result the bits of ``GridFrontEnd.Refi
 ``FleetScanMatchResult`` with ``.coarse`` (the match) and ``.fine`` (the refinement).  ``pose_fixes`` of those yields the refined
 poses: the fix the reference's node fuses.  A handle has one pending submit at a time, of any kind.
 
+The step after it, ``MapBuilder::InsertIntoSubmap`` (map_builder.cc:110-120), is ``insert(scans)``: ``(grid_slot, origin_xy,
+returns_xy, misses_xy_or_None)`` per scan, each into its OWN slot (a call names a slot once), ONE launch of kgb_insert (one
+workgroup per scan): the slot then holds the cells and limits ``GridFrontEnd.Insert`` (GrowAsNeeded + Insert) leaves, bit for bit,
+and the map never leaves the device between ticks.  ``GetGrid(slot)`` / ``GetLimits(slot)`` read a slot back.
+
 All arithmetic happens in the HIP kernel behind librgrid.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -25,8 +30,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .grid import (CeresScanMatcherOptions2D, MatchResult, RealTimeCorrelativeScanMatcherOptions, RefineResult, RgridError, _lib_rgrid,
-                   _MatchOptions, _RefineOptions, _RefineSummary)
+from .grid import (CeresScanMatcherOptions2D, MatchResult, RangeDataInserterOptions, RealTimeCorrelativeScanMatcherOptions, RefineResult,
+                   RgridError, _lib_rgrid, _MatchOptions, _RefineOptions, _RefineSummary)
 
 RGRID_OK, RGRID_ERR_INVALID, RGRID_ERR_CAPACITY, RGRID_ERR_EMPTY = 0, -1, -4, -6
 REDUCE_ARRIVAL, REDUCE_LAUNCH = 0, 1        # rgrid_batch_set_reduction
@@ -41,6 +46,17 @@ class RgridBatchRefineScan(C.Structure):
     """struct rgrid_batch_refine_scan (include/rgrid.h)."""
     _fields_ = [("grid", C.c_int), ("n", C.c_int), ("points_xy", C.c_void_p), ("target_translation", C.c_double * 2),
                 ("initial_pose", C.c_double * 3)]
+
+
+class RgridBatchInsertScan(C.Structure):
+    """struct rgrid_batch_insert_scan (include/rgrid.h)."""
+    _fields_ = [("grid", C.c_int), ("n_returns", C.c_int), ("n_misses", C.c_int), ("returns_xy", C.c_void_p), ("misses_xy", C.c_void_p),
+                ("origin_xy", C.c_float * 2)]
+
+
+class _InsertOptions(C.Structure):
+    """struct rgrid_insert_options (include/rgrid.h)."""
+    _fields_ = [("hit_probability", C.c_float), ("miss_probability", C.c_float), ("insert_free_space", C.c_int)]
 
 
 @dataclass
@@ -70,6 +86,7 @@ class FleetScanMatchResult:
 
 _ready = None
 _refine_ready = None
+_insert_ready = None
 
 
 def _batch_lib():
@@ -123,6 +140,36 @@ def _refine_lib():
     L.rgrid_batch_scan_match_collect.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     _refine_ready = L
     return L
+
+
+def _insert_lib():
+    """``_batch_lib()`` with the argtypes of the insert calls and the slot read-backs set.  Raises LibraryMissing when the built
+    library has no such calls or packs another structure (they are looked up by name); every other call keeps working then."""
+    global _insert_ready
+    if _insert_ready is not None:
+        return _insert_ready
+    L = _batch_lib()
+    names = ("rgrid_batch_insert_submit", "rgrid_batch_insert_collect", "rgrid_batch_get_limits", "rgrid_batch_get_grid",
+             "rgrid_batch_sizeof_insert_scan")
+    missing = [n for n in names if not hasattr(L, n)]
+    if missing:
+        raise _lib.LibraryMissing(f"librgrid.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
+    L.rgrid_batch_sizeof_insert_scan.restype = C.c_int
+    if L.rgrid_batch_sizeof_insert_scan() != C.sizeof(RgridBatchInsertScan):
+        raise _lib.LibraryMissing(f"librgrid.so: struct rgrid_batch_insert_scan has {L.rgrid_batch_sizeof_insert_scan()} bytes, this package "
+                                  f"packs {C.sizeof(RgridBatchInsertScan)}: rebuild it (python __graft_entry__.py)")
+    vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
+    L.rgrid_batch_insert_submit.argtypes = [vp, C.POINTER(_InsertOptions), vp, C.c_int]
+    L.rgrid_batch_insert_collect.argtypes = [vp, vp]
+    L.rgrid_batch_get_limits.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp]
+    L.rgrid_batch_get_grid.argtypes = [vp, C.c_int, vp, C.c_long]
+    _insert_ready = L
+    return L
+
+
+def _insert_options(o):
+    o = o or RangeDataInserterOptions()
+    return _InsertOptions(float(o.hit_probability), float(o.miss_probability), 1 if o.insert_free_space else 0)
 
 
 def _refine_options(o):
@@ -350,6 +397,88 @@ class ScanMatchFleet:
                    refine_options: CeresScanMatcherOptions2D | None = None):
         self.submit_scan_match(scans, match_options, refine_options)
         return self.collect_scan_match()
+
+    # -- MapBuilder::InsertIntoSubmap for a batch: grow and insert, each scan into its own slot ---
+    @staticmethod
+    def pack_insert(scans):
+        """scans: iterable of (grid_slot, origin_xy, returns_xy, misses_xy_or_None).  -> (ctypes array of rgrid_batch_insert_scan,
+        count, the arrays it points into)."""
+        scans = list(scans)
+        arr = (RgridBatchInsertScan * max(len(scans), 1))()
+        keep = []
+        for i, (slot, origin, returns, misses) in enumerate(scans):
+            ret = np.ascontiguousarray(returns, dtype=np.float32).reshape(-1, 2)
+            mis = np.zeros((0, 2), np.float32) if misses is None else np.ascontiguousarray(misses, dtype=np.float32).reshape(-1, 2)
+            keep += [ret, mis]
+            s = arr[i]
+            s.grid, s.n_returns, s.n_misses = int(slot), ret.shape[0], mis.shape[0]
+            s.returns_xy = ret.ctypes.data if s.n_returns else None
+            s.misses_xy = mis.ctypes.data if s.n_misses else None
+            s.origin_xy[0], s.origin_xy[1] = float(origin[0]), float(origin[1])
+        return arr, len(scans), keep
+
+    def submit_insert_packed_code(self, packed, options: RangeDataInserterOptions | None = None) -> int:
+        """``submit_insert_code`` for what ``pack_insert`` returned (reusable: the points are copied by the call)."""
+        co = _insert_options(options)
+        rc = _insert_lib().rgrid_batch_insert_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1])
+        if rc == 0:
+            self._pending = packed[1]
+        return rc
+
+    def submit_insert_code(self, scans, options: RangeDataInserterOptions | None = None) -> int:
+        return self.submit_insert_packed_code(self.pack_insert(scans), options)
+
+    def submit_insert(self, scans, options: RangeDataInserterOptions | None = None):
+        """One scan per entry, each into a slot of its own, the same options for all: ONE launch of kgb_insert; returns without waiting."""
+        self._chk(self.submit_insert_code(scans, options), "rgrid_batch_insert_submit")
+
+    def collect_insert_code(self):
+        """-> (rc, [status]) of the insert submit that has not been collected."""
+        count = self._pending or 0
+        status = np.zeros(max(count, 1), np.int32)
+        rc = _insert_lib().rgrid_batch_insert_collect(self._h, status.ctypes.data)
+        if rc != 0:
+            return rc, []
+        self._pending = None
+        return 0, [int(v) for v in status[:count]]
+
+    def collect_insert(self):
+        """Waits for the launch: one status per submitted scan, in order -- RGRID_OK, or the first code GrowAsNeeded + Insert give
+        for that scan (-1 a non-finite coordinate, -4 growth beyond max_cells / more points than max_points).  Raises only for what
+        concerns the whole call."""
+        rc, out = self.collect_insert_code()
+        self._chk(rc, "rgrid_batch_insert_collect")
+        return out
+
+    def insert(self, scans, options: RangeDataInserterOptions | None = None):
+        self.submit_insert(scans, options)
+        return self.collect_insert()
+
+    def GetLimits_code(self, slot: int):
+        nx, ny = C.c_int(), C.c_int()
+        res, mx, my = C.c_double(), C.c_double(), C.c_double()
+        rc = _insert_lib().rgrid_batch_get_limits(self._h, int(slot), C.byref(nx), C.byref(ny), C.byref(res), C.byref(mx), C.byref(my))
+        return rc, (nx.value, ny.value, res.value, mx.value, my.value)
+
+    def GetLimits(self, slot: int):
+        """MapLimits of slot ``slot`` as ``GridFrontEnd.GetLimits`` gives them: (num_x_cells, num_y_cells, resolution, max_x, max_y)."""
+        rc, lim = self.GetLimits_code(slot)
+        self._chk(rc, "rgrid_batch_get_limits")
+        return lim
+
+    def GetGrid_code(self, slot: int):
+        rc, lim = self.GetLimits_code(slot)
+        if rc != 0:
+            return rc, None
+        out = np.zeros((lim[1], lim[0]), np.uint16)
+        rc = _insert_lib().rgrid_batch_get_grid(self._h, int(slot), out.ctypes.data, out.size)
+        return rc, (out if rc == 0 else None)
+
+    def GetGrid(self, slot: int) -> np.ndarray:
+        """The cells of slot ``slot``: uint16 (num_y_cells, num_x_cells).  Not between a submit and its collect."""
+        rc, out = self.GetGrid_code(slot)
+        self._chk(rc, "rgrid_batch_get_grid")
+        return out
 
     def last_prepare_seconds(self) -> float:
         """Host time the last submit (of any kind) spent before its launch: initial rotations, search parameters, rotation tables, packing."""
