@@ -12,7 +12,9 @@ What differs:
 Written independently of oracle/ekf_oracle.c; shares nothing with the kernel.
 
 `mutate` (see MUTATIONS) plants one defect of the kind an indexing slip in k_fleet_step would cause; tests/test_fleet_edges_cpu.py
-uses it to show that the GPU bound can fail.
+uses it to show that the GPU bound can fail.  SINGLE_MUTATIONS are the slips of the single filter's launch forms (k_mid gathers
+from a covariance stored one scan behind and corrects what it gathers, the downdate works in 64-row tiles with border strips,
+wide scans run as block steps); tests/test_ekf_shapes_cpu.py uses those.
 """
 from __future__ import annotations
 
@@ -23,6 +25,10 @@ import numpy as np
 LD = np.longdouble
 DIFF, OMNI = 0, 1
 MUTATIONS = ("drop_last4", "skip_tile", "w_row_shift", "k_pad_col")
+# (stale_*: `where` = (i, j), the element that misses the previous scan's rank-m correction; skip_tile64: `where` = (I, J), 64-row
+# tiles; border_strip: the last row and column of the state; block_step_drop: the pairs behind the first 32 are not applied)
+SINGLE_MUTATIONS = ("stale_gather", "stale_own_row", "skip_tile64", "border_strip", "w_row_shift", "k_pad_col", "block_step_drop")
+STEP_PAIRS = 32                                                 # pairs per block step of a wide scan without a pose fix
 
 
 def available() -> bool:
@@ -102,6 +108,7 @@ class WitnessEKF:
         self.q = kit.T(float(obs_cov))
         self.last_match = ([], [])
         self.last_S = None
+        self.sigma_stale = None                                 # the covariance the last update started from (the stale_* defects)
 
     def set_state(self, t, mu, sigma, vt=(0.0, 0.0, 0.0)):
         self.time = float(t)
@@ -198,14 +205,26 @@ class WitnessEKF:
         pairs, new = self.match(obs)
         self.last_match = (pairs, new)
         if pairs:
-            H, dz = self._reflector_rows(obs, pairs)
+            upd = pairs[:STEP_PAIRS] if mutate == "block_step_drop" else pairs
+            H, dz = self._reflector_rows(obs, upd)
             m = H.shape[0]
             W = self.sigma @ H.T
             if mutate == "w_row_shift":
                 i, j = where
                 W[i, j] = (self.sigma @ H.T)[i + 1, j]
+            if mutate == "stale_own_row":                       # one element of P(own rows, R) without the pending correction
+                i, j = where
+                Pw = self.sigma.copy()
+                Pw[i, j] = self.sigma_stale[i, j]
+                W = Pw @ H.T
             S = H @ W + self.q * kit.eye(m)
+            if mutate == "stale_gather":                        # one element (and its mirror) of the gathered P(R, R)
+                i, j = where
+                Pg = self.sigma.copy()
+                Pg[i, j] = Pg[j, i] = self.sigma_stale[i, j]
+                S = H @ (Pg @ H.T) + self.q * kit.eye(m)
             self.last_S = S
+            self.sigma_stale = self.sigma
             Kt = W @ chol_inverse(S, kit)
             self.mu = self.mu + Kt @ dz
             self.mu[2] = self.kit.wrap(self.mu[2])
@@ -274,10 +293,14 @@ class WitnessEKF:
             assert m % 4 == 2
             return Kt @ W.T + np.outer(Kt[:, m - 1], W[:, m - 1])
         D = Kt @ W.T
-        if mutate == "skip_tile":
+        if mutate in ("skip_tile", "skip_tile64"):
             I, J = where
-            D[16 * I: 16 * I + 16, 16 * J: 16 * J + 16] = 0
-            D[16 * J: 16 * J + 16, 16 * I: 16 * I + 16] = 0     # the kernel holds the lower triangle only: the mirror goes with it
+            T = 16 if mutate == "skip_tile" else 64
+            D[T * I: T * I + T, T * J: T * J + T] = 0
+            D[T * J: T * J + T, T * I: T * I + T] = 0           # the kernel holds the lower triangle only: the mirror goes with it
+        if mutate == "border_strip":
+            D[-1, :] = 0
+            D[:, -1] = 0
         return D
 
     def state(self):
