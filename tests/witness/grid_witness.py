@@ -1,4 +1,4 @@
-"""tests/witness/grid_witness.py -- TEST INFRASTRUCTURE: second, independent statements of two grid-mapper pieces whose
+"""tests/witness/grid_witness.py -- TEST INFRASTRUCTURE: second, independent statements of three grid-mapper pieces whose
 only other restatement is oracle/grid_oracle.c (reference: src/mapping/probability_grid_range_data_inserter_2d.cc:40-114
 with ray_to_pixel_mask.cc:17-168, probability_values.cc; src/scan_matching/real_time_correlative_scan_matcher_2d.cc:20-136).
 
@@ -8,7 +8,12 @@ with ray_to_pixel_mask.cc:17-168, probability_values.cc; src/scan_matching/real_
     rebuilt with vectorised float32 numpy.
   * match_witness: every (rotation, x, y) candidate scored at once with array indexing, the float32 point-order sum as a
     cumulative sum; the oracle loops candidate by candidate.
-Neither pins parity with the reference (no tests there, Ceres/Eigen semantics restated): they pin the oracle against a
+  * refine_cost_witness: the objective of the Ceres refinement (ceres_scan_matcher_2d.cc:26-62 with
+    occupied_space_cost_function_2d.cc:25-81) at one pose, in longdouble, the bicubic interpolation as a tensor product of
+    Catmull-Rom weights over all points at once; the oracle and the kernel nest two Horner splines point by point.
+match_witness and refine_cost_witness take `mutant`: the grid convention transposed in one place (MUTANTS), for the tests that
+show which fixtures can tell the convention from its transpose (tests/grid_geometry_cases.py).
+None of them pins parity with the reference (no tests there, Ceres/Eigen semantics restated): they pin the oracle against a
 differently structured implementation.
 """
 from __future__ import annotations
@@ -142,13 +147,35 @@ def _rotate(pts, c, s):
     return np.stack([((c * x).astype(f32) - (s * y).astype(f32)).astype(f32), ((s * x).astype(f32) + (c * y).astype(f32)).astype(f32)], -1)
 
 
-def match_witness(initial_pose, points_xy, cells, resolution, max_xy, linear_search_window=0.2, angular_search_window=0.26,
-                  translation_delta_cost_weight=1e-1, rotation_delta_cost_weight=1e-1):
-    """RealTimeCorrelativeScanMatcher2D::Match.  -> (score float32, pose (3,), (scan, x_off, y_off))."""
-    pts = np.ascontiguousarray(points_xy, f32).reshape(-1, 2)
-    n = pts.shape[0]
+# ---- deliberately wrong geometry (tests/test_grid_geometry_cpu.py) ----------------------------------------------------------
+# The reference's convention -- x index from world y and max_y, row from world x and max_x, row stride num_x_cells -- transposed
+# in one place each.  On a square grid with equal maxima all three are the identity; the geometry cases exist to tell them apart.
+MUTANTS = ("bounds", "maxima", "stride")
+
+
+def _geometry(cells, max_xy, mutant):
+    """-> (flat cells, nx, ny, max_x, max_y, bound on x, bound on y, row stride) under `mutant` (None: the convention itself)."""
+    assert mutant is None or mutant in MUTANTS, mutant
     g = np.asarray(cells, np.int64)
     ny, nx = g.shape
+    mx, my = float(max_xy[0]), float(max_xy[1])
+    if mutant == "maxima":
+        mx, my = my, mx
+    bx, by = (ny, nx) if mutant == "bounds" else (nx, ny)
+    return g.reshape(-1), nx, ny, mx, my, bx, by, (ny if mutant == "stride" else nx)
+
+
+def _load(flat, nx, ny, stride, cx, cy):
+    """The cell at (x, y) clamped into the grid, rows `stride` apart (a wrong stride may run past the end: clamped too)."""
+    return flat[np.minimum(stride * np.clip(cy, 0, ny - 1) + np.clip(cx, 0, nx - 1), flat.size - 1)]
+
+
+def match_witness(initial_pose, points_xy, cells, resolution, max_xy, linear_search_window=0.2, angular_search_window=0.26,
+                  translation_delta_cost_weight=1e-1, rotation_delta_cost_weight=1e-1, mutant=None):
+    """RealTimeCorrelativeScanMatcher2D::Match.  -> (score float32, pose (3,), (scan, x_off, y_off)).  `mutant`: one of MUTANTS."""
+    pts = np.ascontiguousarray(points_xy, f32).reshape(-1, 2)
+    n = pts.shape[0]
+    flat, nx, ny, max_x, max_y, bound_x, bound_y, stride = _geometry(cells, max_xy, mutant)
     rot0 = _rotate(pts, *_rotation_cs(f32(initial_pose[2])))
     rng = np.sqrt(((rot0[:, 0] * rot0[:, 0]).astype(f32) + (rot0[:, 1] * rot0[:, 1]).astype(f32)).astype(f32)).astype(f32)
     max_range = max(f32(f32(3) * f32(resolution)), rng.max() if n else f32(0))
@@ -165,12 +192,12 @@ def match_witness(initial_pose, points_xy, cells, resolution, max_xy, linear_sea
         dth += step
         px, py = (rot[:, 0] + tx).astype(f32), (rot[:, 1] + ty).astype(f32)
         lround = lambda v: np.where(v >= 0, np.floor(v + 0.5), -np.floor(-v + 0.5)).astype(np.int64)
-        ix = lround((max_xy[1] - py.astype(np.float64)) / resolution - 0.5)
-        iy = lround((max_xy[0] - px.astype(np.float64)) / resolution - 0.5)
+        ix = lround((max_y - py.astype(np.float64)) / resolution - 0.5)
+        iy = lround((max_x - px.astype(np.float64)) / resolution - 0.5)
         cx = ix[None, None, :] + offs[:, None, None]            # [x_off, y_off, point]
         cy = iy[None, None, :] + offs[None, :, None]
-        inside = (cx >= 0) & (cy >= 0) & (cx < nx) & (cy < ny)
-        p = np.where(inside, prob[g[np.clip(cy, 0, ny - 1), np.clip(cx, 0, nx - 1)]], f32(0.1)).astype(f32)
+        inside = (cx >= 0) & (cy >= 0) & (cx < bound_x) & (cy < bound_y)
+        p = np.where(inside, prob[_load(flat, nx, ny, stride, cx, cy)], f32(0.1)).astype(f32)
         score = (np.add.accumulate(p, axis=2, dtype=f32)[:, :, -1] / f32(n)).astype(f32)     # float32 sum in point order
         orientation = (scan - na) * step
         x = -offs[None, :] * resolution + 0.0 * offs[:, None]
@@ -183,3 +210,51 @@ def match_witness(initial_pose, points_xy, cells, resolution, max_xy, linear_sea
             best = (score[xi, yi], (initial_pose[0] + x[xi, yi], initial_pose[1] + y[xi, yi], initial_pose[2] + orientation),
                     (scan, int(offs[xi]), int(offs[yi])))
     return best
+
+
+# ---- the refinement's objective ---------------------------------------------------------------------------------------------
+K_PADDING = 536870911          # kPadding = INT_MAX / 4 (occupied_space_cost_function_2d.cc:57)
+
+
+def _catmull_rom_weights(t):
+    """The four Catmull-Rom basis weights of the samples at -1, 0, 1, 2 for the offset t in [0, 1): ceres::CubicHermiteSpline
+    written as a weighted sum of its four samples.  t: longdouble (n,) -> (4, n)."""
+    t2 = t * t
+    t3 = t2 * t
+    return np.stack([(-t3 + 2 * t2 - t) / 2, (3 * t3 - 5 * t2 + 2) / 2, (-3 * t3 + 4 * t2 + t) / 2, (t3 - t2) / 2])
+
+
+def refine_cost_witness(pose, target_translation, initial_angle, points_xy, cells, resolution, max_xy, w_occ, w_t, w_r, mutant=None):
+    """The cost CeresScanMatcher2D::Match minimises (ceres_scan_matcher_2d.cc:26-62), at `pose`, as np.longdouble:
+
+      1/2 [ sum_i (w_occ / sqrt(n) bicubic_i)^2 + (w_t (x - tx))^2 + (w_t (y - ty))^2 + (w_r (theta - theta0))^2 ]
+
+    bicubic_i = ceres::BiCubicInterpolator over GridArrayAdapter::GetValue (occupied_space_cost_function_2d.cc:25-81) at the
+    point's padded (row, column).  The padded coordinate (max - w) / res - 0.5 + kPadding is formed in float64 as the reference
+    forms it: adding kPadding quantises the fractional offset to ~6e-8 cells, which is part of the operation.  Everything after
+    it is longdouble.  The interpolation is stated as the tensor product of the Catmull-Rom basis weights over the 4 x 4 taps,
+    all points at once -- not as the nested Horner splines of the oracle and of the kernel.  `mutant`: one of MUTANTS."""
+    LD = np.longdouble
+    pts = np.ascontiguousarray(points_xy, f32).reshape(-1, 2).astype(np.float64)
+    n = pts.shape[0]
+    flat, nx, ny, max_x, max_y, bound_x, bound_y, stride = _geometry(cells, max_xy, mutant)
+    x, y, th = (float(v) for v in pose)
+    c, s = math.cos(th), math.sin(th)
+    wx = c * pts[:, 0] - s * pts[:, 1] + x
+    wy = s * pts[:, 0] + c * pts[:, 1] + y
+    r = (max_x - wx) / resolution - 0.5 + float(K_PADDING)              # float64, rounding included
+    q = (max_y - wy) / resolution - 0.5 + float(K_PADDING)
+    rf, qf = np.floor(r), np.floor(q)
+    row, col = rf.astype(np.int64) - K_PADDING, qf.astype(np.int64) - K_PADDING
+    tap = np.arange(-1, 3)
+    cy = (row[None, :] + tap[:, None])[:, None, :]                      # [4, 1, n]
+    cx = (col[None, :] + tap[:, None])[None, :, :]                      # [1, 4, n]
+    inside = (cx >= 0) & (cy >= 0) & (cx < bound_x) & (cy < bound_y)
+    taps = np.where(inside, value_to_cost(_load(flat, nx, ny, stride, cx, cy)), f32(0.9)).astype(LD)     # [4, 4, n]
+    wr = _catmull_rom_weights(r.astype(LD) - rf.astype(LD))
+    wc = _catmull_rom_weights(q.astype(LD) - qf.astype(LD))
+    bicubic = (wr[:, None, :] * wc[None, :, :] * taps).sum(axis=(0, 1))
+    occ = LD(w_occ) / np.sqrt(LD(n)) * bicubic
+    d = np.array([LD(w_t) * (LD(x) - LD(float(target_translation[0]))), LD(w_t) * (LD(y) - LD(float(target_translation[1]))),
+                  LD(w_r) * (LD(th) - LD(float(initial_angle)))])
+    return LD(0.5) * ((occ * occ).sum() + (d * d).sum())
