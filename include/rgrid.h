@@ -295,9 +295,44 @@ int rgrid_batch_get_limits(rgrid_batch_t *b, int grid, int *num_x_cells, int *nu
                            double *max_y);
 int rgrid_batch_get_grid(rgrid_batch_t *b, int grid, uint16_t *cells, long cap);
 
+/* ---- fleet voxel filters: the filter stage of MapBuilder::AddRangeData (map_builder.cc:30-31,73) for one scan of many robots,
+ * ONE launch and ONE synchronisation per call (kgb_filter, one workgroup per scan, csrc/rgrid_batch.hip).  The specification is
+ * the single calls: for scan j, fr = rgrid_voxel_filter(returns, voxel_filter_size), fm = rgrid_voxel_filter(misses,
+ * voxel_filter_size) -- a filter of its own: the returns' voxels do not suppress misses -- and av = rgrid_adaptive_voxel_filter(fr,
+ * adaptive_max_length, adaptive_min_num_points, adaptive_max_range), each the same points in input order with the input's bit
+ * patterns.  The points are float32 xy, already in the gravity-aligned frame: nothing is rotated here.  The filter needs no grid:
+ * it works on a handle whose slots were never set.  Its staging is allocated by the handle's first filter submit.  Finite
+ * coordinates whose voxel index (int)lroundf(v / size) no int holds are outside the contract, as they are for rgrid_voxel_filter.
+ * The ABI version stays 4: a caller that may meet an older library looks for these symbols. */
+typedef struct rgrid_filter_options { float voxel_filter_size; double adaptive_max_length, adaptive_min_num_points, adaptive_max_range; } rgrid_filter_options;
+typedef struct rgrid_batch_filter_scan {   /* 24 bytes on LP64 */
+    int n_returns, n_misses;
+    const float *returns_xy, *misses_xy;   /* 2*n floats each, NULL when n == 0 */
+} rgrid_batch_filter_scan;
+
+/* Enqueues the filters of scans[0 .. count) and returns without waiting; the points are copied before the call returns.  Refused as
+ * a whole with RGRID_ERR_INVALID, nothing launched and the handle still usable: a null b, opt or scans, count outside
+ * [0, max_scans], a negative point count, a null pointer with a positive count, voxel_filter_size or adaptive_max_length not > 0
+ * (NaN included), a pending submit of any kind.  Per scan, in collect's status[j], the other scans unaffected, no workgroup and
+ * counts 0 for such a scan: RGRID_ERR_CAPACITY (n_returns or n_misses above min(max_points, rgrid_batch_filter_max_points())),
+ * RGRID_ERR_INVALID (a non-finite coordinate: the reference's lround of it is undefined).  A scan without returns is RGRID_OK with
+ * counts (0, |fm|, 0): whether AddRangeData would drop it is the caller's decision. */
+int rgrid_batch_filter_submit(rgrid_batch_t *b, const rgrid_filter_options *opt, const rgrid_batch_filter_scan *scans, int count);
+
+/* Waits once and hands out the pending filter submit's results in its order: status (count), counts (3 * count: |fr|, |fm|, |av| of
+ * every scan) and the clouds, consecutively in out_xy: scan 0's fr, fm, av, then scan 1's, ...; the offsets follow from counts.
+ * RGRID_ERR_BUFFER when out_cap_points is below the sum of counts: status and counts are filled and the submit is LEFT PENDING, the
+ * caller comes again with room; out_cap_points = sum of 2 * n_returns + n_misses always suffices.  RGRID_ERR_INVALID without a
+ * pending filter submit (a pending submit of another kind stays pending). */
+int rgrid_batch_filter_collect(rgrid_batch_t *b, int *status, int *counts, float *out_xy, long out_cap_points);
+
+/* Points per cloud one workgroup of kgb_filter holds (8192: 8 B of voxel keys and two 4 B table slots per point in LDS). */
+int rgrid_batch_filter_max_points(void);
+
 int rgrid_batch_sizeof_scan(void);
 int rgrid_batch_sizeof_refine_scan(void);
 int rgrid_batch_sizeof_insert_scan(void);
+int rgrid_batch_sizeof_filter_scan(void);
 const char *rgrid_batch_last_hip_error(rgrid_batch_t *b);
 
 const char *rgrid_strerror(int code);

@@ -452,6 +452,220 @@ __global__ __launch_bounds__(KGI_THREADS) void kgb_insert(InsertBufs B)
     if (tid == 0) B.bad[blockIdx.x] = 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The filter stage of MapBuilder::AddRangeData for a batch (map_builder.cc:30-31,73): ONE workgroup per scan computes
+// VoxelFilter(size).Filter(returns), VoxelFilter(size).Filter(misses) and AdaptiveVoxelFilter(options).Filter of the first,
+// the whole search over voxel sizes included (voxel_filter.cc:15-76), and writes the three clouds -- the points rgrid_voxel_filter
+// and rgrid_adaptive_voxel_filter return, input order and input bits.  DESIGN.md 10.5.
+//
+// First occurrence per voxel comes from an insert-only open-addressing hash table in LDS.  A slot holds a point index.  A point
+// walks its probe sequence to the first slot that is empty -- it claims it by compare-and-swap -- or whose holder has its own
+// voxel key -- it lowers the slot to its index (atomic min).  A claimed slot keeps its key for the rest of the pass (holders only
+// change within one voxel, nothing is freed), so every point of a voxel stops at the same slot, and after the barrier that slot
+// holds the voxel's smallest index: point i survives iff its slot holds i, whatever the hash and the order of the threads.
+// The table has at least two slots per point, so a probe always meets an empty slot.
+// A thread keeps its points (i = u * 1024 + tid, u < 8) and their slots in registers and a cloud's subset as a bit per point:
+// the range gate and every candidate size of the search are masks over the returns, nothing is compacted between passes.
+#define KGF_THREADS 1024
+#define KGF_WAVES (KGF_THREADS / 64)
+#define KGF_PER 8                         // points per thread
+#define KGF_MAX_POINTS (KGF_THREADS * KGF_PER)   // 8192: 8 B of keys + 2 slots of 4 B per point = 128 KB of gfx950's 160 KB
+#define KGF_EMPTY 0x7fffffff
+#define KGF_SCRATCH 256                   // bytes in front of the keys: three counters, two rows of wave sums
+
+// One runnable scan of a filter call; an array of these lies at the start of the filter's input staging.  Offsets count points.
+struct FilterRec {
+    int n_ret, n_mis;
+    int ret_off, mis_off;                 // its returns and misses in the input points
+    int out_off;                          // its three output clouds: fr at out_off (room n_ret), fm behind it (n_mis), av behind that (n_ret)
+    int pad;
+};
+
+struct FilterBufs {
+    const unsigned char *in;              // FilterRec[nrec] | float2 points at pts_off
+    int pts_off;
+    int key_cap;                          // points the launch's key area holds (the largest cloud, padded to 16)
+    float2 *out;                          // pinned host memory
+    int *counts;                          // [nrec][3]: |fr|, |fm|, |av|, pinned host memory
+    double min_pts;
+    float vsize, maxl, max_range;
+};
+
+// slots of a cloud's table: a power of two, at least two per point
+__host__ __device__ static inline int kgf_table_size(int n)
+{
+    int s = 64;
+    while (s < 2 * n) s <<= 1;
+    return s;
+}
+
+__device__ static inline unsigned kgf_hash(int kx, int ky)
+{
+    unsigned h = (unsigned)kx * 0x9E3779B1u + (unsigned)ky * 0x85EBCA77u;
+    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 13;
+    return h;
+}
+
+// Workgroup sum of the set bits of `mask`, read by every thread from LDS after the barrier.  Count k adds into counter k % 3;
+// behind its barrier thread 0 zeroes the counter of count k - 1 (everybody has read it: they are all past this barrier), which
+// count k + 2 adds into only behind the next count's barrier.
+__device__ __forceinline__ int kgf_count(int *s_cnt, int &turn, unsigned mask)
+{
+    int c = __popc(mask);
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[turn], c);
+    __syncthreads();
+    const int m = *(volatile int *)&s_cnt[turn];
+    if (threadIdx.x == 0) s_cnt[(turn + 2) % 3] = 0;
+    turn = (turn + 1) % 3;
+    return m;
+}
+
+// VoxelFilter(res).Filter of the points whose bit is set in `in` (all of them below n): -> the survivors' bits, m = their number
+__device__ __forceinline__ unsigned kgf_pass(const float (&px)[KGF_PER], const float (&py)[KGF_PER], unsigned in, float res, int n, int2 *key,
+                                             int *tab, int *s_cnt, int &turn, int &m)
+{
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    const int S = kgf_table_size(n), mask = S - 1;
+    int4 *t4 = reinterpret_cast<int4 *>(tab);
+    for (int q = tid; q < S / 4; q += KGF_THREADS) t4[q] = make_int4(KGF_EMPTY, KGF_EMPTY, KGF_EMPTY, KGF_EMPTY);
+    int kx[KGF_PER], ky[KGF_PER], slot[KGF_PER];
+#pragma unroll
+    for (int u = 0; u < KGF_PER; ++u) {
+        if (u * KGF_THREADS >= n) break;
+        if (in >> u & 1u) {
+            // GetCellIndex (voxel_filter.cc:105-110): RoundToInt(point / resolution), float division, lround
+            kx[u] = (int)lroundf(px[u] / res); ky[u] = (int)lroundf(py[u] / res);
+            key[u * KGF_THREADS + tid] = make_int2(kx[u], ky[u]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < KGF_PER; ++u) {
+        if (u * KGF_THREADS >= n) break;
+        if (in >> u & 1u) {
+            const int i = u * KGF_THREADS + tid;
+            int s = (int)(kgf_hash(kx[u], ky[u]) & (unsigned)mask);
+            for (;;) {
+                int cur = __hip_atomic_load(&tab[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (cur == KGF_EMPTY) {
+                    cur = atomicCAS(&tab[s], KGF_EMPTY, i);
+                    if (cur == KGF_EMPTY) break;                                   // claimed: unordered_set::insert(...).second (:89-93)
+                }
+                const int2 k = key[cur];                                           // somebody holds it: its voxel ...
+                if (k.x == kx[u] && k.y == ky[u]) {                                // ... is this point's: the smaller index stays
+                    if (i < cur) atomicMin(&tab[s], i);
+                    break;
+                }
+                s = (s + 1) & mask;
+            }
+            slot[u] = s;
+        }
+    }
+    __syncthreads();
+    unsigned keep = 0;
+#pragma unroll
+    for (int u = 0; u < KGF_PER; ++u) {
+        if (u * KGF_THREADS >= n) break;
+        if ((in >> u & 1u) && tab[slot[u]] == u * KGF_THREADS + tid) keep |= 1u << u;
+    }
+    m = kgf_count(s_cnt, turn, keep);                                              // its barrier: the table and the keys are free again
+    return keep;
+}
+
+// order-preserving ballot-scan compaction (kg_compact) of the points whose bit is set in `keep`, a tile of 1024 points per step
+__device__ __forceinline__ int kgf_emit(const float (&px)[KGF_PER], const float (&py)[KGF_PER], unsigned keep, int n, float2 *out, int *s_w)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    __syncthreads();                                                               // the wave sums of an earlier call have been read
+    int base = 0;
+#pragma unroll
+    for (int u = 0; u < KGF_PER; ++u) {
+        if (u * KGF_THREADS >= n) break;
+        const bool k = keep >> u & 1u;
+        const unsigned long long bal = __ballot(k);
+        int *row = s_w + (u & 1) * KGF_WAVES;                                      // two rows in turn: one barrier per tile
+        if (lane == 0) row[wave] = __popcll(bal);
+        __syncthreads();
+        int off = base, tot = 0;
+#pragma unroll
+        for (int w = 0; w < KGF_WAVES; ++w) { const int c = row[w]; if (w < wave) off += c; tot += c; }
+        if (k) out[off + __popcll(bal & lt)] = make_float2(px[u], py[u]);
+        base += tot;
+    }
+    return base;
+}
+
+__device__ __forceinline__ unsigned kgf_load(const float2 *__restrict__ src, int n, float (&px)[KGF_PER], float (&py)[KGF_PER])
+{
+    unsigned in = 0;
+#pragma unroll
+    for (int u = 0; u < KGF_PER; ++u) {
+        const int i = u * KGF_THREADS + (int)threadIdx.x;
+        px[u] = 0.f; py[u] = 0.f;
+        if (i < n) { const float2 p = src[i]; px[u] = p.x; py[u] = p.y; in |= 1u << u; }
+    }
+    return in;
+}
+
+__global__ __launch_bounds__(KGF_THREADS) void kgb_filter(FilterBufs B)
+{
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char kgf_lds[];
+    int *s_cnt = reinterpret_cast<int *>(kgf_lds);                                 // [3]
+    int *s_w = s_cnt + 4;                                                          // [2][KGF_WAVES]
+    int2 *key = reinterpret_cast<int2 *>(kgf_lds + KGF_SCRATCH);
+    int *tab = reinterpret_cast<int *>(kgf_lds + KGF_SCRATCH + sizeof(int2) * (size_t)B.key_cap);
+    const FilterRec R = reinterpret_cast<const FilterRec *>(B.in)[blockIdx.x];
+    const float2 *__restrict__ pin = reinterpret_cast<const float2 *>(B.in + B.pts_off);
+    float2 *out = B.out + R.out_off;
+    if (threadIdx.x == 0) { s_cnt[0] = 0; s_cnt[1] = 0; s_cnt[2] = 0; }            // (the first pass's first barrier publishes them)
+    int turn = 0;
+    float px[KGF_PER], py[KGF_PER];
+    // ---- VoxelFilter(voxel_filter_size).Filter(returns) (map_builder.cc:30)
+    const int nr = R.n_ret;
+    unsigned in = kgf_load(pin + R.ret_off, nr, px, py);
+    int m;
+    const unsigned fr = kgf_pass(px, py, in, B.vsize, nr, key, tab, s_cnt, turn, m);
+    const int n_fr = kgf_emit(px, py, fr, nr, out, s_w);
+    // ---- AdaptiveVoxelFilter(options).Filter(fr) (map_builder.cc:73): FilterByMaxRange (voxel_filter.cc:15-27) ...
+    unsigned gate = 0;
+#pragma unroll
+    for (int u = 0; u < KGF_PER; ++u)
+        if ((fr >> u & 1u) && sqrtf(px[u] * px[u] + py[u] * py[u]) <= B.max_range) gate |= 1u << u;
+    const int ni = kgf_count(s_cnt, turn, gate);
+    // ... and AdaptivelyVoxelFiltered (:29-76), one candidate size after the other; every decision from a count read from LDS
+    unsigned av = gate;
+    const double min_pts = B.min_pts;
+    if (!((double)ni <= min_pts)) {                                                // :33-37 already sparse enough
+        const float maxl = B.maxl;
+        av = kgf_pass(px, py, gate, maxl, nr, key, tab, s_cnt, turn, m);            // :38
+        if (!((double)m >= min_pts)) {                                             // :39-43
+            for (float high = maxl; high > 1e-2f * maxl; high /= 2.f) {            // :47-48
+                float low = high / 2.f;
+                av = kgf_pass(px, py, gate, low, nr, key, tab, s_cnt, turn, m);
+                if ((double)m >= min_pts) {
+                    while ((high - low) / low > 1e-1f) {                           // :57 bisection to 10 %
+                        const float mid = (low + high) / 2.f;
+                        const unsigned cand = kgf_pass(px, py, gate, mid, nr, key, tab, s_cnt, turn, m);
+                        if ((double)m >= min_pts) { low = mid; av = cand; } else high = mid;
+                    }
+                    break;
+                }
+            }                                                                      // nothing dense enough: the last size tried (:75)
+        }
+    }
+    const int n_av = kgf_emit(px, py, av, nr, out + nr + R.n_mis, s_w);
+    // ---- VoxelFilter(voxel_filter_size).Filter(misses) (map_builder.cc:31): a fresh filter, a fresh table
+    const int nm = R.n_mis;
+    in = kgf_load(pin + R.mis_off, nm, px, py);
+    const unsigned fm = kgf_pass(px, py, in, B.vsize, nm, key, tab, s_cnt, turn, m);
+    const int n_fm = kgf_emit(px, py, fm, nm, out + nr, s_w);
+    if (threadIdx.x == 0) { int *c = B.counts + 3 * blockIdx.x; c[0] = n_fr; c[1] = n_fm; c[2] = n_av; }
+}
+
 struct GridSlot {
     bool set = false;
     int nx = 0, ny = 0;
@@ -468,7 +682,10 @@ struct Pending {
 // what a packed match launches with
 struct MatchWork { int nrec, nwg, nf2, n_max; };
 
-enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3, KIND_INSERT = 4 };  // the pending submit
+enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3, KIND_INSERT = 4, KIND_FILTER = 5 };  // the pending submit
+
+// what collect needs of a scan of a filter submit
+struct FilterPending { int status, rec, out_off, n_ret, n_mis; };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -514,6 +731,15 @@ struct rgrid_batch {
     int *h_bad = nullptr, *dv_bad = nullptr;
     std::vector<unsigned long long> slot_call;   // the insert submit that named a slot last (a call names a slot once)
     unsigned long long n_insert = 0;
+    // the filter: its own staging, allocated by the first filter submit -- records and input points the kernel reads in place
+    // (host-visible device memory, else pinned host memory), output points and counts in pinned host memory
+    unsigned char *h_fin = nullptr;
+    const unsigned char *dv_fin = nullptr;
+    bool fin_in_vram = false;
+    size_t fpts_off = 0;
+    float2 *h_fout = nullptr, *dv_fout = nullptr;
+    int *h_fcnt = nullptr, *dv_fcnt = nullptr;
+    std::vector<FilterPending> fsub;
     std::vector<GridSlot> grids;
     bool outstanding = false;
     int kind = 0;                          // KIND_* of the outstanding submit
@@ -632,6 +858,52 @@ void refine_result(const rgrid_batch_t *b, const Pending &P, double *pose, rgrid
     if (summary) { summary->initial_cost = o.initial_cost; summary->final_cost = o.final_cost; summary->iterations = o.iterations; summary->termination = o.termination; }
 }
 
+// points per cloud of a filter submit: what the handle stages and what one workgroup of kgb_filter holds
+int filter_point_cap(const rgrid_batch_t *b) { return b->max_points < KGF_MAX_POINTS ? b->max_points : KGF_MAX_POINTS; }
+
+// the lround of a non-finite coordinate is undefined in the reference: such a scan is refused
+bool all_finite(const float *v, size_t n)
+{
+    unsigned bad = 0;
+    for (size_t i = 0; i < n; ++i) {
+        unsigned u;
+        std::memcpy(&u, v + i, sizeof(u));
+        bad |= (unsigned)((u & 0x7f800000u) == 0x7f800000u);
+    }
+    return !bad;
+}
+
+// the filter's staging: records and input points for max_scans scans of two clouds, three output clouds per scan, three counts
+int filter_staging(rgrid_batch_t *b)
+{
+    const size_t nS = (size_t)b->max_scans, nP = (size_t)filter_point_cap(b);
+    b->fpts_off = align_up(sizeof(FilterRec) * nS, 256);
+    const size_t in_bytes = b->fpts_off + sizeof(float2) * 2 * nS * nP, out_points = 3 * nS * nP;
+    if (out_points > 0x7fffffffu) return RGRID_ERR_CAPACITY;                       // a record's offsets are ints
+    if (b->pack.size() < sizeof(FilterRec) * nS) b->pack.resize(sizeof(FilterRec) * nS);
+    b->fsub.resize(nS);
+    void *dv = nullptr;
+    if (!b->h_fin) {
+        b->h_fin = (unsigned char *)host_visible::alloc(in_bytes);
+        if (b->h_fin) { b->fin_in_vram = true; b->dv_fin = b->h_fin; }
+        else {
+            G_TRY(b, hipHostMalloc((void **)&b->h_fin, in_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+            G_TRY(b, hipHostGetDevicePointer(&dv, b->h_fin, 0)); b->dv_fin = (const unsigned char *)dv;
+        }
+    }
+    if (!b->h_fout) {
+        G_TRY(b, hipHostMalloc((void **)&b->h_fout, sizeof(float2) * out_points, hipHostMallocMapped | hipHostMallocCoherent));
+        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_fout, 0)); b->dv_fout = (float2 *)dv;
+    }
+    // the keys and the table of an 8192-point cloud: 128 KB of LDS, above the 64 KB a launch gets unasked
+    G_TRY(b, hipFuncSetAttribute((const void *)kgb_filter, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)(KGF_SCRATCH + sizeof(int2) * (KGF_MAX_POINTS + 16) + sizeof(int) * (size_t)kgf_table_size(KGF_MAX_POINTS))));
+    if (!b->h_fcnt) G_TRY(b, hipHostMalloc((void **)&b->h_fcnt, sizeof(int) * 3 * nS, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(b->h_fcnt, 0, sizeof(int) * 3 * nS);
+    G_TRY(b, hipHostGetDevicePointer(&dv, b->h_fcnt, 0)); b->dv_fcnt = (int *)dv;   // last: it marks the staging as complete
+    return RGRID_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -719,6 +991,9 @@ void rgrid_batch_destroy(rgrid_batch_t *b)
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->h_rout) (void)hipHostFree(b->h_rout);
     if (b->h_bad) (void)hipHostFree(b->h_bad);
+    if (b->h_fin) { if (b->fin_in_vram) (void)hipFree(b->h_fin); else (void)hipHostFree(b->h_fin); }
+    if (b->h_fout) (void)hipHostFree(b->h_fout);
+    if (b->h_fcnt) (void)hipHostFree(b->h_fcnt);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -1042,6 +1317,95 @@ int rgrid_batch_insert_collect(rgrid_batch_t *b, int *status)
     for (int j = 0; j < count; ++j) {
         const Pending &P = b->sub[(size_t)j];
         status[j] = (P.status == RGRID_OK && b->h_bad[P.rec]) ? RGRID_ERR_CAPACITY : P.status;   // an end point outside the grid after growth
+    }
+    return RGRID_OK;
+}
+
+int rgrid_batch_filter_max_points(void) { return KGF_MAX_POINTS; }
+
+int rgrid_batch_sizeof_filter_scan(void) { return (int)sizeof(rgrid_batch_filter_scan); }
+
+int rgrid_batch_filter_submit(rgrid_batch_t *b, const rgrid_filter_options *opt, const rgrid_batch_filter_scan *scans, int count)
+{
+    if (!b || !opt || !scans || count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
+    if (!(opt->voxel_filter_size > 0.f) || !(opt->adaptive_max_length > 0.)) return RGRID_ERR_INVALID;
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_filter_scan &s = scans[j];
+        if (s.n_returns < 0 || s.n_misses < 0 || (s.n_returns > 0 && !s.returns_xy) || (s.n_misses > 0 && !s.misses_xy)) return RGRID_ERR_INVALID;
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    G_TRY(b, hipSetDevice(b->device));
+    const int cap = filter_point_cap(b);
+    if (!b->dv_fcnt) {                                                             // the first filter submit of this handle
+        const int rc = filter_staging(b);
+        if (rc != RGRID_OK) return rc;
+    }
+    FilterRec *recs = reinterpret_cast<FilterRec *>(b->pack.data());               // (the image of a match's records: free between submits)
+    float *pts = reinterpret_cast<float *>(b->h_fin + b->fpts_off);
+    int nrec = 0, nin = 0, nout = 0, n_max = 0;
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_filter_scan &s = scans[j];
+        FilterPending &P = b->fsub[(size_t)j];
+        P.status = RGRID_OK; P.rec = -1; P.out_off = 0; P.n_ret = s.n_returns; P.n_mis = s.n_misses;
+        if (s.n_returns > cap || s.n_misses > cap) { P.status = RGRID_ERR_CAPACITY; continue; }
+        if (!all_finite(s.returns_xy, 2 * (size_t)s.n_returns) || !all_finite(s.misses_xy, 2 * (size_t)s.n_misses)) { P.status = RGRID_ERR_INVALID; continue; }
+        FilterRec &R = recs[nrec];
+        R.n_ret = s.n_returns; R.n_mis = s.n_misses; R.ret_off = nin; R.mis_off = nin + s.n_returns; R.out_off = nout; R.pad = 0;
+        if (s.n_returns > 0) std::memcpy(pts + 2 * (size_t)R.ret_off, s.returns_xy, sizeof(float) * 2 * (size_t)s.n_returns);   // forward, straight into the staging
+        if (s.n_misses > 0) std::memcpy(pts + 2 * (size_t)R.mis_off, s.misses_xy, sizeof(float) * 2 * (size_t)s.n_misses);
+        nin += s.n_returns + s.n_misses;
+        nout += 2 * s.n_returns + s.n_misses;
+        if (s.n_returns > n_max) n_max = s.n_returns;
+        if (s.n_misses > n_max) n_max = s.n_misses;
+        P.rec = nrec; P.out_off = R.out_off;
+        ++nrec;
+    }
+    b->sub_count = count;
+    if (nrec == 0) {
+        b->outstanding = true; b->kind = KIND_FILTER;
+        b->prepare_seconds = seconds_since(t_begin);
+        return RGRID_OK;
+    }
+    std::memcpy(b->h_fin, recs, sizeof(FilterRec) * (size_t)nrec);
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
+    b->prepare_seconds = seconds_since(t_begin);
+    FilterBufs Ff;
+    Ff.in = b->dv_fin; Ff.pts_off = (int)b->fpts_off; Ff.key_cap = (n_max + 15) / 16 * 16 + 16;
+    Ff.out = b->dv_fout; Ff.counts = b->dv_fcnt;
+    Ff.min_pts = opt->adaptive_min_num_points;
+    Ff.vsize = opt->voxel_filter_size; Ff.maxl = (float)opt->adaptive_max_length; Ff.max_range = (float)opt->adaptive_max_range;
+    const size_t lds = KGF_SCRATCH + sizeof(int2) * (size_t)Ff.key_cap + sizeof(int) * (size_t)kgf_table_size(n_max);
+    hipLaunchKernelGGL(kgb_filter, dim3((unsigned)nrec), dim3(KGF_THREADS), lds, b->stream, Ff);
+    G_TRY(b, hipGetLastError());
+    b->outstanding = true; b->kind = KIND_FILTER;
+    return RGRID_OK;
+}
+
+int rgrid_batch_filter_collect(rgrid_batch_t *b, int *status, int *counts, float *out_xy, long out_cap_points)
+{
+    if (!b || !b->outstanding || b->kind != KIND_FILTER) return RGRID_ERR_INVALID;
+    const int count = b->sub_count;
+    if ((count > 0 && (!status || !counts)) || out_cap_points < 0) return RGRID_ERR_INVALID;
+    G_TRY(b, hipSetDevice(b->device));
+    G_TRY(b, hipStreamSynchronize(b->stream));
+    long total = 0;
+    for (int j = 0; j < count; ++j) {
+        const FilterPending &P = b->fsub[(size_t)j];
+        status[j] = P.status;
+        for (int c = 0; c < 3; ++c) total += counts[3 * j + c] = P.rec >= 0 ? b->h_fcnt[3 * P.rec + c] : 0;
+    }
+    if (total > out_cap_points || (total > 0 && !out_xy)) return RGRID_ERR_BUFFER;         // the submit stays pending: come again with room
+    b->outstanding = false;
+    float *dst = out_xy;
+    for (int j = 0; j < count; ++j) {
+        const FilterPending &P = b->fsub[(size_t)j];
+        if (P.rec < 0) continue;
+        const int off[3] = {P.out_off, P.out_off + P.n_ret, P.out_off + P.n_ret + P.n_mis};   // fr, fm, av as the kernel laid them out
+        for (int c = 0; c < 3; ++c) {
+            const size_t k = (size_t)counts[3 * j + c];
+            if (k > 0) std::memcpy(dst, b->h_fout + off[c], sizeof(float2) * k);
+            dst += 2 * k;
+        }
     }
     return RGRID_OK;
 }

@@ -20,20 +20,28 @@ returns_xy, misses_xy_or_None)`` per scan, each into its OWN slot (a call names 
 workgroup per scan): the slot then holds the cells and limits ``GridFrontEnd.Insert`` (GrowAsNeeded + Insert) leaves, bit for bit,
 and the map never leaves the device between ticks.  ``GetGrid(slot)`` / ``GetLimits(slot)`` read a slot back.
 
+The stage in front of all that, the filters of ``MapBuilder::AddRangeData`` (map_builder.cc:30-31,73), is ``filter(scans)``:
+``(returns_xy, misses_xy_or_None)`` per scan, already gravity-aligned (``gravity_aligned_scans`` turns raw range data and EKF poses
+into such scans), ONE launch of kgb_filter (one workgroup per scan) and one wait: per scan a ``FleetFilterResult`` with the two
+voxel-filtered clouds and the adaptively filtered returns, the bits of ``GridFrontEnd.VoxelFilter`` (twice) and
+``GridFrontEnd.AdaptiveVoxelFilter``.  It needs no grid.
+
 All arithmetic happens in the HIP kernel behind librgrid.so; there is no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
-from .grid import (CeresScanMatcherOptions2D, MatchResult, RangeDataInserterOptions, RealTimeCorrelativeScanMatcherOptions, RefineResult,
+from .grid import (AdaptiveVoxelFilterOptions, CeresScanMatcherOptions2D, MatchResult, RangeDataInserterOptions, RealTimeCorrelativeScanMatcherOptions, RefineResult,
                    RgridError, _lib_rgrid, _MatchOptions, _RefineOptions, _RefineSummary)
 
 RGRID_OK, RGRID_ERR_INVALID, RGRID_ERR_CAPACITY, RGRID_ERR_EMPTY = 0, -1, -4, -6
+RGRID_ERR_BUFFER = -5
 REDUCE_ARRIVAL, REDUCE_LAUNCH = 0, 1        # rgrid_batch_set_reduction
 
 
@@ -57,6 +65,27 @@ class RgridBatchInsertScan(C.Structure):
 class _InsertOptions(C.Structure):
     """struct rgrid_insert_options (include/rgrid.h)."""
     _fields_ = [("hit_probability", C.c_float), ("miss_probability", C.c_float), ("insert_free_space", C.c_int)]
+
+
+class RgridBatchFilterScan(C.Structure):
+    """struct rgrid_batch_filter_scan (include/rgrid.h)."""
+    _fields_ = [("n_returns", C.c_int), ("n_misses", C.c_int), ("returns_xy", C.c_void_p), ("misses_xy", C.c_void_p)]
+
+
+class _FilterOptions(C.Structure):
+    """struct rgrid_filter_options (include/rgrid.h)."""
+    _fields_ = [("voxel_filter_size", C.c_float), ("adaptive_max_length", C.c_double), ("adaptive_min_num_points", C.c_double),
+                ("adaptive_max_range", C.c_double)]
+
+
+@dataclass
+class FleetFilterResult:
+    """The filter stage of MapBuilder::AddRangeData for one scan: ``returns`` = VoxelFilter(size).Filter(returns), ``misses`` =
+    VoxelFilter(size).Filter(misses), ``filtered`` = AdaptiveVoxelFilter(options).Filter(``returns``); (k, 2) float32 each."""
+    status: int                      # RGRID_OK, -4 more points than the handle or one workgroup holds, -1 a non-finite coordinate (clouds empty then)
+    returns: np.ndarray
+    misses: np.ndarray
+    filtered: np.ndarray
 
 
 @dataclass
@@ -87,6 +116,7 @@ class FleetScanMatchResult:
 _ready = None
 _refine_ready = None
 _insert_ready = None
+_filter_ready = None
 
 
 def _batch_lib():
@@ -165,6 +195,54 @@ def _insert_lib():
     L.rgrid_batch_get_grid.argtypes = [vp, C.c_int, vp, C.c_long]
     _insert_ready = L
     return L
+
+
+def _filter_lib():
+    """``_batch_lib()`` with the argtypes of the filter calls set.  Raises LibraryMissing when the built library has no such calls or
+    packs another structure (they are looked up by name); every other call keeps working then."""
+    global _filter_ready
+    if _filter_ready is not None:
+        return _filter_ready
+    L = _batch_lib()
+    names = ("rgrid_batch_filter_submit", "rgrid_batch_filter_collect", "rgrid_batch_filter_max_points", "rgrid_batch_sizeof_filter_scan")
+    missing = [n for n in names if not hasattr(L, n)]
+    if missing:
+        raise _lib.LibraryMissing(f"librgrid.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
+    L.rgrid_batch_sizeof_filter_scan.restype = C.c_int
+    if L.rgrid_batch_sizeof_filter_scan() != C.sizeof(RgridBatchFilterScan):
+        raise _lib.LibraryMissing(f"librgrid.so: struct rgrid_batch_filter_scan has {L.rgrid_batch_sizeof_filter_scan()} bytes, this package "
+                                  f"packs {C.sizeof(RgridBatchFilterScan)}: rebuild it (python __graft_entry__.py)")
+    vp = C.c_void_p
+    L.rgrid_batch_filter_max_points.restype = C.c_int
+    L.rgrid_batch_filter_max_points.argtypes = []
+    L.rgrid_batch_filter_submit.argtypes = [vp, C.POINTER(_FilterOptions), vp, C.c_int]
+    L.rgrid_batch_filter_collect.argtypes = [vp, vp, vp, vp, C.c_long]
+    _filter_ready = L
+    return L
+
+
+def filter_max_points() -> int:
+    """Points per cloud one workgroup of kgb_filter holds (rgrid_batch_filter_max_points)."""
+    return int(_filter_lib().rgrid_batch_filter_max_points())
+
+
+def _filter_options(voxel_filter_size, o):
+    o = o or AdaptiveVoxelFilterOptions()
+    return _FilterOptions(float(voxel_filter_size), float(o.max_length), float(o.min_num_points), float(o.max_range))
+
+
+def gravity_aligned_scans(range_datas, ekf_poses):
+    """``(returns, misses)`` of every ``map_builder.RangeData`` rotated into the gravity-aligned frame of its EKF pose ``(x, y, yaw)``,
+    as MapBuilder::AddRangeData does before it filters (map_builder.cc:20-28, with map_builder.py's own arithmetic): the scans
+    ``ScanMatchFleet.filter`` takes.  The kernel does not rotate."""
+    from .map_builder import rigid2f_apply, yaw_of_quaternion_f32
+    scans = []
+    for rd, pose in zip(range_datas, ekf_poses):
+        theta = float(pose[2])
+        yaw = yaw_of_quaternion_f32(math.cos(theta / 2), math.sin(theta / 2))
+        misses = np.zeros((0, 2), np.float32) if rd.misses is None else rd.misses
+        scans.append((rigid2f_apply((0.0, 0.0), yaw, rd.returns), rigid2f_apply((0.0, 0.0), yaw, misses)))
+    return scans
 
 
 def _insert_options(o):
@@ -453,6 +531,73 @@ class ScanMatchFleet:
     def insert(self, scans, options: RangeDataInserterOptions | None = None):
         self.submit_insert(scans, options)
         return self.collect_insert()
+
+    # -- the filter stage of MapBuilder::AddRangeData for a batch: two voxel filters and the adaptive filter per scan ---
+    @staticmethod
+    def pack_filter(scans):
+        """scans: iterable of (returns_xy, misses_xy_or_None).  -> (ctypes array of rgrid_batch_filter_scan, count, the arrays it
+        points into)."""
+        scans = list(scans)
+        arr = (RgridBatchFilterScan * max(len(scans), 1))()
+        keep = []
+        for i, (returns, misses) in enumerate(scans):
+            ret = np.ascontiguousarray(returns, dtype=np.float32).reshape(-1, 2)
+            mis = np.zeros((0, 2), np.float32) if misses is None else np.ascontiguousarray(misses, dtype=np.float32).reshape(-1, 2)
+            keep += [ret, mis]
+            s = arr[i]
+            s.n_returns, s.n_misses = ret.shape[0], mis.shape[0]
+            s.returns_xy = ret.ctypes.data if s.n_returns else None
+            s.misses_xy = mis.ctypes.data if s.n_misses else None
+        return arr, len(scans), keep
+
+    def submit_filter_packed_code(self, packed, voxel_filter_size: float = 0.025, options: AdaptiveVoxelFilterOptions | None = None) -> int:
+        """``submit_filter_code`` for what ``pack_filter`` returned (reusable: the points are copied by the call)."""
+        co = _filter_options(voxel_filter_size, options)
+        rc = _filter_lib().rgrid_batch_filter_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1])
+        if rc == 0:
+            self._pending = packed[1]
+            self._filter_room = sum(2 * packed[0][i].n_returns + packed[0][i].n_misses for i in range(packed[1]))
+        return rc
+
+    def submit_filter_code(self, scans, voxel_filter_size: float = 0.025, options: AdaptiveVoxelFilterOptions | None = None) -> int:
+        return self.submit_filter_packed_code(self.pack_filter(scans), voxel_filter_size, options)
+
+    def submit_filter(self, scans, voxel_filter_size: float = 0.025, options: AdaptiveVoxelFilterOptions | None = None):
+        """One scan per entry, the same sizes and options for all: ONE launch of kgb_filter; returns without waiting."""
+        self._chk(self.submit_filter_code(scans, voxel_filter_size, options), "rgrid_batch_filter_submit")
+
+    def collect_filter_code(self, out_cap_points: int | None = None):
+        """-> (rc, [FleetFilterResult]) of the filter submit that has not been collected.  ``out_cap_points`` (default: what always
+        suffices) is the room offered for the clouds: when it is too small the answer is (RGRID_ERR_BUFFER, [(|fr|, |fm|, |av|) per
+        scan]) and the submit stays pending."""
+        count = self._pending or 0
+        n = max(count, 1)
+        room = int(getattr(self, "_filter_room", 0) if out_cap_points is None else out_cap_points)
+        status, counts, out = np.zeros(n, np.int32), np.zeros((n, 3), np.int32), np.zeros((max(room, 1), 2), np.float32)
+        rc = _filter_lib().rgrid_batch_filter_collect(self._h, status.ctypes.data, counts.ctypes.data, out.ctypes.data, room)
+        if rc == RGRID_ERR_BUFFER:
+            return rc, [tuple(int(v) for v in counts[i]) for i in range(count)]
+        if rc != 0:
+            return rc, []
+        self._pending = None
+        results, at = [], 0
+        for i in range(count):
+            clouds = []
+            for k in counts[i]:
+                clouds.append(out[at:at + k].copy())
+                at += int(k)
+            results.append(FleetFilterResult(int(status[i]), *clouds))
+        return 0, results
+
+    def collect_filter(self, out_cap_points: int | None = None):
+        """Waits for the launch: one FleetFilterResult per submitted scan, in order.  Raises only for what concerns the whole call."""
+        rc, out = self.collect_filter_code(out_cap_points)
+        self._chk(rc, "rgrid_batch_filter_collect")
+        return out
+
+    def filter(self, scans, voxel_filter_size: float = 0.025, options: AdaptiveVoxelFilterOptions | None = None):
+        self.submit_filter(scans, voxel_filter_size, options)
+        return self.collect_filter()
 
     def GetLimits_code(self, slot: int):
         nx, ny = C.c_int(), C.c_int()
