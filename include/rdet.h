@@ -152,6 +152,51 @@ int rdet3d_handle_cloud(rdet3d_t *h, double stamp, const float *xyzi, int N,
 int rdet3d_submit(rdet3d_t *h, double stamp, const float *xyzi, int N, int max_centers);
 int rdet3d_collect(rdet3d_t *h, float *centers_xy, int max_centers, int *K, double *obs_time);
 
+/* ---- the 3D detector for many robots: one launch per tick (csrc/det3d_batch.hip) ----------------
+ * Member m of a batch handle is one PointCloudReflectorDetect: options opts[m], sensor_to_base_link
+ * s2b_xyyaw[m] (HandlePointCloud reads no odometry).  One workgroup per cloud, no workgroup waits
+ * for another.  Results are bit for bit those of B rdet3d handles. */
+typedef struct rdet3d_batch rdet3d_batch_t;
+
+/* one cloud of one member: N points (x, y, z, intensity) */
+typedef struct rdet3d_cloud {
+    int member;                       /* 0 .. B-1 */
+    double stamp;
+    const float *xyzi;
+    int N;
+} rdet3d_cloud;
+
+/* B >= 1 members, clouds of at most max_points points.  Refused before any HIP call: null
+ * pointers, B < 1, max_points < 1. */
+int rdet3d_batch_create(const rdet3d_options *opts, const double *s2b_xyyaw, int B, int max_points,
+                        int device, rdet3d_batch_t **out);
+void rdet3d_batch_destroy(rdet3d_batch_t *b);
+int rdet3d_batch_set_sensor_to_base_link(rdet3d_batch_t *b, int member, const double xyyaw[3]);
+
+/* The member's slice of the device-visible staging area (4 * max_points floats).  A cloud whose
+ * xyzi pointer is this is read in place by the kernel.  It stays valid for the life of the handle;
+ * do not write it between submit and collect. */
+int rdet3d_batch_staging(rdet3d_batch_t *b, int member, float **xyzi);
+
+/* At most one cloud per member.  Everything is validated first: a null b, null clouds with
+ * count > 0, count < 0, a member out of range or named twice, N < 0, N > 0 with a null pointer, a
+ * submit that has not been collected (RDET_ERR_INVALID), N > max_points (RDET_ERR_CAPACITY) refuse
+ * the WHOLE call and change nothing.  Enqueues one launch and returns. */
+int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count);
+
+/* Waits for the launch; status / K / obs_time (= stamp) / n_bright (the survivors of the intensity
+ * gate) / centres of cloud i of the submit at index i (centres at centers_xy + 2 * max_centers * i).
+ * max_centers is capped at RDET_MAX_CENTERS.  Per-cloud statuses are data, the other clouds run:
+ * RDET_ERR_CAPACITY with K = 0 for more than rdet3d_batch_max_bright() survivors of the gate
+ * (n_bright holds the true count: send that cloud through an rdet3d_t) or more than 256 accepted
+ * clusters, RDET_ERR_BUFFER with K = 0 for more accepted clusters than max_centers.  centers_xy may
+ * be null when max_centers is 0; obs_time and n_bright may be null. */
+int rdet3d_batch_collect(rdet3d_batch_t *b, int *status, int *K, float *centers_xy, int max_centers,
+                         double *obs_time, int *n_bright);
+int rdet3d_batch_max_bright(void);    /* 5120 */
+int rdet3d_batch_sizeof_cloud(void);
+const char *rdet3d_batch_last_hip_error(rdet3d_batch_t *b);
+
 const char *rdet_strerror(int code);
 int rdet_abi_version(void);
 

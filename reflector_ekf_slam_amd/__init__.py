@@ -8,6 +8,6 @@ synthetic session generator (``synth``) and the session driver (``session``).
 from .ekf_slam import (DIFF, OMNI, EKFOptions, Map, Observation, OdometryData,  # noqa: F401
                        ReflectorEKFSLAM, ReflectorMatchResult, RekfError, State)
 from .fleet import ReflectorEKFSLAMFleet  # noqa: F401
-from .fleet_detect import LaserReflectorDetectFleet, scan_events  # noqa: F401
+from .fleet_detect import LaserReflectorDetectFleet, PointCloud, PointCloudReflectorDetectFleet, cloud_events, scan_events  # noqa: F401
 from .fleet_match import (FleetFilterResult, FleetRefineResult, FleetScanMatchResult, RgridBatchFilterScan,  # noqa: F401
                           RgridBatchInsertScan, ScanMatchFleet, gravity_aligned_scans, pose_fixes)

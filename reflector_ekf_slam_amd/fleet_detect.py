@@ -1,20 +1,26 @@
-"""Fleet detector: the 2D reflector detector for many robots, ONE kernel launch per tick (rdet2d_batch_* of include/rdet.h).
+"""Fleet detectors: the 2D and the 3D reflector detector for many robots, ONE kernel launch per tick (rdet2d_batch_* and
+rdet3d_batch_* of include/rdet.h).
 
 ``LaserReflectorDetectFleet(options_list)`` holds B members, each a reflector_detect::LaserReflectorDetect with its own options,
 sensor_to_base_link and odometry.  ``submit(scans)`` takes at most one ``LaserScan`` per member and enqueues one launch of
 k_det2d_batch (one workgroup per scan); ``collect()`` waits and returns ``(status, Observation)`` per scan, in the order given.
 ``scan_events`` turns a tick's result into the events ``ReflectorEKFSLAMFleet.submit`` takes.
 
-All arithmetic happens in the HIP kernel behind librdet.so; there is no CPU fallback.
+``PointCloudReflectorDetectFleet(options_list)`` is the same for reflector_detect::PointCloudReflectorDetect: ``submit(clouds)`` takes
+at most one cloud per member, ``(member, stamp, xyzi)`` or ``(member, PointCloud)``, and enqueues one launch of k_det3d_batch (one
+workgroup per cloud).  ``scan_events`` takes its ticks in the second form, ``cloud_events`` in the first.
+
+All arithmetic happens in the HIP kernels behind librdet.so; there is no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib, fleet
-from .detect import MAX_CENTERS, LaserScan, RangeData, Rdet2dOptions, RdetError, _as_f32, _rdet
+from .detect import MAX_CENTERS, LaserScan, RangeData, Rdet2dOptions, Rdet3dOptions, RdetError, _as_f32, _rdet
 from .ekf_slam import Observation, OdometryData
 
 MAX_BEAMS = 8192
@@ -28,7 +34,20 @@ class Rdet2dScan(C.Structure):
                 ("ranges", C.c_void_p), ("intensities", C.c_void_p), ("N", C.c_int)]
 
 
+class Rdet3dCloud(C.Structure):
+    """struct rdet3d_cloud (include/rdet.h)."""
+    _fields_ = [("member", C.c_int), ("stamp", C.c_double), ("xyzi", C.c_void_p), ("N", C.c_int)]
+
+
+@dataclass
+class PointCloud:
+    """What HandlePointCloud reads of a sensor_msgs::PointCloud2: the stamp and N points (x, y, z, intensity)."""
+    stamp: float
+    xyzi: np.ndarray
+
+
 _ready = None
+_ready3 = None
 
 
 def _batch_lib():
@@ -57,6 +76,42 @@ def _batch_lib():
     L.rdet2d_batch_get_range_data.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip]
     _ready = L
     return L
+
+
+def _batch3_lib():
+    """librdet.so with the rdet3d_batch_* argtypes set.  Raises LibraryMissing when it was not built, or was built without them."""
+    global _ready3
+    if _ready3 is not None:
+        return _ready3
+    L = _rdet()
+    if not hasattr(L, "rdet3d_batch_create") or not hasattr(L, "rdet3d_batch_sizeof_cloud"):
+        raise _lib.LibraryMissing("librdet.so has no rdet3d_batch_*: rebuild it (python __graft_entry__.py); there is no CPU fallback")
+    vp = C.c_void_p
+    L.rdet3d_batch_sizeof_cloud.restype = C.c_int
+    if L.rdet3d_batch_sizeof_cloud() != C.sizeof(Rdet3dCloud):
+        raise _lib.LibraryMissing(f"librdet.so: struct rdet3d_cloud has {L.rdet3d_batch_sizeof_cloud()} bytes, this package packs "
+                                  f"{C.sizeof(Rdet3dCloud)}: rebuild it (python __graft_entry__.py)")
+    L.rdet3d_batch_last_hip_error.restype = C.c_char_p
+    L.rdet3d_batch_last_hip_error.argtypes = [vp]
+    L.rdet3d_batch_max_bright.restype = C.c_int
+    L.rdet3d_batch_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.rdet3d_batch_destroy.argtypes = [vp]
+    L.rdet3d_batch_destroy.restype = None
+    L.rdet3d_batch_set_sensor_to_base_link.argtypes = [vp, C.c_int, vp]
+    L.rdet3d_batch_staging.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.rdet3d_batch_submit.argtypes = [vp, vp, C.c_int]
+    L.rdet3d_batch_collect.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
+    _ready3 = L
+    return L
+
+
+def cloud_events(clouds, observations):
+    """``scan_events`` for a 3D tick given as ``PointCloudReflectorDetectFleet.submit`` takes it in its first form
+    ([(member, stamp, xyzi), ...]): one ``fleet.scan_event`` per cloud with status 0, nothing truncated."""
+    clouds, observations = list(clouds), list(observations)
+    if len(clouds) != len(observations):
+        raise ValueError("one observation per cloud")
+    return [fleet.scan_event(c[0], obs.time_, obs.cloud_) for c, (status, obs) in zip(clouds, observations) if status == 0]
 
 
 def scan_events(scans, observations):
@@ -205,4 +260,133 @@ class LaserReflectorDetectFleet:
 
     def detect(self, scans, max_centers: int = MAX_CENTERS):
         self.submit(scans)
+        return self.collect(max_centers)
+
+
+class PointCloudReflectorDetectFleet:
+    """B reflector_detect::PointCloudReflectorDetect on one MI355X, one kernel launch per ``submit``."""
+
+    def __init__(self, options_list, max_points: int = 65536, device: int = 0, sensor_to_base_link=None):
+        self._L = _batch3_lib()
+        self._h = None
+        self.options_list = list(options_list)
+        B = len(self.options_list)
+        opts = (Rdet3dOptions * max(B, 1))()
+        for i, o in enumerate(self.options_list):
+            opts[i] = Rdet3dOptions(o.intensity_min)
+        if sensor_to_base_link is None:
+            s2b = np.zeros((B, 3))
+        else:
+            s2b = np.array(sensor_to_base_link, dtype=np.float64)
+            s2b = np.ascontiguousarray(np.broadcast_to(s2b, (B, 3))) if s2b.ndim == 1 else np.ascontiguousarray(s2b.reshape(B, 3))
+        h = C.c_void_p()
+        rc = self._L.rdet3d_batch_create(C.cast(opts, C.c_void_p), s2b.ctypes.data if B else None, B, int(max_points), int(device), C.byref(h))
+        if rc != 0:
+            raise RdetError(rc, "rdet3d_batch_create")
+        self._h = h
+        self.B = B
+        self.max_points = int(max_points)
+        self.sensor_to_base_link = s2b
+        self.last_n_bright = []       # the survivors of the intensity gate, per cloud of the last collect
+        self._pending = None          # the submit that has not been collected: (records, arrays they point into, count)
+        self._staging = {}
+
+    # -- lifetime -----------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.rdet3d_batch_destroy(self._h)
+            self._h = None
+            self._staging = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.B
+
+    def _chk(self, rc, where):
+        if rc != 0:
+            detail = self._L.rdet3d_batch_last_hip_error(self._h).decode() if rc == -2 else ""
+            raise RdetError(rc, where + (": " + detail if detail else ""))
+
+    @staticmethod
+    def max_bright() -> int:
+        """Survivors of the intensity gate a cloud may have (more: status -4, and the cloud goes through a PointCloudReflectorDetect)."""
+        return int(_batch3_lib().rdet3d_batch_max_bright())
+
+    # -- per member ---------------------------------------------------------
+    def SetSensorToBaseLinkTransform(self, member: int, xyyaw):
+        """Takes the transform already projected with ``detect.project2d`` (x, y, yaw)."""
+        v = np.ascontiguousarray(xyyaw, dtype=np.float64).reshape(3)
+        self._chk(self._L.rdet3d_batch_set_sensor_to_base_link(self._h, int(member), v.ctypes.data), "SetSensorToBaseLinkTransform")
+        self.sensor_to_base_link[int(member)] = v
+
+    def staging(self, member: int):
+        """A (max_points, 4) float32 numpy view of the member's slice of the staging area.  A cloud that is a leading slice of this
+        view is read in place by the kernel, without a copy."""
+        member = int(member)
+        if member not in self._staging:
+            p = C.c_void_p()
+            self._chk(self._L.rdet3d_batch_staging(self._h, member, C.byref(p)), "staging")
+            tp = C.c_float * (4 * self.max_points)
+            self._staging[member] = np.ctypeslib.as_array(tp.from_address(p.value)).reshape(self.max_points, 4)
+        return self._staging[member]
+
+    # -- the fleet interface --------------------------------------------------
+    @staticmethod
+    def pack(clouds):
+        """clouds: iterable of (member, stamp, xyzi) or (member, PointCloud).  -> (ctypes array of rdet3d_cloud, count, the float32
+        arrays it points into)."""
+        clouds = list(clouds)
+        arr = (Rdet3dCloud * max(len(clouds), 1))()
+        keep = []
+        for i, item in enumerate(clouds):
+            member, stamp, xyzi = (item[0], item[1].stamp, item[1].xyzi) if len(item) == 2 else item
+            pts = _as_f32(xyzi)
+            if pts.size & 3:
+                raise ValueError("points are (x, y, z, intensity) quadruples")
+            keep.append(pts)
+            c = arr[i]
+            c.member, c.stamp, c.N = int(member), float(stamp), pts.size >> 2
+            c.xyzi = pts.ctypes.data if c.N else None
+        return arr, len(clouds), keep
+
+    def submit_code(self, clouds) -> int:
+        arr, count, keep = self.pack(clouds)
+        rc = self._L.rdet3d_batch_submit(self._h, C.cast(arr, C.c_void_p), count)
+        if rc == 0:
+            self._pending = (arr, keep, count)
+        return rc
+
+    def submit(self, clouds):
+        """One cloud of any subset of members, at most one per member: ONE kernel launch; returns without waiting for it."""
+        self._chk(self.submit_code(clouds), "rdet3d_batch_submit")
+
+    def collect_code(self, max_centers: int = MAX_CENTERS):
+        """-> (rc, [(status, Observation)]) of the submit that has not been collected."""
+        count = self._pending[2] if self._pending else 0
+        n = max(count, 1)
+        mc = max(0, min(int(max_centers), MAX_CENTERS))
+        status, K, t, nb = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32)
+        cen = np.zeros((n, max(mc, 1), 2), np.float32)
+        rc = self._L.rdet3d_batch_collect(self._h, status.ctypes.data, K.ctypes.data, cen.ctypes.data, mc, t.ctypes.data, nb.ctypes.data)
+        if rc != 0:
+            return rc, []
+        self._pending = None
+        self.last_n_bright = [int(v) for v in nb[:count]]
+        return 0, [(int(status[i]), Observation(float(t[i]), cen[i, : int(K[i])].copy())) for i in range(count)]
+
+    def collect(self, max_centers: int = MAX_CENTERS):
+        """Waits for the launch: [(status, Observation)] in the order of the submitted clouds.  status 0, or the cloud's own error
+        (-4: more than ``max_bright()`` survivors of the intensity gate -- ``last_n_bright`` holds the count -- or more than 256
+        reflectors; -5: more centres than ``max_centers``)."""
+        rc, out = self.collect_code(max_centers)
+        self._chk(rc, "rdet3d_batch_collect")
+        return out
+
+    def detect(self, clouds, max_centers: int = MAX_CENTERS):
+        self.submit(clouds)
         return self.collect(max_centers)
