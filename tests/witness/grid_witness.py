@@ -1,4 +1,4 @@
-"""tests/witness/grid_witness.py -- TEST INFRASTRUCTURE: second, independent statements of three grid-mapper pieces whose
+"""tests/witness/grid_witness.py -- TEST INFRASTRUCTURE: second, independent statements of four grid-mapper pieces whose
 only other restatement is oracle/grid_oracle.c (reference: src/mapping/probability_grid_range_data_inserter_2d.cc:40-114
 with ray_to_pixel_mask.cc:17-168, probability_values.cc; src/scan_matching/real_time_correlative_scan_matcher_2d.cc:20-136).
 
@@ -6,13 +6,17 @@ with ray_to_pixel_mask.cc:17-168, probability_values.cc; src/scan_matching/real_
     crossed between the ordinates y_in and y_out; with half-open pixels [Y, Y+1) an ascending ray covers rows floor(y_in) ..
     ceil(y_out) - 1" -- instead of the oracle's (and the reference's) incremental sub-pixel recurrence; the lookup tables are
     rebuilt with vectorised float32 numpy.
+  * grow_witness: GrowAsNeeded + Grid2D::GrowLimits (probability_grid_range_data_inserter_2d.cc:20-38, grid_2d.cc:59-99) as a
+    closed form -- the number of doublings from the padded bounding box, the offsets as a sum, the old cells pasted as one block
+    -- instead of the oracle's (and the reference's) point-by-point loop that doubles until the point is inside.
   * match_witness: every (rotation, x, y) candidate scored at once with array indexing, the float32 point-order sum as a
     cumulative sum; the oracle loops candidate by candidate.
   * refine_cost_witness: the objective of the Ceres refinement (ceres_scan_matcher_2d.cc:26-62 with
     occupied_space_cost_function_2d.cc:25-81) at one pose, in longdouble, the bicubic interpolation as a tensor product of
     Catmull-Rom weights over all points at once; the oracle and the kernel nest two Horner splines point by point.
-match_witness and refine_cost_witness take `mutant`: the grid convention transposed in one place (MUTANTS), for the tests that
-show which fixtures can tell the convention from its transpose (tests/grid_geometry_cases.py).
+All of them take `mutant`: the grid convention transposed in one place (MUTANTS), for the tests that show which fixtures can
+tell the convention from its transpose (tests/grid_geometry_cases.py for the matchers, tests/grid_write_cases.py for
+insert_witness and grow_witness).
 None of them pins parity with the reference (no tests there, Ceres/Eigen semantics restated): they pin the oracle against a
 differently structured implementation.
 """
@@ -102,32 +106,82 @@ def _cell_index(px, py, max_x, max_y, res):
     return rnd((max_y - float(py)) / res - 0.5), rnd((max_x - float(px)) / res - 0.5)
 
 
-def insert_witness(cells, resolution, max_xy, origin, returns_xy, misses_xy=None, hit_probability=0.55,
-                   miss_probability=0.49, insert_free_space=True):
-    """ProbabilityGridRangeDataInserter2D::Insert on cells[ny, nx] (uint16).  Returns the new grid, or None when a point
-    falls outside (the oracle reports -1 and leaves the grid alone; growing is a separate step)."""
-    g = np.array(cells, np.int64)
-    ny, nx = g.shape
+def super_indices(resolution, max_xy, origin, returns_xy, misses_xy=None):
+    """[(x, y)] super-scaled cell indices (kSubpixelScale sub-pixels per pixel) of the origin, the returns and the misses, in
+    that order (probability_grid_range_data_inserter_2d.cc:48-68)."""
     rs = resolution / S
     pts = [tuple(origin)] + [tuple(p) for p in np.asarray(returns_xy, f32).reshape(-1, 2)] + \
           [tuple(p) for p in (np.asarray(misses_xy, f32).reshape(-1, 2) if misses_xy is not None else [])]
-    idx = [_cell_index(p[0], p[1], max_xy[0], max_xy[1], rs) for p in pts]
-    if any(ix < 0 or iy < 0 or ix >= nx * S or iy >= ny * S for ix, iy in idx):
+    return [_cell_index(p[0], p[1], max_xy[0], max_xy[1], rs) for p in pts]
+
+
+def insert_witness(cells, resolution, max_xy, origin, returns_xy, misses_xy=None, hit_probability=0.55,
+                   miss_probability=0.49, insert_free_space=True, mutant=None):
+    """ProbabilityGridRangeDataInserter2D::Insert on cells[ny, nx] (uint16).  Returns the new grid, or None when a point
+    falls outside (the oracle reports -1 and leaves the grid alone; growing is a separate step).  `mutant`: one of MUTANTS --
+    the bounds test, the maxima or the row stride transposed; a write that a mutant sends past the end of the array is dropped."""
+    g, nx, ny, max_x, max_y, bound_x, bound_y, stride = _geometry(cells, max_xy, mutant)
+    g = g.copy()
+    idx = super_indices(resolution, (max_x, max_y), origin, returns_xy, misses_xy)
+    if any(ix < 0 or iy < 0 or ix >= bound_x * S or iy >= bound_y * S for ix, iy in idx):
         return None
     n_ret = np.asarray(returns_xy).reshape(-1, 2).shape[0]
     hit, miss = lookup_table(hit_probability), lookup_table(miss_probability)
+
+    def apply(table, x, y):                                     # ApplyLookupTable (probability_grid.cc:38-53)
+        k = stride * y + x
+        if 0 <= k < g.size and g[k] < MARK:
+            g[k] = table[g[k]]
+
     for ix, iy in idx[1:1 + n_ret]:                             # hits first (:57-62)
-        x, y = ix // S, iy // S
-        if g[y, x] < MARK:
-            g[y, x] = hit[g[y, x]]
+        apply(hit, ix // S, iy // S)
     if insert_free_space:
         bx, by = idx[0]
         for ix, iy in idx[1:]:                                  # then the rays to every return and miss (:69-91)
             for x, y in ray_pixels(bx, by, ix, iy):
-                if g[y, x] < MARK:
-                    g[y, x] = miss[g[y, x]]
+                apply(miss, x, y)
     g[g >= MARK] -= MARK                                        # FinishUpdate (grid_2d.cc:20-29)
-    return g.astype(np.uint16)
+    return g.reshape(ny, nx).astype(np.uint16)
+
+
+def grow_witness(cells, resolution, max_xy, origin, returns_xy, misses_xy=None, mutant=None):
+    """GrowAsNeeded + Grid2D::GrowLimits (probability_grid_range_data_inserter_2d.cc:20-38, grid_2d.cc:59-99) in closed form ->
+    (grown cells, new max_xy, offset (x, y) of the old cell (0, 0)).
+
+    The box of origin, returns and misses in float32, padded by float32 1e-6; k = the smallest number of doublings after which
+    both padded corners have a cell index inside; after k doublings a side of n cells has 2^k n, the old cell (0, 0) lies at
+    sum_{j<k} floor(n 2^j / 2) in each axis, and the maxima have grown by resolution times the OTHER axis' offset of each step
+    (max.x belongs to the rows), accumulated in double step by step as the reference rounds them; the old cells are one block
+    in a grid of zeros.  `mutant`="maxima" feeds each maximum from its own axis' offset (the other two MUTANTS have no place
+    here and change nothing); k is decided by the convention itself, so that a mutant stays defined."""
+    assert mutant is None or mutant in MUTANTS, mutant
+    old = np.asarray(cells, np.uint16)
+    ny, nx = old.shape
+    pts = np.concatenate([np.asarray(origin, f32).reshape(1, 2), np.asarray(returns_xy, f32).reshape(-1, 2),
+                          np.asarray(misses_xy if misses_xy is not None else [], f32).reshape(-1, 2)])
+    pad = f32(1e-6)
+    corners = ((pts[:, 0].min() - pad, pts[:, 1].min() - pad), (pts[:, 0].max() + pad, pts[:, 1].max() + pad))
+    maxima = [(float(max_xy[0]), float(max_xy[1]))]              # after 0, 1, 2 ... doublings
+
+    def inside(k):
+        cols, rows = nx << k, ny << k
+        at = [_cell_index(px, py, maxima[k][0], maxima[k][1], resolution) for px, py in corners]
+        return all(0 <= ix < cols and 0 <= iy < rows for ix, iy in at)
+
+    k = 0
+    while not inside(k):
+        maxima.append((maxima[k][0] + resolution * float((ny << k) // 2), maxima[k][1] + resolution * float((nx << k) // 2)))
+        k += 1
+    off_x, off_y = sum((nx << j) // 2 for j in range(k)), sum((ny << j) // 2 for j in range(k))
+    new_max = maxima[k]
+    if mutant == "maxima":
+        mx, my = maxima[0]
+        for j in range(k):
+            mx, my = mx + resolution * float((nx << j) // 2), my + resolution * float((ny << j) // 2)
+        new_max = (mx, my)
+    grown = np.zeros((ny << k, nx << k), np.uint16)
+    grown[off_y:off_y + ny, off_x:off_x + nx] = old
+    return grown, new_max, (off_x, off_y)
 
 
 # ---- real-time correlative matcher ----------------------------------------------------------------------------------
