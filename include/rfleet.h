@@ -7,7 +7,7 @@
  * with events in the call is advanced by one workgroup of one launch (csrc/fleet_kernels.hip), whatever the number of members.
  *
  * Per member the semantics are the single filter's (reference reflector_ekf_slam.cc): Predict (DIFF / OMNI), ReflectorMatch's
- * state branch, the joint EKF update, landmark augmentation, and the odometry quirks (a message with t < state time is
+ * map and state branches, the joint EKF update, landmark augmentation, and the odometry quirks (a message with t < state time is
  * dropped, use_imu ignores odometry, an empty scan is a Predict).
  *
  * Conventions: as rekf.h -- opaque handle, one HIP stream per handle, NOT thread-safe, caller-owned host buffers borrowed
@@ -24,7 +24,11 @@
  * exist only when the scan matched at least one reflector (a fix on a scan without a match, an empty one included, is
  * ignored).  rfleet_predict_poses is PredictState's pose block for every member: the pose a scan matcher starts from.
  *
- * Deliberately OUT OF SCOPE (use a rekf handle): the pre-loaded map branch (rekf_set_map; n_map is always 0 here), scans
+ * The localisation deployment (LoadMapFromTxtFile; reflector_ekf_slam.cc:401-425, :279-302) is served by ONE pre-loaded reflector
+ * map per fleet, shared by its members (one hall): rfleet_set_map.  A member that uses it tries the map first (weighted distance
+ * < 0.05), then its own state (< 0.6); a map-matched observation corrects the pose through rows without a landmark block.
+ *
+ * Deliberately OUT OF SCOPE (use a rekf handle): a map per member, a map of more than RFLEET_MAX_MAP_POINTS points, scans
  * wider than RFLEET_MAX_OBS, auto-grow, PredictState's landmark part (the full state), marker ellipses.
  *
  * The covariance of a member lives on the device as its lower triangle; the getters mirror it (as rekf_get_state does).
@@ -41,6 +45,7 @@ extern "C" {
 #define RFLEET_ABI_VERSION 2
 #define RFLEET_MAX_LANDMARKS 128     /* per member: n <= 259 */
 #define RFLEET_MAX_OBS 32            /* per scan: one joint update, m <= 64 innovation rows */
+#define RFLEET_MAX_MAP_POINTS 2048   /* the fleet's shared pre-loaded map */
 
 typedef struct rfleet rfleet_t;
 
@@ -83,8 +88,15 @@ int rfleet_get_state(rfleet_t *f, int member, double *t, int *n, double *mu, lon
 /* As rekf_set_state: only the lower triangle of sigma is used; vt3 = nullable last odometry velocity. */
 int rfleet_set_state(rfleet_t *f, int member, double t, int n, const double *mu, const double *sigma, const double *vt3);
 /* The member's last scan: pairs are (observation, landmark); buffers hold RFLEET_MAX_OBS entries (pairs: twice that).
- * Any pointer may be NULL.  *n_map is always 0. */
+ * Any pointer may be NULL.  map_pairs are (observation, map point); *n_map is 0 for a member that does not use the map. */
 int rfleet_get_last_match(rfleet_t *f, int member, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new, int *new_ids);
+/* map_ as LoadMapFromTxtFile leaves it, shared by the fleet: M points (float32 xy) and M row-major 2x2 weights, as rekf_set_map.
+ * use[b] != 0: member b matches against it (NULL = every member).  M = 0 clears the map.  Synchronises, replaces the device copy;
+ * takes effect with the next rfleet_submit.  A null handle, M < 0, M > 0 with a null xy or cov, or a non-finite coordinate or
+ * weight is REKF_ERR_INVALID, M > RFLEET_MAX_MAP_POINTS is REKF_ERR_UNSUPPORTED, both before any HIP call; a refused call
+ * leaves the old map in place.  (Added without a new RFLEET_ABI_VERSION: a binding looks the two calls up by name.) */
+int rfleet_set_map(rfleet_t *f, const float *xy, const double *cov, int M, const unsigned char *use /*[B], nullable*/);
+int rfleet_get_map_size(rfleet_t *f, int *M);
 /* Wait for all enqueued work.  REKF_ERR_HIP when the device reported an error. */
 int rfleet_sync(rfleet_t *f);
 int rfleet_size(rfleet_t *f, int *B, int *max_landmarks);

@@ -10,6 +10,9 @@
 //                        and columns [m, roundup(m, 16)) are written as zeros, nothing beyond them is read
 //   Kn  [ld x 64]        K = W S^-1, same shape and padding
 //   ctl                  FleetMemberCtl: n, sticky flags, the last scan's ReflectorMatchResult
+// and per FLEET, shared by its members (rfleet_set_map): the pre-loaded reflector map, M_ points as float32 (x, y) and M_ row-major
+// 2 x 2 FP64 weights, read from global memory by every workgroup of k_fleet_step_map (<= 80 KB: it stays in L2), and one byte per
+// member that says whether the member matches against it.
 // W and Kn are scratch of the member's own workgroup: written and read inside one launch by that workgroup only.
 // Time and the last odometry velocity live on the HOST (rfleet_api.hip): an event arrives with its dt and velocity.
 #pragma once
@@ -32,9 +35,11 @@ struct FleetMemberCtl {
     int n;                   // state dimension 3 + 2 L
     int flags;               // sticky REKF_FLAG_*
     int K, n_state, n_new;   // the last scan's record
-    int pad_[3];
+    int n_map;               // written by k_fleet_step_map only: the host knows which kernel wrote a member's last record
+    int pad_[2];
     int state_pairs[2 * RFLEET_MAX_OBS_DEV];
     int new_ids[RFLEET_MAX_OBS_DEV];
+    int map_pairs[2 * RFLEET_MAX_OBS_DEV];    // (observation, map point), k_fleet_step_map only
 };
 
 struct FleetMemberOpt { double lin_cov, ang_cov, obs_cov; int model; int pad_; };
@@ -59,6 +64,11 @@ struct FleetLaunch {         // one rfleet_submit: G members with events, member
     const float *obs;
     const double *fix;       // the pose fixes of the call's scans, three doubles each; NULL when no scan of the call has one
     int G, pad_;
+    // the shared map (k_fleet_step_map only; behind everything else, so that no argument of the other two kernels moves)
+    const float *map_xy;     // [M_map][2]
+    const double *map_cov;   // [M_map][4], row-major 2 x 2
+    const unsigned char *map_use;   // [B]: non-zero = the member matches against the map
+    int M_map, pad2_;        // M_map > 0 selects k_fleet_step_map
 };
 
 hipError_t rfleet_launch_step(const FleetDev &d, const FleetLaunch &l, hipStream_t s);

@@ -1,11 +1,15 @@
 // rfleet_api.hip -- host side of the fleet filter (include/rfleet.h): validation, the host's time / velocity mirror,
-// the pinned staging ring, one launch of k_fleet_step per rfleet_submit.
+// the pinned staging ring, one launch of k_fleet_step per rfleet_submit, the fleet's shared pre-loaded map.
 //
 // Time and vt_ are host state: HandleOdometryMessage's `t < state time` test (cc:211-212) and the use_imu switch are decided
 // here, before packing, and every packed event carries its own dt and velocity.  A call's events are grouped by member (stable:
 // a member's events keep their order) into one segment of a ring of pinned buffers, which the kernel reads in place; a
 // segment is reused only after the launch that read it has finished (one hipEvent per segment), so consecutive submits
 // do not synchronise until the ring has gone round.
+//
+// The map (rfleet_set_map) is one device buffer per fleet and a byte per member.  A submit takes k_fleet_step_map only when a member
+// with events in it uses a non-empty map.  The other two kernels never touch FleetMemberCtl::n_map / map_pairs, so the host
+// remembers per member whether its last scan's record was written by the map kernel (map_rec).
 #include "fleet_dev.h"
 #include "../../include/rfleet.h"
 
@@ -36,6 +40,13 @@ struct rfleet {
     Segment seg[kSegs];
     int next_seg = 0;
     std::string hip_error;
+    // the shared map: device copies, the host's copy of the per-member switch, and who wrote each member's last match record
+    float *map_xy = nullptr;
+    double *map_cov = nullptr;
+    unsigned char *map_use_dev = nullptr;
+    int M_map = 0;
+    std::vector<unsigned char> map_use, map_rec;
+    std::vector<int> scanned;               // scratch of rfleet_submit: members with a scan event in the call
     // scratch of rfleet_submit (kept to avoid per-call allocation)
     std::vector<int> cnt, pos, order;
     std::vector<double> time_tmp, vt_tmp;
@@ -77,6 +88,9 @@ void rfleet_destroy(rfleet_t *f)
     if (f->dev.ctl) (void)hipFree(f->dev.ctl);
     if (f->dev.opt) (void)hipFree((void *)f->dev.opt);
     if (f->pose_host) (void)hipHostFree(f->pose_host);
+    if (f->map_xy) (void)hipFree(f->map_xy);
+    if (f->map_cov) (void)hipFree(f->map_cov);
+    if (f->map_use_dev) (void)hipFree(f->map_use_dev);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
@@ -146,6 +160,8 @@ int rfleet_create(const rekf_options *opts, int B, int max_landmarks, int device
     f->vt.assign((size_t)3 * B, 0.0);
     f->cnt.resize((size_t)B);
     f->pos.resize((size_t)B);
+    f->map_use.assign((size_t)B, 0);
+    f->map_rec.assign((size_t)B, 0);
     const int rc = fleet_create_body(f, opts);
     if (rc != REKF_OK) {
         rfleet_destroy(f);
@@ -196,6 +212,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     f->time_tmp = f->time;
     f->vt_tmp = f->vt;
     f->order.clear();
+    f->scanned.clear();
     std::fill(f->cnt.begin(), f->cnt.end(), 0);
     size_t n_obs = 0, n_fix = 0;
     std::vector<double> &dts = f->stage;
@@ -210,6 +227,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
         } else {
             n_obs += (size_t)e.K;
             n_fix += e.has_pose_fix ? 1 : 0;
+            f->scanned.push_back(b);
         }
         dts[4 * (size_t)i] = e.t - f->time_tmp[b];                         // cc:217-218 / :232-233
         for (int k = 0; k < 3; ++k) dts[4 * (size_t)i + 1 + k] = f->vt_tmp[3 * b + k];
@@ -220,7 +238,11 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     const int E = (int)f->order.size();
     if (E == 0) return REKF_OK;
     int G = 0;
-    for (int b = 0; b < B; ++b) G += f->cnt[b] > 0;
+    bool with_map = false;                                                 // a member with events matches against a non-empty map
+    for (int b = 0; b < B; ++b) {
+        G += f->cnt[b] > 0;
+        with_map = with_map || (f->cnt[b] > 0 && f->M_map > 0 && f->map_use[b]);
+    }
     // ---- a ring segment: members[G] | ev_begin[G + 1] | events[E] | fix[3 n_fix] | obs[2 n_obs]
     const size_t off_mem = 0, off_beg = align16(off_mem + sizeof(int) * G), off_ev = align16(off_beg + sizeof(int) * (G + 1));
     const size_t off_fix = align16(off_ev + sizeof(FleetEvent) * E), off_obs = align16(off_fix + sizeof(double) * 3 * n_fix);
@@ -288,7 +310,14 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     L.obs = (const float *)(s.dev + off_obs);
     L.fix = n_fix ? (const double *)(s.dev + off_fix) : nullptr;      // (NULL selects the kernel without the pose phase)
     L.G = G;
+    if (with_map) {                                                        // (M_map > 0 selects the kernel with the map branch)
+        L.map_xy = f->map_xy;
+        L.map_cov = f->map_cov;
+        L.map_use = f->map_use_dev;
+        L.M_map = f->M_map;
+    }
     FLEET_HIP(f, rfleet_launch_step(f->dev, L, f->stream));
+    for (int b : f->scanned) f->map_rec[b] = with_map ? 1 : 0;
     f->time.swap(f->time_tmp);
     f->vt.swap(f->vt_tmp);
     FLEET_HIP(f, hipEventRecord(s.done, f->stream));
@@ -407,17 +436,65 @@ int rfleet_set_state(rfleet_t *f, int member, double t, int n, const double *mu,
 
 int rfleet_get_last_match(rfleet_t *f, int member, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new, int *new_ids)
 {
-    (void)map_pairs;
     if (!f || member < 0 || member >= f->B) return REKF_ERR_INVALID;
     const int rc = rfleet_sync(f);
     if (rc != REKF_OK) return rc;
     FleetMemberCtl c;
     FLEET_HIP(f, hipMemcpy(&c, f->dev.ctl + member, sizeof(c), hipMemcpyDeviceToHost));
     if (n_state) *n_state = c.n_state;
-    if (n_map) *n_map = 0;
+    const int nm = f->map_rec[member] ? c.n_map : 0;                       // (only the map kernel writes the map part of a record)
+    if (n_map) *n_map = nm;
+    if (map_pairs) memcpy(map_pairs, c.map_pairs, sizeof(int) * 2 * (size_t)nm);
     if (n_new) *n_new = c.n_new;
     if (state_pairs) memcpy(state_pairs, c.state_pairs, sizeof(int) * 2 * (size_t)c.n_state);
     if (new_ids) memcpy(new_ids, c.new_ids, sizeof(int) * (size_t)c.n_new);
+    return REKF_OK;
+}
+
+int rfleet_set_map(rfleet_t *f, const float *xy, const double *cov, int M, const unsigned char *use)
+{
+    if (!f || M < 0 || (M > 0 && (!xy || !cov))) return REKF_ERR_INVALID;
+    if (M > RFLEET_MAX_MAP_POINTS) return REKF_ERR_UNSUPPORTED;
+    for (int i = 0; i < 2 * M; ++i)
+        if (!std::isfinite(xy[i])) return REKF_ERR_INVALID;
+    for (int i = 0; i < 4 * M; ++i)
+        if (!std::isfinite(cov[i])) return REKF_ERR_INVALID;
+    const int rc = rfleet_sync(f);                                         // no launch reads the old copy any more
+    if (rc != REKF_OK) return rc;
+    const size_t B = (size_t)f->B;
+    std::vector<unsigned char> want(B, 1);
+    if (use)
+        for (size_t b = 0; b < B; ++b) want[b] = use[b] ? 1 : 0;
+    float *nxy = nullptr;
+    double *ncov = nullptr;
+    if (M > 0) {                                                           // the new copy first: a failure leaves the old map in place
+        hipError_t e_ = hipMalloc((void **)&nxy, sizeof(float) * 2 * (size_t)M);
+        if (e_ == hipSuccess) e_ = hipMalloc((void **)&ncov, sizeof(double) * 4 * (size_t)M);
+        if (e_ == hipSuccess && !f->map_use_dev) e_ = hipMalloc((void **)&f->map_use_dev, B);
+        if (e_ == hipSuccess) e_ = hipMemcpy(nxy, xy, sizeof(float) * 2 * (size_t)M, hipMemcpyHostToDevice);
+        if (e_ == hipSuccess) e_ = hipMemcpy(ncov, cov, sizeof(double) * 4 * (size_t)M, hipMemcpyHostToDevice);
+        if (e_ == hipSuccess) e_ = hipMemcpy(f->map_use_dev, want.data(), B, hipMemcpyHostToDevice);
+        if (e_ != hipSuccess) {
+            if (nxy) (void)hipFree(nxy);
+            if (ncov) (void)hipFree(ncov);
+            if (f->map_use_dev) (void)hipMemcpy(f->map_use_dev, f->map_use.data(), B, hipMemcpyHostToDevice);
+            f->hip_error = std::string("rfleet_set_map: ") + hipGetErrorString(e_);
+            return REKF_ERR_HIP;
+        }
+    }
+    if (f->map_xy) (void)hipFree(f->map_xy);
+    if (f->map_cov) (void)hipFree(f->map_cov);
+    f->map_xy = nxy;
+    f->map_cov = ncov;
+    f->M_map = M;
+    f->map_use.swap(want);
+    return REKF_OK;
+}
+
+int rfleet_get_map_size(rfleet_t *f, int *M)
+{
+    if (!f || !M) return REKF_ERR_INVALID;
+    *M = f->M_map;
     return REKF_OK;
 }
 

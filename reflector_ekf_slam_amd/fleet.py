@@ -3,7 +3,8 @@
 ``ReflectorEKFSLAMFleet(options_list)`` holds B independent filters (at most 128 reflectors each).  ``submit(events)`` hands
 over any number of odometry / scan messages of any subset of members and enqueues one launch of k_fleet_step (one workgroup
 per member with events); ``poses()`` reads all poses back.  A scan may carry an absolute pose fix (the reference's USE_GPS
-deployment: ``predict_poses(times)`` -> scan matcher -> ``scan_event(..., pose_fix=matched_pose)``).  ``member(i)`` is a view with the snake_case filter interface of
+deployment: ``predict_poses(times)`` -> scan matcher -> ``scan_event(..., pose_fix=matched_pose)``).  ``set_map(xy, cov)`` gives the
+fleet ONE pre-loaded reflector map that its members localise against (the reference's LoadMapFromTxtFile deployment).  ``member(i)`` is a view with the snake_case filter interface of
 ``ReflectorEKFSLAM`` (each call a one-event submit), for code that drives one robot at a time.
 
 All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fallback.
@@ -21,6 +22,7 @@ from .ekf_slam import ReflectorMatchResult, RekfError, State
 RFLEET_ABI_VERSION = 2        # must equal RFLEET_ABI_VERSION of include/rfleet.h and rfleet_abi_version() of the built library
 MAX_LANDMARKS = 128
 MAX_OBS = 32
+MAX_MAP_POINTS = 2048
 EV_ODOM, EV_SCAN = 0, 1
 
 
@@ -69,6 +71,25 @@ def rfleet():
     L.rfleet_sync.argtypes = [vp]
     L.rfleet_size.argtypes = [vp, ip, ip]
     _rfleet = L
+    return L
+
+
+_map_ready = None
+
+
+def _map_lib():
+    """``rfleet()`` with the argtypes of the map calls set.  They were added without a new ABI version and are looked up by name:
+    raises LibraryMissing when the built library has none; every other call keeps working then."""
+    global _map_ready
+    if _map_ready is not None:
+        return _map_ready
+    L = rfleet()
+    missing = [n for n in ("rfleet_set_map", "rfleet_get_map_size") if not hasattr(L, n)]
+    if missing:
+        raise _lib.LibraryMissing(f"librfleet.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
+    L.rfleet_set_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.rfleet_get_map_size.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    _map_ready = L
     return L
 
 
@@ -235,11 +256,39 @@ class ReflectorEKFSLAMFleet:
 
     def last_match(self, i: int) -> ReflectorMatchResult:
         sp = np.zeros((MAX_OBS, 2), np.int32)
+        mp = np.zeros((MAX_OBS, 2), np.int32)
         nw = np.zeros((MAX_OBS,), np.int32)
         ns, nm, nn = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self._L.rfleet_get_last_match(self._h, int(i), C.byref(ns), sp.ctypes.data, C.byref(nm), None,
+        self._chk(self._L.rfleet_get_last_match(self._h, int(i), C.byref(ns), sp.ctypes.data, C.byref(nm), mp.ctypes.data,
                                                 C.byref(nn), nw.ctypes.data), "rfleet_get_last_match")
-        return ReflectorMatchResult(np.zeros((0, 2), np.int32), sp[: ns.value].copy(), nw[: nn.value].copy())
+        return ReflectorMatchResult(mp[: nm.value].copy(), sp[: ns.value].copy(), nw[: nn.value].copy())
+
+    # -- the shared pre-loaded map ------------------------------------------------
+    def set_map_code(self, xy, cov, members=None) -> int:
+        xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+        cov = np.ascontiguousarray(cov, dtype=np.float64).reshape(-1, 4)
+        if xy.shape[0] != cov.shape[0]:
+            raise ValueError("one 2 x 2 weight per map point")
+        use = None
+        if members is not None:
+            use = np.zeros(self.B, np.uint8)
+            use[np.asarray(list(members), np.int64)] = 1
+        M = xy.shape[0]
+        return _map_lib().rfleet_set_map(self._h, xy.ctypes.data if M else None, cov.ctypes.data if M else None, M,
+                                         None if use is None else use.ctypes.data)
+
+    def set_map(self, xy, cov, members=None):
+        """The fleet's pre-loaded reflector map (sensor::Map as LoadMapFromTxtFile leaves it): xy [M, 2] float32, cov [M, 2, 2]
+        weights, M <= MAX_MAP_POINTS; an empty map clears it.  ``members``: the indices of the members that match against it
+        (None = all).  Synchronises; holds from the next ``submit``.  The map is the fleet's: a member has no map of its own."""
+        rc = self.set_map_code(xy, cov, members)
+        if rc != 0:
+            self._chk(rc, "rfleet_set_map")
+
+    def map_size(self) -> int:
+        M = C.c_int()
+        self._chk(_map_lib().rfleet_get_map_size(self._h, C.byref(M)), "rfleet_get_map_size")
+        return M.value
 
 
 class FleetMember:
