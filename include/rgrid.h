@@ -329,6 +329,31 @@ int rgrid_batch_filter_collect(rgrid_batch_t *b, int *status, int *counts, float
 /* Points per cloud one workgroup of kgb_filter holds (8192: 8 B of voxel keys and two 4 B table slots per point in LDS). */
 int rgrid_batch_filter_max_points(void);
 
+/* ---- fleet texture: MapBuilder::ToSubmapTexture (map_builder.cc:128-134 -> ProbabilityGrid::DrawToSubmapTexture,
+ * probability_grid.cc:86-131) for the resident slots of many robots, ONE launch and ONE synchronisation per call (kgb_texture, one
+ * workgroup per named slot, csrc/rgrid_batch.hip).  The specification is the single call: for every named slot, box, slice_max and
+ * the bytes are exactly what rgrid_draw_texture returns from an rgrid_t holding the same grid -- the box of the cells whose raw
+ * value is not 0 as (offset_x, offset_y, width, height), (0, 0, 1, 1) and the one pair (0, 0) when there is none; two bytes
+ * (value, alpha) per cell of the box, x fastest; slice_max = limits.max - resolution * (offset_y, offset_x).  The call only reads
+ * the slots, which stay on the device.  The slots are named by a plain array of ints: a slot index is all a texture needs, a
+ * record of one field would only make the caller pack what it already has.  The table of byte pairs is uploaded by the handle's
+ * first texture submit; the output area (pinned host memory the kernel writes, 2 * num_x_cells * num_y_cells bytes per named slot)
+ * and the box records are allocated by it too and grow only when a later call needs more: a steady-state call allocates nothing.
+ * The ABI version stays 4: a caller that may meet an older library looks for these symbols. */
+
+/* Enqueues the textures of slots grids[0 .. count) and returns without waiting.  Refused as a whole with RGRID_ERR_INVALID, nothing
+ * launched and the handle still usable: a null b, a null grids with count > 0, count outside [0, max_scans], a slot out of range or
+ * not yet set, a pending submit of any kind.  The same slot may be named more than once.  count == 0 is a submit with nothing
+ * launched. */
+int rgrid_batch_texture_submit(rgrid_batch_t *b, const int *grids, int count);
+
+/* Waits once and hands out the pending texture submit's results in its order: boxes (4 * count), slice_max (2 * count), offsets
+ * (count: the byte in `cells` where texture j starts) and the textures back to back in `cells`, 2 * width * height bytes each.
+ * RGRID_ERR_BUFFER when cap is below their sum, or cells is NULL with a sum that is not 0: boxes, slice_max and offsets are filled
+ * and the submit is LEFT PENDING, the caller comes again with room; cap = sum of 2 * num_x_cells * num_y_cells always suffices.
+ * RGRID_ERR_INVALID without a pending texture submit (a pending submit of another kind stays pending). */
+int rgrid_batch_texture_collect(rgrid_batch_t *b, int *boxes, double *slice_max, long *offsets, uint8_t *cells, long cap);
+
 int rgrid_batch_sizeof_scan(void);
 int rgrid_batch_sizeof_refine_scan(void);
 int rgrid_batch_sizeof_insert_scan(void);

@@ -461,26 +461,6 @@ __global__ __launch_bounds__(256) void kg_texture(const unsigned short *__restri
     if (x < w) out[(size_t)w * y + x] = table[cells[(size_t)nx * (y0 + y) + (x0 + x)] & 32767u];
 }
 
-// (value, alpha) of every cell value: 128 - ProbabilityToLogOddsInteger(GetProbability) (probability_grid.cc:97-114,
-// submaps.h:22-41), host float32 with the same libm a CPU build uses; entry = value | alpha << 8
-void texture_table(unsigned short *table)
-{
-#pragma clang fp contract(off)
-    const float kMinP = 0.1f, kMaxP = 1.f - kMinP;
-    const float kMaxLogOdds = std::log(kMaxP / (1.f - kMaxP)), kMinLogOdds = std::log(kMinP / (1.f - kMinP));
-    const float lower = 1.f - kMaxP, upper = 1.f - kMinP, kScale = (upper - lower) / (32768 - 2.f);
-    table[0] = 0;                                                                // unknown: (0, 0)
-    for (int v = 1; v < 32768; ++v) {
-        const float cost = (float)v * kScale + (lower - kScale);
-        const float p = 1.f - cost;
-        const float logit = std::log(p / (1.f - p));
-        const int li = (int)std::lround((logit - kMinLogOdds) * 254.f / (kMaxLogOdds - kMinLogOdds)) + 1;
-        const int delta = 128 - li;
-        const unsigned alpha = (unsigned)(delta > 0 ? 0 : -delta) & 255u, value = (unsigned)(delta > 0 ? delta : 0) & 255u;
-        table[v] = (unsigned short)(value | ((value || alpha) ? alpha : 1u) << 8);
-    }
-}
-
 }  // namespace
 
 struct rgrid {

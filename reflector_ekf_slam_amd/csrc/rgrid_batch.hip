@@ -666,6 +666,116 @@ __global__ __launch_bounds__(KGF_THREADS) void kgb_filter(FilterBufs B)
     if (threadIdx.x == 0) { int *c = B.counts + 3 * blockIdx.x; c[0] = n_fr; c[1] = n_fm; c[2] = n_av; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// MapBuilder::ToSubmapTexture for a batch (Submap2D::GetMapTextureData -> ProbabilityGrid::DrawToSubmapTexture,
+// probability_grid.cc:86-131, with Grid2D::ComputeCroppedLimits, grid_2d.cc:36-48): ONE workgroup per named slot does what
+// rgrid_draw_texture does with kg_known_box, a round trip to the host and kg_texture.  Phase 1 reduces the slot's nx * ny cells to
+// the box of its known cells (raw value not 0) inside the workgroup -- per-thread min / max, wave shuffles, LDS across the waves:
+// no atomics, nothing to clear before the launch.  Phase 2, behind the barrier, writes the (value, alpha) pairs of the box
+// compactly (stride = width) to the start of the slot's region of the output area.  The launch only reads the pool, so a slot may
+// be named more than once and no workgroup waits for another.  DESIGN.md 10.7.
+//
+// Both phases move 16 bytes per lane where they can.  A slot starts grid * max_cells cells into the pool, which is 2-byte aligned
+// and no more when max_cells is odd: phase 1 walks the slot as ONE array of nx * ny cells -- the cells in front of the first
+// 16-byte boundary and behind the last one singly, the eight-cell vectors between them whole -- and never touches the stale
+// max_cells - nx * ny cells behind it.  Phase 2 gathers single cells (a row of the box starts anywhere) and stores eight pairs at
+// once: the region's start is 16-byte aligned by the host's prefix sum, the last w * h mod 8 pairs go singly.
+#define KGT_THREADS 512
+#define KGT_WAVES (KGT_THREADS / 64)
+#define KGT_PF 4                          // 16-byte vectors of cells a thread has in flight in phase 1
+
+// One named slot of a texture call; an array of these lies at the start of the call's segment.
+struct TextureRec {
+    long long cells_off;                  // its grid's first cell in the grid pool
+    long long out_off;                    // its region's first pair in the output area (a multiple of 8)
+    int nx, ny;
+};
+static_assert(sizeof(TextureRec) <= sizeof(BatchRec), "the texture records lie where a match's records lie");
+
+struct TextureBufs {
+    const unsigned char *seg;             // the call's segment: TextureRec[nrec]
+    const unsigned short *cells;          // grid pool
+    const unsigned short *table;          // texture_table: value | alpha << 8 per cell value
+    unsigned short *out;                  // pinned host memory: a region of nx * ny pairs (rounded up to 8) per record
+    int *box;                             // [nrec][4]: offset_x, offset_y, width, height, pinned host memory
+};
+
+__global__ __launch_bounds__(KGT_THREADS) void kgb_texture(TextureBufs B)
+{
+    __shared__ int s_box[KGT_WAVES][4];
+    const TextureRec R = reinterpret_cast<const TextureRec *>(B.seg)[blockIdx.x];
+    const unsigned short *__restrict__ cells = B.cells + R.cells_off;
+    const int nx = R.nx, n = R.nx * R.ny;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // ---- phase 1: the columns [x0, x1] and the linear indices [k0, k1] the known cells span; the rows follow from k0 and k1
+    int x0 = 0x7fffffff, x1 = -1, k0 = 0x7fffffff, k1 = -1;
+    auto see = [&](int k, int x) { x0 = min(x0, x); x1 = max(x1, x); k0 = min(k0, k); k1 = max(k1, k); };
+    const int to_boundary = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(cells) & 15u)) & 15u) >> 1);
+    const int head = min(n, to_boundary), nvec = (n - head) >> 3, tail = head + 8 * nvec;
+    for (int k = tid; k < head; k += KGT_THREADS)
+        if (cells[k] != 0) see(k, k % nx);
+    for (int k = tail + tid; k < n; k += KGT_THREADS)
+        if (cells[k] != 0) see(k, k % nx);
+    const uint4 *__restrict__ vec = reinterpret_cast<const uint4 *>(cells + head);
+    for (int v0 = 0; v0 < nvec; v0 += KGT_THREADS * KGT_PF) {
+        uint4 q[KGT_PF];
+#pragma unroll
+        for (int u = 0; u < KGT_PF; ++u) {
+            const int v = v0 + u * KGT_THREADS + tid;
+            q[u] = v < nvec ? vec[v] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < KGT_PF; ++u) {
+            if ((q[u].x | q[u].y | q[u].z | q[u].w) == 0u) continue;                // eight unknown cells (or none at all)
+            const unsigned w32[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+            const int k = head + 8 * (v0 + u * KGT_THREADS + tid);
+            int x = k % nx;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                if (((w32[c >> 1] >> (16 * (c & 1))) & 0xffffu) != 0u) see(k + c, x);
+                if (++x == nx) x = 0;                                              // the vector runs on into the next row
+            }
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        x0 = min(x0, __shfl_xor(x0, off, 64)); x1 = max(x1, __shfl_xor(x1, off, 64));
+        k0 = min(k0, __shfl_xor(k0, off, 64)); k1 = max(k1, __shfl_xor(k1, off, 64));
+    }
+    if (lane == 0) { s_box[wave][0] = x0; s_box[wave][1] = x1; s_box[wave][2] = k0; s_box[wave][3] = k1; }
+    __syncthreads();
+    for (int w = 0; w < KGT_WAVES; ++w) {
+        x0 = min(x0, s_box[w][0]); x1 = max(x1, s_box[w][1]); k0 = min(k0, s_box[w][2]); k1 = max(k1, s_box[w][3]);
+    }
+    int y0 = 0, y1 = 0;
+    if (x1 < 0) { x0 = 0; x1 = 0; }                                                // nothing known: offset 0, CellLimits(1, 1) (grid_2d.cc:39-44)
+    else { y0 = k0 / nx; y1 = k1 / nx; }
+    x0 = __builtin_amdgcn_readfirstlane(x0); y0 = __builtin_amdgcn_readfirstlane(y0);
+    const int w = __builtin_amdgcn_readfirstlane(x1 - x0 + 1), h = __builtin_amdgcn_readfirstlane(y1 - y0 + 1);
+    if (tid == 0) { int *box = B.box + 4 * blockIdx.x; box[0] = x0; box[1] = y0; box[2] = w; box[3] = h; }
+    // ---- phase 2: pair o of the texture is cell (x0 + o % w, y0 + o / w); eight pairs per store
+    const unsigned short *__restrict__ table = B.table;
+    const unsigned short *__restrict__ win = cells + (size_t)nx * y0 + x0;         // the box's first cell: all of it lies inside the slot
+    unsigned short *out = B.out + R.out_off;
+    const int total = w * h, nout = total >> 3;
+    for (int v = tid; v < nout; v += KGT_THREADS) {
+        const int o = 8 * v;
+        int yy = o / w, xx = o - yy * w;
+        unsigned p[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            p[c] = win[nx * yy + xx];
+            if (++xx == w) { xx = 0; ++yy; }
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) p[c] = table[p[c] & 32767u];
+        reinterpret_cast<uint4 *>(out)[v] = make_uint4(p[0] | p[1] << 16, p[2] | p[3] << 16, p[4] | p[5] << 16, p[6] | p[7] << 16);
+    }
+    for (int o = 8 * nout + tid; o < total; o += KGT_THREADS) {
+        const int yy = o / w, xx = o - yy * w;
+        out[o] = table[win[nx * yy + xx] & 32767u];
+    }
+}
+
 struct GridSlot {
     bool set = false;
     int nx = 0, ny = 0;
@@ -682,10 +792,13 @@ struct Pending {
 // what a packed match launches with
 struct MatchWork { int nrec, nwg, nf2, n_max; };
 
-enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3, KIND_INSERT = 4, KIND_FILTER = 5 };  // the pending submit
+enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3, KIND_INSERT = 4, KIND_FILTER = 5, KIND_TEXTURE = 6 };  // the pending submit
 
 // what collect needs of a scan of a filter submit
 struct FilterPending { int status, rec, out_off, n_ret, n_mis; };
+
+// what collect needs of a named slot of a texture submit
+struct TexturePending { int grid; long long out_off; };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -740,6 +853,13 @@ struct rgrid_batch {
     float2 *h_fout = nullptr, *dv_fout = nullptr;
     int *h_fcnt = nullptr, *dv_fcnt = nullptr;
     std::vector<FilterPending> fsub;
+    // the texture: the (value, alpha) table (uint16[32768]) on the device, uploaded by the first texture submit; the output area
+    // and the box records in pinned host memory, allocated by the first texture submit and grown only when a call needs more
+    unsigned short *d_tex = nullptr;
+    unsigned short *h_tout = nullptr, *dv_tout = nullptr;
+    size_t tout_pairs = 0;
+    int *h_tbox = nullptr, *dv_tbox = nullptr;
+    std::vector<TexturePending> tsub;
     std::vector<GridSlot> grids;
     bool outstanding = false;
     int kind = 0;                          // KIND_* of the outstanding submit
@@ -904,6 +1024,34 @@ int filter_staging(rgrid_batch_t *b)
     return RGRID_OK;
 }
 
+// the texture's staging for a call that writes `pairs` pairs: the table and the box records once, the output area when it is too small
+int texture_staging(rgrid_batch_t *b, size_t pairs)
+{
+    void *dv = nullptr;
+    if (!b->d_tex) {
+        std::vector<unsigned short> t(32768);
+        texture_table(t.data());
+        unsigned short *d = nullptr;
+        G_TRY(b, hipMalloc((void **)&d, 2 * 32768));
+        if (hipMemcpy(d, t.data(), 2 * 32768, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); b->hip_error = "texture table: upload failed"; return RGRID_ERR_HIP; }
+        b->d_tex = d;
+    }
+    if (!b->h_tbox) {
+        b->tsub.resize((size_t)b->max_scans);
+        G_TRY(b, hipHostMalloc((void **)&b->h_tbox, sizeof(int) * 4 * (size_t)b->max_scans, hipHostMallocMapped | hipHostMallocCoherent));
+        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_tbox, 0)); b->dv_tbox = (int *)dv;
+    }
+    if (pairs > b->tout_pairs) {
+        G_TRY(b, hipStreamSynchronize(b->stream));                                 // (nothing is pending: the area is idle)
+        if (b->h_tout) (void)hipHostFree(b->h_tout);
+        b->h_tout = nullptr; b->dv_tout = nullptr; b->tout_pairs = 0;
+        G_TRY(b, hipHostMalloc((void **)&b->h_tout, sizeof(unsigned short) * pairs, hipHostMallocMapped | hipHostMallocCoherent));
+        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_tout, 0)); b->dv_tout = (unsigned short *)dv;
+        b->tout_pairs = pairs;
+    }
+    return RGRID_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -994,6 +1142,9 @@ void rgrid_batch_destroy(rgrid_batch_t *b)
     if (b->h_fin) { if (b->fin_in_vram) (void)hipFree(b->h_fin); else (void)hipHostFree(b->h_fin); }
     if (b->h_fout) (void)hipHostFree(b->h_fout);
     if (b->h_fcnt) (void)hipHostFree(b->h_fcnt);
+    (void)hipFree(b->d_tex);
+    if (b->h_tout) (void)hipHostFree(b->h_tout);
+    if (b->h_tbox) (void)hipHostFree(b->h_tbox);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -1407,6 +1558,72 @@ int rgrid_batch_filter_collect(rgrid_batch_t *b, int *status, int *counts, float
             dst += 2 * k;
         }
     }
+    return RGRID_OK;
+}
+
+int rgrid_batch_texture_submit(rgrid_batch_t *b, const int *grids, int count)
+{
+    if (!b || count < 0 || count > b->max_scans || (count > 0 && !grids) || b->outstanding) return RGRID_ERR_INVALID;
+    size_t pairs = 0;
+    for (int j = 0; j < count; ++j) {
+        if (grids[j] < 0 || grids[j] >= b->num_grids || !b->grids[(size_t)grids[j]].set) return RGRID_ERR_INVALID;
+        const GridSlot &g = b->grids[(size_t)grids[j]];
+        pairs += align_up((size_t)g.nx * (size_t)g.ny, 8);                          // every region starts on a 16-byte boundary
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    b->sub_count = count;
+    if (count == 0) {
+        b->outstanding = true; b->kind = KIND_TEXTURE;
+        b->prepare_seconds = seconds_since(t_begin);
+        return RGRID_OK;
+    }
+    G_TRY(b, hipSetDevice(b->device));
+    const int rc = texture_staging(b, pairs);
+    if (rc != RGRID_OK) return rc;
+    const int k = (int)(b->n_submit++ % KGB_SEGMENTS);
+    TextureRec *recs = reinterpret_cast<TextureRec *>(b->pack.data());
+    long long at = 0;
+    for (int j = 0; j < count; ++j) {
+        const GridSlot &g = b->grids[(size_t)grids[j]];
+        TextureRec &R = recs[j];
+        R.cells_off = (long long)grids[j] * (long long)b->max_cells;
+        R.out_off = at; R.nx = g.nx; R.ny = g.ny;
+        b->tsub[(size_t)j] = TexturePending{grids[j], at};
+        at += (long long)align_up((size_t)g.nx * (size_t)g.ny, 8);
+    }
+    std::memcpy(b->h_seg[k], recs, sizeof(TextureRec) * (size_t)count);
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
+    b->prepare_seconds = seconds_since(t_begin);
+    TextureBufs Tf;
+    Tf.seg = b->dv_seg[k]; Tf.cells = b->d_cells; Tf.table = b->d_tex; Tf.out = b->dv_tout; Tf.box = b->dv_tbox;
+    hipLaunchKernelGGL(kgb_texture, dim3((unsigned)count), dim3(KGT_THREADS), 0, b->stream, Tf);
+    G_TRY(b, hipGetLastError());
+    b->outstanding = true; b->kind = KIND_TEXTURE;
+    return RGRID_OK;
+}
+
+int rgrid_batch_texture_collect(rgrid_batch_t *b, int *boxes, double *slice_max, long *offsets, uint8_t *cells, long cap)
+{
+    if (!b || !b->outstanding || b->kind != KIND_TEXTURE) return RGRID_ERR_INVALID;
+    const int count = b->sub_count;
+    if (count > 0 && (!boxes || !slice_max || !offsets)) return RGRID_ERR_INVALID;
+    G_TRY(b, hipSetDevice(b->device));
+    G_TRY(b, hipStreamSynchronize(b->stream));                // the one wait: the kernel wrote boxes and pairs into host memory
+    long total = 0;
+    for (int j = 0; j < count; ++j) {
+        const GridSlot &g = b->grids[(size_t)b->tsub[(size_t)j].grid];
+        const int *box = b->h_tbox + 4 * j;
+        const int x0 = box[0], y0 = box[1];
+        for (int c = 0; c < 4; ++c) boxes[4 * j + c] = box[c];
+        slice_max[2 * j] = g.max_x - g.resolution * y0;                             // (probability_grid.cc:122-123), rgrid_draw_texture's expressions
+        slice_max[2 * j + 1] = g.max_y - g.resolution * x0;
+        offsets[j] = total;
+        total += 2l * box[2] * box[3];
+    }
+    if (total > cap || (total > 0 && !cells)) return RGRID_ERR_BUFFER;             // the submit stays pending: come again with room
+    b->outstanding = false;
+    for (int j = 0; j < count; ++j)
+        std::memcpy(cells + offsets[j], b->h_tout + b->tsub[(size_t)j].out_off, 2 * (size_t)boxes[4 * j + 2] * (size_t)boxes[4 * j + 3]);
     return RGRID_OK;
 }
 

@@ -26,6 +26,12 @@ into such scans), ONE launch of kgb_filter (one workgroup per scan) and one wait
 voxel-filtered clouds and the adaptively filtered returns, the bits of ``GridFrontEnd.VoxelFilter`` (twice) and
 ``GridFrontEnd.AdaptiveVoxelFilter``.  It needs no grid.
 
+The way out of the mapper, ``MapBuilder::ToSubmapTexture`` (map_builder.cc:128-134), is ``draw_textures(slots)``: ONE launch of
+kgb_texture (one workgroup per named slot) and one wait turn resident slots into what the reference publishes -- per slot a
+``FleetTexture`` with the ``(cells, box, slice_max)`` that ``GridFrontEnd.DrawTexture`` returns for the same grid, byte for byte;
+``submap_textures(slots, submap_origins)`` gives the reference's ``SubmapTexture`` fields as ``MapBuilder.ToSubmapTexture`` does.
+The slots are only read and stay on the device.
+
 All arithmetic happens in the HIP kernel behind librgrid.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -89,6 +95,19 @@ class FleetFilterResult:
 
 
 @dataclass
+class FleetTexture:
+    """ProbabilityGrid::DrawToSubmapTexture of one slot, the three things ``GridFrontEnd.DrawTexture`` returns (and unpacks like
+    them): ``cells`` uint8 (height, width, 2) = (value, alpha) per cell of the known-cells box, ``box`` = (offset_x, offset_y,
+    width, height), ``slice_max`` = (x, y)."""
+    cells: np.ndarray
+    box: tuple
+    slice_max: tuple
+
+    def __iter__(self):
+        return iter((self.cells, self.box, self.slice_max))
+
+
+@dataclass
 class FleetMatchResult(MatchResult):
     status: int = 0                  # RGRID_OK, or the scan's own error: -6 empty cloud, -4 more points / rotated scans than the handle holds
 
@@ -117,6 +136,7 @@ _ready = None
 _refine_ready = None
 _insert_ready = None
 _filter_ready = None
+_texture_ready = None
 
 
 def _batch_lib():
@@ -221,6 +241,24 @@ def _filter_lib():
     return L
 
 
+def _texture_lib():
+    """``_batch_lib()`` with the argtypes of the texture calls set.  Raises LibraryMissing when the built library has no such calls
+    (they are looked up by name); every other call keeps working then."""
+    global _texture_ready
+    if _texture_ready is not None:
+        return _texture_ready
+    L = _batch_lib()
+    names = ("rgrid_batch_texture_submit", "rgrid_batch_texture_collect")
+    missing = [n for n in names if not hasattr(L, n)]
+    if missing:
+        raise _lib.LibraryMissing(f"librgrid.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
+    vp = C.c_void_p
+    L.rgrid_batch_texture_submit.argtypes = [vp, vp, C.c_int]
+    L.rgrid_batch_texture_collect.argtypes = [vp, vp, vp, vp, vp, C.c_long]
+    _texture_ready = L
+    return L
+
+
 def filter_max_points() -> int:
     """Points per cloud one workgroup of kgb_filter holds (rgrid_batch_filter_max_points)."""
     return int(_filter_lib().rgrid_batch_filter_max_points())
@@ -287,6 +325,7 @@ class ScanMatchFleet:
         self._h = h
         self.max_scans, self.max_points, self.num_grids = int(max_scans), int(max_points), int(num_grids)
         self._pending = None          # the submit that has not been collected: its scan count
+        self._set_slots = set()       # the slots SetGrid has filled: what draw_textures draws by default
 
     # -- lifetime -----------------------------------------------------------
     def close(self):
@@ -310,8 +349,11 @@ class ScanMatchFleet:
         g = np.ascontiguousarray(cells, dtype=np.uint16)
         if g.ndim != 2:
             raise ValueError("cells is a (num_y_cells, num_x_cells) array")
-        return self._L.rgrid_batch_set_grid(self._h, int(slot), g.ctypes.data, g.shape[1], g.shape[0], float(resolution),
-                                            float(max_xy[0]), float(max_xy[1]))
+        rc = self._L.rgrid_batch_set_grid(self._h, int(slot), g.ctypes.data, g.shape[1], g.shape[0], float(resolution),
+                                          float(max_xy[0]), float(max_xy[1]))
+        if rc == 0:
+            self._set_slots.add(int(slot))
+        return rc
 
     def SetGrid(self, slot: int, cells, resolution: float, max_xy):
         """``GridFrontEnd.SetGrid`` for grid slot ``slot``: uint16 (num_y_cells, num_x_cells) correspondence-cost values,
@@ -598,6 +640,80 @@ class ScanMatchFleet:
     def filter(self, scans, voxel_filter_size: float = 0.025, options: AdaptiveVoxelFilterOptions | None = None):
         self.submit_filter(scans, voxel_filter_size, options)
         return self.collect_filter()
+
+    # -- MapBuilder::ToSubmapTexture for a batch: the known-cells box and its (value, alpha) bytes of every named slot ---
+    def set_slots(self):
+        """The slots that have been set, in ascending order."""
+        return sorted(getattr(self, "_set_slots", ()))
+
+    def submit_texture_code(self, slots) -> int:
+        """-> the code of rgrid_batch_texture_submit for the named slots (any order, a slot any number of times)."""
+        L = _texture_lib()
+        ids = np.ascontiguousarray([int(k) for k in slots], dtype=np.int32)
+        room = 0                                                                   # what collect's buffer must hold at most
+        for k in ids:
+            rc, lim = self.GetLimits_code(int(k)) if 0 <= k < self.num_grids else (RGRID_ERR_INVALID, None)
+            room += 2 * lim[0] * lim[1] if rc == 0 else 0
+        rc = L.rgrid_batch_texture_submit(self._h, ids.ctypes.data if ids.size else None, int(ids.size))
+        if rc == 0:
+            self._pending = int(ids.size)
+            self._texture_room = room
+        return rc
+
+    def submit_texture(self, slots):
+        """ONE launch of kgb_texture, one workgroup per named slot; returns without waiting.  The slots are only read."""
+        self._chk(self.submit_texture_code(slots), "rgrid_batch_texture_submit")
+
+    def collect_texture_code(self, cap: int | None = None):
+        """-> (rc, [FleetTexture]) of the texture submit that has not been collected.  ``cap`` (default: what always suffices, from
+        the slots' limits) is the room offered for the bytes: when it is too small the answer is (RGRID_ERR_BUFFER, [(box,
+        slice_max, offset) per slot]) and the submit stays pending."""
+        L = _texture_lib()
+        count = self._pending or 0
+        n = max(count, 1)
+        room = int(getattr(self, "_texture_room", 0) if cap is None else cap)
+        boxes, sm, offs = np.zeros((n, 4), np.int32), np.zeros((n, 2)), np.zeros(n, dtype=C.c_long)
+        out = np.empty(max(room, 1), np.uint8)
+        rc = L.rgrid_batch_texture_collect(self._h, boxes.ctypes.data, sm.ctypes.data, offs.ctypes.data, out.ctypes.data, room)
+        if rc == RGRID_ERR_BUFFER:
+            return rc, [(tuple(int(v) for v in boxes[i]), (float(sm[i, 0]), float(sm[i, 1])), int(offs[i])) for i in range(count)]
+        if rc != 0:
+            return rc, []
+        self._pending = None
+        results = []
+        for i in range(count):
+            w, h, at = int(boxes[i, 2]), int(boxes[i, 3]), int(offs[i])
+            # (a view: the textures of a call share the one buffer the library filled, and nothing else holds it)
+            results.append(FleetTexture(out[at:at + 2 * w * h].reshape(h, w, 2), tuple(int(v) for v in boxes[i]),
+                                        (float(sm[i, 0]), float(sm[i, 1]))))
+        return 0, results
+
+    def collect_texture(self, cap: int | None = None):
+        """Waits for the launch: one FleetTexture per named slot, in order."""
+        rc, out = self.collect_texture_code(cap)
+        self._chk(rc, "rgrid_batch_texture_collect")
+        return out
+
+    def draw_textures(self, slots=None):
+        """``GridFrontEnd.DrawTexture`` of every named slot (default: every slot that has been set) in ONE launch: a list of
+        FleetTexture, in the order named."""
+        self.submit_texture(self.set_slots() if slots is None else slots)
+        return self.collect_texture()
+
+    def submap_textures(self, slots, submap_origins):
+        """``MapBuilder.ToSubmapTexture`` per named slot: a dict with the reference's SubmapTexture fields (grid_2d.h:16-24) --
+        ``cells`` the raw (value, alpha) bytes, ``width``, ``height``, ``resolution``, ``slice_pose`` and ``global_pose`` as (x, y)
+        translations.  ``submap_origins[i]`` is the local_pose translation of the submap in ``slots[i]`` (submap_2d.cc:18-24)."""
+        slots = [int(k) for k in slots]
+        origins = [(float(o[0]), float(o[1])) for o in submap_origins]
+        if len(origins) != len(slots):
+            raise ValueError("one submap origin per named slot")
+        resolutions = [self.GetLimits(k)[2] for k in slots]
+        out = []
+        for tex, resolution, (ox, oy) in zip(self.draw_textures(slots), resolutions, origins):
+            out.append({"cells": tex.cells, "width": tex.box[2], "height": tex.box[3], "resolution": resolution,
+                        "slice_pose": (tex.slice_max[0] - ox, tex.slice_max[1] - oy), "global_pose": (ox, oy)})
+        return out
 
     def GetLimits_code(self, slot: int):
         nx, ny = C.c_int(), C.c_int()
