@@ -1,0 +1,52 @@
+// batch_host.h -- the two kinds of buffer a fleet handle shares with the device.  Each knows how its memory was taken: what
+// alloc() took, release() gives back the same way, and release() of an empty buffer does nothing.  Plain aggregates: a handle
+// holds them by value and releases them when it is destroyed; nothing copies them.
+#pragma once
+#include "host_visible.h"
+
+#include <hip/hip_runtime.h>
+
+namespace batch_host {
+namespace {   // (a handle's translation unit exports its C functions and nothing else)
+
+// n elements of pinned host memory, mapped and coherent: the host reads and writes `h`, the device `dv`, both in place
+template <typename T>
+struct Pinned {
+    T *h = nullptr, *dv = nullptr;
+    // all or nothing: a buffer whose device pointer cannot be had is given back
+    hipError_t alloc(size_t n)
+    {
+        hipError_t e = hipHostMalloc((void **)&h, sizeof(T) * n, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e != hipSuccess) { h = nullptr; return e; }
+        e = hipHostGetDevicePointer((void **)&dv, h, 0);
+        if (e != hipSuccess) release();
+        return e;
+    }
+    void release()
+    {
+        if (h) (void)hipHostFree(h);
+        h = dv = nullptr;
+    }
+};
+
+// a staging area the host writes and a kernel reads in place: host-visible device memory where the platform gives it
+// (host_visible.h; `in_vram` says so), else pinned host memory
+template <typename T>
+struct Staging : Pinned<T> {
+    bool in_vram = false;
+    hipError_t alloc(size_t n)
+    {
+        this->h = this->dv = static_cast<T *>(host_visible::alloc(sizeof(T) * n));
+        in_vram = this->h != nullptr;
+        return in_vram ? hipSuccess : alloc_pinned(n);
+    }
+    hipError_t alloc_pinned(size_t n) { return Pinned<T>::alloc(n); }
+    void release()
+    {
+        if (in_vram) { (void)hipFree(this->h); this->h = this->dv = nullptr; in_vram = false; }
+        else Pinned<T>::release();
+    }
+};
+
+}  // namespace
+}  // namespace batch_host

@@ -18,7 +18,7 @@
 // limit.  The contributions to the centres (8 B per beam) go to a per-member slice in device memory that only this workgroup
 // touches, ordered by a __syncthreads(); the de-skewed returns go straight to the member's point-cloud buffer, compacted.
 #include "../../include/rdet.h"
-#include "host_visible.h"
+#include "batch_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -528,13 +528,9 @@ struct rdet2d_batch {
     std::vector<rdet2d_batch_member> m;
     // the staging area the host writes and the kernel reads in place: fine-grained DEVICE memory through the PCIe BAR where
     // the platform maps it, else pinned host memory (host_visible.h)
-    float *h_stage = nullptr;          // [B][2][max_beams]
-    const float *dv_stage = nullptr;
-    bool stage_in_vram = false;
-    BatchRec *h_recs = nullptr;        // [B], pinned
-    const BatchRec *dv_recs = nullptr;
-    BatchOut *h_out = nullptr;         // [B], pinned
-    BatchOut *dv_out = nullptr;
+    batch_host::Staging<float> stage;  // [B][2][max_beams]
+    batch_host::Pinned<BatchRec> recs; // [B]
+    batch_host::Pinned<BatchOut> out;  // [B]
     float *h_tables = nullptr;         // pinned image of d_tables
     float *d_tables = nullptr;         // [RDET2DB_TABLES + B][3][max_beams]: the cached tables, then one per member for a call with more lidars than those
     unsigned long long *d_contrib = nullptr;
@@ -602,21 +598,10 @@ int rdet2d_batch_create(const rdet2d_options *opts, const double *s2b_xyyaw, int
     int rc = [&]() -> int {
         DETB_TRY(b, hipSetDevice(device));
         DETB_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-        b->h_stage = (float *)host_visible::alloc(4 * nb * 2 * nB);
-        if (b->h_stage) {
-            b->stage_in_vram = true;
-            b->dv_stage = b->h_stage;
-        } else {
-            void *dv = nullptr;
-            DETB_TRY(b, hipHostMalloc(&b->h_stage, 4 * nb * 2 * nB, hipHostMallocMapped | hipHostMallocCoherent));
-            DETB_TRY(b, hipHostGetDevicePointer(&dv, b->h_stage, 0)); b->dv_stage = (const float *)dv;
-        }
-        void *dv = nullptr;
-        DETB_TRY(b, hipHostMalloc(&b->h_recs, sizeof(BatchRec) * nB, hipHostMallocMapped | hipHostMallocCoherent));
-        DETB_TRY(b, hipHostGetDevicePointer(&dv, b->h_recs, 0)); b->dv_recs = (const BatchRec *)dv;
-        DETB_TRY(b, hipHostMalloc(&b->h_out, sizeof(BatchOut) * nB, hipHostMallocMapped | hipHostMallocCoherent));
-        DETB_TRY(b, hipHostGetDevicePointer(&dv, b->h_out, 0)); b->dv_out = (BatchOut *)dv;
-        std::memset(b->h_out, 0, sizeof(BatchOut) * nB);
+        DETB_TRY(b, b->stage.alloc(nb * 2 * nB));
+        DETB_TRY(b, b->recs.alloc(nB));
+        DETB_TRY(b, b->out.alloc(nB));
+        std::memset(b->out.h, 0, sizeof(BatchOut) * nB);
         DETB_TRY(b, hipHostMalloc(&b->h_tables, 4 * nb * 3 * (RDET2DB_TABLES + nB)));
         DETB_TRY(b, hipMalloc(&b->d_tables, 4 * nb * 3 * (RDET2DB_TABLES + nB)));
         DETB_TRY(b, hipMalloc(&b->d_contrib, 8 * nb * nB));
@@ -634,10 +619,8 @@ void rdet2d_batch_destroy(rdet2d_batch_t *b)
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     (void)hipFree(b->d_tables); (void)hipFree(b->d_contrib); (void)hipFree(b->d_returns);
-    if (b->h_stage) { if (b->stage_in_vram) (void)hipFree(b->h_stage); else (void)hipHostFree(b->h_stage); }
-    if (b->h_recs) (void)hipHostFree(b->h_recs);
-    if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->h_tables) (void)hipHostFree(b->h_tables);
+    b->stage.release(); b->recs.release(); b->out.release();
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -660,7 +643,7 @@ int rdet2d_batch_handle_odometry(rdet2d_batch_t *b, int member, double t, const 
 int rdet2d_batch_staging(rdet2d_batch_t *b, int member, float **ranges, float **intensities)
 {
     if (!b || !ranges || !intensities || member < 0 || member >= b->B) return RDET_ERR_INVALID;
-    *ranges = b->h_stage + (size_t)member * 2 * (size_t)b->max_beams;
+    *ranges = b->stage.h + (size_t)member * 2 * (size_t)b->max_beams;
     *intensities = *ranges + b->max_beams;
     return RDET_OK;
 }
@@ -699,7 +682,7 @@ int rdet2d_batch_submit(rdet2d_batch_t *b, const rdet2d_scan *scans, int count)
     for (int i = 0; i < count; ++i) {
         const rdet2d_scan &s = scans[i];
         rdet2d_batch_member &M = b->m[(size_t)s.member];
-        BatchRec &A = b->h_recs[i];
+        BatchRec &A = b->recs.h[i];
         std::memset(&A, 0, sizeof(A));
         b->sub_member[(size_t)i] = s.member;
         b->sub_stamp[(size_t)i] = s.stamp;                                          // :26 (USE_CORRECT_TIME undefined)
@@ -734,7 +717,7 @@ int rdet2d_batch_submit(rdet2d_batch_t *b, const rdet2d_scan *scans, int count)
         A.n_odom = (int)(M.odom.size() > 2 ? 2 : M.odom.size());
         if (!M.odom.empty()) { A.front = M.odom.front(); A.back = M.odom.back(); }
         // the scan into the member's staging slice, unless it was received there
-        float *sr = b->h_stage + (size_t)s.member * 2 * mb, *si = sr + mb;
+        float *sr = b->stage.h + (size_t)s.member * 2 * mb, *si = sr + mb;
         if (s.ranges != sr) std::memcpy(sr, s.ranges, sizeof(float) * (size_t)N);
         if (s.intensities != si) std::memcpy(si, s.intensities, sizeof(float) * (size_t)N);
         // beam-angle table: the float32 accumulation of :51/:175 and its cos/sin (:68), host libm; one per lidar
@@ -764,12 +747,12 @@ int rdet2d_batch_submit(rdet2d_batch_t *b, const rdet2d_scan *scans, int count)
     if (n_run > 0) {
         __atomic_thread_fence(__ATOMIC_SEQ_CST);              // write-combined stores drained before the doorbell
         BatchBufs Bf;
-        Bf.recs = b->dv_recs; Bf.stage = b->dv_stage; Bf.tables = b->d_tables; Bf.contrib = b->d_contrib;
-        Bf.returns = b->d_returns; Bf.out = b->dv_out; Bf.max_beams = b->max_beams;
+        Bf.recs = b->recs.dv; Bf.stage = b->stage.dv; Bf.tables = b->d_tables; Bf.contrib = b->d_contrib;
+        Bf.returns = b->d_returns; Bf.out = b->out.dv; Bf.max_beams = b->max_beams;
         hipLaunchKernelGGL(k_det2d_batch, dim3((unsigned)count), dim3(1024), 0, b->stream, Bf);
         DETB_TRY(b, hipGetLastError());
     } else {
-        for (int i = 0; i < count; ++i) std::memset(&b->h_out[i], 0, 4 * sizeof(int));
+        for (int i = 0; i < count; ++i) std::memset(&b->out.h[i], 0, 4 * sizeof(int));
     }
     return RDET_OK;
 }
@@ -784,7 +767,7 @@ int rdet2d_batch_collect(rdet2d_batch_t *b, int *status, int *K, float *centers_
     DETB_TRY(b, hipSetDevice(b->device));
     DETB_TRY(b, hipStreamSynchronize(b->stream));
     for (int i = 0; i < count; ++i) {
-        const BatchOut &o = b->h_out[i];
+        const BatchOut &o = b->out.h[i];
         K[i] = 0;
         status[i] = b->sub_status[(size_t)i];
         if (obs_time) obs_time[i] = b->sub_stamp[(size_t)i];

@@ -20,7 +20,7 @@
 // first and only while their box is nearer than the query's current 31st distance (k3_knn's scheme on LDS).  The multiset of the 31
 // smallest distances is exact whatever the boxes are.
 #include "../../include/rdet.h"
-#include "host_visible.h"
+#include "batch_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -467,13 +467,9 @@ struct rdet3d_batch {
     std::vector<rdet3d_batch_member> m;
     // the staging area the host writes and the kernel reads in place: fine-grained DEVICE memory through the PCIe BAR where the platform
     // maps it, else pinned host memory (host_visible.h)
-    float *h_stage = nullptr;          // [B][4 * max_points]
-    const float *dv_stage = nullptr;
-    bool stage_in_vram = false;
-    Cloud3Rec *h_recs = nullptr;       // [B], pinned
-    const Cloud3Rec *dv_recs = nullptr;
-    Cloud3Out *h_out = nullptr;        // [B], pinned
-    Cloud3Out *dv_out = nullptr;
+    batch_host::Staging<float> stage;  // [B][4 * max_points]
+    batch_host::Pinned<Cloud3Rec> recs; // [B]
+    batch_host::Pinned<Cloud3Out> out; // [B]
     // the submit that has not been collected
     bool outstanding = false;
     int sub_count = 0;
@@ -521,21 +517,10 @@ int rdet3d_batch_create(const rdet3d_options *opts, const double *s2b_xyyaw, int
     int rc = [&]() -> int {
         DET3B_TRY(b, hipSetDevice(device));
         DET3B_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-        b->h_stage = (float *)host_visible::alloc(sizeof(float) * 4 * np * nB);
-        if (b->h_stage) {
-            b->stage_in_vram = true;
-            b->dv_stage = b->h_stage;
-        } else {
-            void *dv = nullptr;
-            DET3B_TRY(b, hipHostMalloc(&b->h_stage, sizeof(float) * 4 * np * nB, hipHostMallocMapped | hipHostMallocCoherent));
-            DET3B_TRY(b, hipHostGetDevicePointer(&dv, b->h_stage, 0)); b->dv_stage = (const float *)dv;
-        }
-        void *dv = nullptr;
-        DET3B_TRY(b, hipHostMalloc(&b->h_recs, sizeof(Cloud3Rec) * nB, hipHostMallocMapped | hipHostMallocCoherent));
-        DET3B_TRY(b, hipHostGetDevicePointer(&dv, b->h_recs, 0)); b->dv_recs = (const Cloud3Rec *)dv;
-        DET3B_TRY(b, hipHostMalloc(&b->h_out, sizeof(Cloud3Out) * nB, hipHostMallocMapped | hipHostMallocCoherent));
-        DET3B_TRY(b, hipHostGetDevicePointer(&dv, b->h_out, 0)); b->dv_out = (Cloud3Out *)dv;
-        std::memset(b->h_out, 0, sizeof(Cloud3Out) * nB);
+        DET3B_TRY(b, b->stage.alloc(4 * np * nB));
+        DET3B_TRY(b, b->recs.alloc(nB));
+        DET3B_TRY(b, b->out.alloc(nB));
+        std::memset(b->out.h, 0, sizeof(Cloud3Out) * nB);
         DET3B_TRY(b, hipFuncSetAttribute((const void *)k_det3d_batch, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)(LDS_PER_NODE * RDET3DB_MAX_BRIGHT)));
         return RDET_OK;
@@ -550,9 +535,7 @@ void rdet3d_batch_destroy(rdet3d_batch_t *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->h_stage) { if (b->stage_in_vram) (void)hipFree(b->h_stage); else (void)hipHostFree(b->h_stage); }
-    if (b->h_recs) (void)hipHostFree(b->h_recs);
-    if (b->h_out) (void)hipHostFree(b->h_out);
+    b->stage.release(); b->recs.release(); b->out.release();
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -567,7 +550,7 @@ int rdet3d_batch_set_sensor_to_base_link(rdet3d_batch_t *b, int member, const do
 int rdet3d_batch_staging(rdet3d_batch_t *b, int member, float **xyzi)
 {
     if (!b || !xyzi || member < 0 || member >= b->B) return RDET_ERR_INVALID;
-    *xyzi = b->h_stage + (size_t)member * 4 * (size_t)b->max_points;
+    *xyzi = b->stage.h + (size_t)member * 4 * (size_t)b->max_points;
     return RDET_OK;
 }
 
@@ -598,10 +581,10 @@ int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count
         const rdet3d_batch_member &M = b->m[(size_t)c.member];
         b->sub_stamp[(size_t)i] = c.stamp;                                          // observation.time_ (:97)
         b->sub_runs[(size_t)i] = 0;
-        std::memset(&b->h_out[i], 0, 4 * sizeof(int));
+        std::memset(&b->out.h[i], 0, 4 * sizeof(int));
         if (c.N == 0) continue;                                                     // nothing to detect: no workgroup
         b->sub_runs[(size_t)i] = 1;
-        Cloud3Rec &A = b->h_recs[n_run++];
+        Cloud3Rec &A = b->recs.h[n_run++];
         std::memset(&A, 0, sizeof(A));
         A.intensity_min = M.opt.intensity_min;
         A.stamp = c.stamp;
@@ -610,7 +593,7 @@ int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count
         const float sa = (float)M.s2b[2];
         A.cs = cosf(sa); A.sn = sinf(sa);
         if (c.N > n_max) n_max = c.N;
-        float *dst = b->h_stage + (size_t)c.member * 4 * np;                        // the cloud into the member's slice, unless it was received there
+        float *dst = b->stage.h + (size_t)c.member * 4 * np;                        // the cloud into the member's slice, unless it was received there
         if (c.xyzi != dst) std::memcpy(dst, c.xyzi, sizeof(float) * 4 * (size_t)c.N);
     }
     b->sub_count = count;
@@ -618,7 +601,7 @@ int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count
     if (n_run > 0) {
         __atomic_thread_fence(__ATOMIC_SEQ_CST);              // write-combined stores drained before the doorbell
         Batch3Bufs Bf;
-        Bf.recs = b->dv_recs; Bf.stage = b->dv_stage; Bf.out = b->dv_out; Bf.max_points = b->max_points;
+        Bf.recs = b->recs.dv; Bf.stage = b->stage.dv; Bf.out = b->out.dv; Bf.max_points = b->max_points;
         int cap = (n_max + TILE - 1) / TILE * TILE;           // no cloud of this call has more survivors than points
         if (cap > RDET3DB_MAX_BRIGHT) cap = RDET3DB_MAX_BRIGHT;
         Bf.cap = cap;
@@ -638,7 +621,7 @@ int rdet3d_batch_collect(rdet3d_batch_t *b, int *status, int *K, float *centers_
     DET3B_TRY(b, hipSetDevice(b->device));
     DET3B_TRY(b, hipStreamSynchronize(b->stream));
     for (int i = 0; i < count; ++i) {
-        const Cloud3Out &o = b->h_out[i];
+        const Cloud3Out &o = b->out.h[i];
         K[i] = 0;
         status[i] = RDET_OK;
         if (obs_time) obs_time[i] = b->sub_stamp[(size_t)i];

@@ -26,7 +26,7 @@
 // directly where the platform maps it, else pinned host memory (host_visible.h).  Results land in pinned host memory, a slot
 // per scan, published by the end of the launch.
 #include "../../include/rgrid.h"
-#include "host_visible.h"
+#include "batch_host.h"
 #include "rgrid_dev.h"
 #include "rgrid_refine_dev.h"
 
@@ -826,43 +826,52 @@ struct rgrid_batch {
     long max_cells = 0;
     int mode = RGRID_BATCH_REDUCE_ARRIVAL;
     hipStream_t stream = nullptr;
-    // staging segments the kernels read in place
-    unsigned char *h_seg[KGB_SEGMENTS] = {nullptr, nullptr};
-    const unsigned char *dv_seg[KGB_SEGMENTS] = {nullptr, nullptr};
-    bool seg_in_vram = false;
-    size_t seg_bytes = 0, wgmap_off = 0, f2_off = 0, rrec_off = 0, raw_off = 0;
-    std::vector<unsigned char> pack;       // the segment's image in ordinary memory (rotated points are read back while packing)
-    unsigned long long n_submit = 0;
+    // the staging segments the kernels read in place, used in turn, and a segment's image in ordinary memory (rotated points are
+    // read back while packing)
+    struct {
+        batch_host::Staging<unsigned char> buf[KGB_SEGMENTS];
+        size_t wgmap_off = 0, f2_off = 0, rrec_off = 0, raw_off = 0;
+        std::vector<unsigned char> pack;
+        unsigned long long n_taken = 0;
+    } seg;
     unsigned short *d_cells = nullptr;     // grid pool
-    unsigned long long *d_bb = nullptr;
-    int *d_arrived = nullptr;
-    BestRec *h_out = nullptr, *dv_out = nullptr;
-    RefineOut *h_rout = nullptr, *dv_rout = nullptr;
-    // the inserter: the two lookup tables (uint16[32768] each) and the probabilities they were built for, a flag per record
-    unsigned short *d_hit = nullptr, *d_miss = nullptr;
-    float tab_hit_p = -1.f, tab_miss_p = -1.f;
-    int *h_bad = nullptr, *dv_bad = nullptr;
-    std::vector<unsigned long long> slot_call;   // the insert submit that named a slot last (a call names a slot once)
-    unsigned long long n_insert = 0;
-    // the filter: its own staging, allocated by the first filter submit -- records and input points the kernel reads in place
-    // (host-visible device memory, else pinned host memory), output points and counts in pinned host memory
-    unsigned char *h_fin = nullptr;
-    const unsigned char *dv_fin = nullptr;
-    bool fin_in_vram = false;
-    size_t fpts_off = 0;
-    float2 *h_fout = nullptr, *dv_fout = nullptr;
-    int *h_fcnt = nullptr, *dv_fcnt = nullptr;
-    std::vector<FilterPending> fsub;
-    // the texture: the (value, alpha) table (uint16[32768]) on the device, uploaded by the first texture submit; the output area
-    // and the box records in pinned host memory, allocated by the first texture submit and grown only when a call needs more
-    unsigned short *d_tex = nullptr;
-    unsigned short *h_tout = nullptr, *dv_tout = nullptr;
-    size_t tout_pairs = 0;
-    int *h_tbox = nullptr, *dv_tbox = nullptr;
-    std::vector<TexturePending> tsub;
     std::vector<GridSlot> grids;
+    // the matcher and the refinement: a result slot per scan
+    struct {
+        unsigned long long *d_bb = nullptr;
+        int *d_arrived = nullptr;
+        batch_host::Pinned<BestRec> best;
+        batch_host::Pinned<RefineOut> fine;
+    } res;
+    // the inserter: the two lookup tables (uint16[32768] each) and the probabilities they were built for, a flag per record
+    struct {
+        unsigned short *d_hit = nullptr, *d_miss = nullptr;
+        float tab_hit_p = -1.f, tab_miss_p = -1.f;
+        batch_host::Pinned<int> bad;
+        std::vector<unsigned long long> slot_call;   // the insert submit that named a slot last (a call names a slot once)
+        unsigned long long n_calls = 0;
+    } ins;
+    // the filter: its own staging, allocated by the first filter submit (filter_staging) -- records and input points the kernel
+    // reads in place, output points and counts
+    struct {
+        batch_host::Staging<unsigned char> in;
+        size_t pts_off = 0;
+        batch_host::Pinned<float2> out;
+        batch_host::Pinned<int> cnt;         // allocated last: it marks the staging as complete
+        std::vector<FilterPending> sub;
+    } fil;
+    // the texture (texture_staging): the (value, alpha) table (uint16[32768]) on the device, uploaded by the first texture submit;
+    // the output area and the box records, allocated by the first texture submit, the area grown only when a call needs more
+    struct {
+        unsigned short *d_table = nullptr;
+        batch_host::Pinned<unsigned short> out;
+        size_t out_pairs = 0;
+        batch_host::Pinned<int> box;
+        std::vector<TexturePending> sub;
+    } tex;
+    // the submit that has not been collected
     bool outstanding = false;
-    int kind = 0;                          // KIND_* of the outstanding submit
+    int kind = 0;                          // its KIND_*
     int sub_count = 0;
     std::vector<Pending> sub;
     double prepare_seconds = 0.;
@@ -871,31 +880,90 @@ struct rgrid_batch {
 
 namespace {
 
+bool slot_ok(const rgrid_batch_t *b, int grid) { return grid >= 0 && grid < b->num_grids && b->grids[(size_t)grid].set; }
+
+// a slot's first cell in the grid pool
+long long cells_offset(const rgrid_batch_t *b, int grid) { return (long long)grid * (long long)b->max_cells; }
+
+// one cloud of a scan of a match or a refine submit, into a set slot
+bool cloud_ok(const rgrid_batch_t *b, int grid, const float *points_xy, int n) { return slot_ok(b, grid) && n >= 0 && (n == 0 || points_xy); }
+
+// the two clouds of a scan of an insert or a filter submit
+bool two_clouds_ok(const float *returns_xy, int n_returns, const float *misses_xy, int n_misses)
+{
+    return n_returns >= 0 && n_misses >= 0 && (n_returns == 0 || returns_xy) && (n_misses == 0 || misses_xy);
+}
+
+// The segments are used in turn, and the turn passes once per launch that reads one.  next_segment is the one that launch will read
+// (a submit may write points straight into it before it knows whether it has anything to launch); take_segment is next_segment for
+// a submit that does launch.
+int next_segment(const rgrid_batch_t *b) { return (int)(b->seg.n_taken % KGB_SEGMENTS); }
+int take_segment(rgrid_batch_t *b) { return (int)(b->seg.n_taken++ % KGB_SEGMENTS); }
+
+double seconds_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
+
+// The end of every submit, after the caller has packed `count` scans into `nrec` records and staged them.  A submit without a
+// record launches nothing and is pending all the same: its collect gives the per-scan statuses.  A launch that fails leaves
+// nothing pending.
+template <typename Launch>
+int submit_tail(rgrid_batch_t *b, int kind, int count, int nrec, std::chrono::steady_clock::time_point t_begin, Launch launch)
+{
+    b->sub_count = count;
+    if (nrec > 0) __atomic_thread_fence(__ATOMIC_SEQ_CST);      // write-combined stores drained before the doorbell
+    b->prepare_seconds = seconds_since(t_begin);
+    if (nrec > 0) {
+        launch();
+        G_TRY(b, hipGetLastError());
+    }
+    b->outstanding = true; b->kind = kind;
+    return RGRID_OK;
+}
+
+// The start of every collect: the pending submit is of `kind` and, unless it had no scans, the caller has its required outputs;
+// gives its scan count and waits for the launch.  With clear_first nothing is pending from here on, a HIP error in the wait
+// included; without, the caller clears `outstanding` itself once it knows the results fit (RGRID_ERR_BUFFER leaves the submit
+// pending, and the next collect waits again).
+int collect_head(rgrid_batch_t *b, int kind, bool outputs, bool clear_first, int *count)
+{
+    if (!b || !b->outstanding || b->kind != kind) return RGRID_ERR_INVALID;
+    *count = b->sub_count;
+    if (*count > 0 && !outputs) return RGRID_ERR_INVALID;
+    if (clear_first) b->outstanding = false;
+    G_TRY(b, hipSetDevice(b->device));
+    G_TRY(b, hipStreamSynchronize(b->stream));
+    return RGRID_OK;
+}
+
+// scan j's entry for collect, zeroed and without a record
+Pending &fresh_pending(rgrid_batch_t *b, int j)
+{
+    Pending &P = b->sub[(size_t)j];
+    std::memset(&P, 0, sizeof(P));
+    P.rec = -1;
+    return P;
+}
+
 // the whole-call conditions on the scans of a match (or match-plus-refine) submit
 bool match_scans_ok(const rgrid_batch_t *b, const rgrid_batch_scan *scans, int count)
 {
-    for (int j = 0; j < count; ++j) {
-        const rgrid_batch_scan &s = scans[j];
-        if (s.grid < 0 || s.grid >= b->num_grids || !b->grids[(size_t)s.grid].set || s.n < 0 || (s.n > 0 && !s.points_xy)) return false;
-    }
+    for (int j = 0; j < count; ++j)
+        if (!cloud_ok(b, scans[j].grid, scans[j].points_xy, scans[j].n)) return false;
     return true;
 }
 
-// Plans every scan of a match into b->sub and the segment's image b->pack: records, workgroup map, rotated points, rotation tables
+// Plans every scan of a match into b->sub and the segment's image: records, workgroup map, rotated points, rotation tables
 MatchWork pack_match(rgrid_batch_t *b, const rgrid_match_options *opt, const rgrid_batch_scan *scans, int count)
 {
 #pragma clang fp contract(off)
     const int rot_cap = b->max_rotations < KGB_MAX_ROT ? b->max_rotations : KGB_MAX_ROT;
-    BatchRec *recs = reinterpret_cast<BatchRec *>(b->pack.data());
-    int2 *wgmap = reinterpret_cast<int2 *>(b->pack.data() + b->wgmap_off);
-    float *f2 = reinterpret_cast<float *>(b->pack.data() + b->f2_off);
+    BatchRec *recs = reinterpret_cast<BatchRec *>(b->seg.pack.data());
+    int2 *wgmap = reinterpret_cast<int2 *>(b->seg.pack.data() + b->seg.wgmap_off);
+    float *f2 = reinterpret_cast<float *>(b->seg.pack.data() + b->seg.f2_off);
     int nrec = 0, nwg = 0, nf2 = 0, n_max = 0;
     for (int j = 0; j < count; ++j) {
         const rgrid_batch_scan &s = scans[j];
         const GridSlot &g = b->grids[(size_t)s.grid];
-        Pending &P = b->sub[(size_t)j];
-        std::memset(&P, 0, sizeof(P));
-        P.rec = -1;
+        Pending &P = fresh_pending(b, j);
         if (s.n == 0) { P.status = RGRID_ERR_EMPTY; continue; }
         if (s.n > b->max_points || b->max_rotations > KGB_MAX_ROT) { P.status = RGRID_ERR_CAPACITY; continue; }
         const int n = s.n;
@@ -916,7 +984,7 @@ MatchWork pack_match(rgrid_batch_t *b, const rgrid_match_options *opt, const rgr
         A.resolution = M.res; A.max_x = g.max_x; A.max_y = g.max_y;
         A.num_angular_d = (double)M.num_angular; A.step = M.step;
         A.wt = opt->translation_delta_cost_weight; A.wr = opt->rotation_delta_cost_weight;
-        A.cells_off = (long long)s.grid * (long long)b->max_cells;
+        A.cells_off = cells_offset(b, s.grid);
         A.n = n; A.num_scans = num_scans; A.num_linear = M.num_linear; A.nx = g.nx; A.ny = g.ny;
         A.pts_off = pts_off; A.cs_off = cs_off;
         A.tx = (float)s.initial_pose[0]; A.ty = (float)s.initial_pose[1];
@@ -933,16 +1001,18 @@ MatchWork pack_match(rgrid_batch_t *b, const rgrid_match_options *opt, const rgr
 // the match's image into segment k: three forward copies, nothing is read back from it
 void stage_match(rgrid_batch_t *b, int k, const MatchWork &W)
 {
-    std::memcpy(b->h_seg[k], b->pack.data(), sizeof(BatchRec) * (size_t)W.nrec);
-    std::memcpy(b->h_seg[k] + b->wgmap_off, b->pack.data() + b->wgmap_off, sizeof(int2) * (size_t)W.nwg);
-    std::memcpy(b->h_seg[k] + b->f2_off, b->pack.data() + b->f2_off, sizeof(float2) * (size_t)W.nf2);
+    unsigned char *to = b->seg.buf[k].h;
+    const unsigned char *from = b->seg.pack.data();
+    std::memcpy(to, from, sizeof(BatchRec) * (size_t)W.nrec);
+    std::memcpy(to + b->seg.wgmap_off, from + b->seg.wgmap_off, sizeof(int2) * (size_t)W.nwg);
+    std::memcpy(to + b->seg.f2_off, from + b->seg.f2_off, sizeof(float2) * (size_t)W.nf2);
 }
 
 void launch_match(rgrid_batch_t *b, int k, const MatchWork &W)
 {
     BatchBufs Bf;
-    Bf.seg = b->dv_seg[k]; Bf.wgmap_off = (int)b->wgmap_off; Bf.f2_off = (int)b->f2_off;
-    Bf.cells = b->d_cells; Bf.bb = b->d_bb; Bf.arrived = b->d_arrived; Bf.out = b->dv_out;
+    Bf.seg = b->seg.buf[k].dv; Bf.wgmap_off = (int)b->seg.wgmap_off; Bf.f2_off = (int)b->seg.f2_off;
+    Bf.cells = b->d_cells; Bf.bb = b->res.d_bb; Bf.arrived = b->res.d_arrived; Bf.out = b->res.best.dv;
     Bf.max_rotations = b->max_rotations < KGB_MAX_ROT ? b->max_rotations : KGB_MAX_ROT;
     const size_t lds = sizeof(int2) * (size_t)((W.n_max + KGB_PF - 1) / KGB_PF * KGB_PF);
     if (b->mode == RGRID_BATCH_REDUCE_ARRIVAL) {
@@ -953,19 +1023,45 @@ void launch_match(rgrid_batch_t *b, int k, const MatchWork &W)
     }
 }
 
+// Refine record `rec` of a call that launches from segment k: everything but the start pose (or the plan it is decoded with) and
+// match_rec, which the caller fills in.  The record goes into the segment's image, the raw points forward, straight into the segment
+// at point `nraw`; `threads` becomes the largest scan's thread count.
+RefineRec &pack_refine(rgrid_batch_t *b, int k, int rec, const rgrid_refine_options *opt, int grid, const float *points_xy, int n, int &nraw, int &threads)
+{
+    RefineRec &R = reinterpret_cast<RefineRec *>(b->seg.pack.data() + b->seg.rrec_off)[rec];
+    std::memset(&R, 0, sizeof(R));
+    refine_args(R.A, b->grids[(size_t)grid], opt, n);
+    R.cells_off = cells_offset(b, grid);
+    R.pts_off = nraw;
+    std::memcpy(reinterpret_cast<float *>(b->seg.buf[k].h + b->seg.raw_off) + 2 * (size_t)nraw, points_xy, sizeof(float) * 2 * (size_t)n);
+    nraw += n;
+    if (refine_threads(n) > threads) threads = refine_threads(n);
+    return R;
+}
+
 // one workgroup per refine record of segment k, `threads` = the largest scan's thread count
 void launch_refine(rgrid_batch_t *b, int k, int nrec, int threads)
 {
     RefineBufs Rf;
-    Rf.seg = b->dv_seg[k]; Rf.rrec_off = (int)b->rrec_off; Rf.raw_off = (int)b->raw_off;
-    Rf.cells = b->d_cells; Rf.best = b->dv_out; Rf.out = b->dv_rout;
+    Rf.seg = b->seg.buf[k].dv; Rf.rrec_off = (int)b->seg.rrec_off; Rf.raw_off = (int)b->seg.raw_off;
+    Rf.cells = b->d_cells; Rf.best = b->res.best.dv; Rf.out = b->res.fine.dv;
     hipLaunchKernelGGL(kgb_refine, dim3((unsigned)nrec), dim3((unsigned)threads), 0, b->stream, Rf);
 }
 
-double seconds_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
-
 void zero3(double *p) { p[0] = p[1] = p[2] = 0.; }
 void zero3(int *p) { if (p) p[0] = p[1] = p[2] = 0; }
+
+// scan j's match outputs from its result record (all zero when it had none); best3 and info3 may be absent
+void match_result(const rgrid_batch_t *b, int j, double *poses, double *scores, int *best3, int *info3)
+{
+    const Pending &P = b->sub[(size_t)j];
+    int *best = best3 ? &best3[3 * j] : nullptr, *info = info3 ? &info3[3 * j] : nullptr;
+    zero3(&poses[3 * j]);
+    scores[j] = 0.;
+    zero3(best);
+    zero3(info);
+    if (P.status == RGRID_OK) decode_best(P.plan, P.pose, b->res.best.h[P.rec], &poses[3 * j], &scores[j], best, info);
+}
 
 // a scan's refine outputs from its result record (all zero when it had none)
 void refine_result(const rgrid_batch_t *b, const Pending &P, double *pose, rgrid_refine_summary *summary)
@@ -973,9 +1069,48 @@ void refine_result(const rgrid_batch_t *b, const Pending &P, double *pose, rgrid
     zero3(pose);
     if (summary) std::memset(summary, 0, sizeof(*summary));
     if (P.status != RGRID_OK) return;
-    const RefineOut &o = b->h_rout[P.rec];
+    const RefineOut &o = b->res.fine.h[P.rec];
     pose[0] = o.pose[0]; pose[1] = o.pose[1]; pose[2] = o.pose[2];
     if (summary) { summary->initial_cost = o.initial_cost; summary->final_cost = o.final_cost; summary->iterations = o.iterations; summary->termination = o.termination; }
+}
+
+// Plans every scan of an insert into b->sub, the slots' limits and the segment's image; the points go forward, straight into
+// segment k.  Gives the number of records.
+int pack_insert(rgrid_batch_t *b, int k, const rgrid_batch_insert_scan *scans, int count)
+{
+    InsertRec *recs = reinterpret_cast<InsertRec *>(b->seg.pack.data());
+    float *ret = reinterpret_cast<float *>(b->seg.buf[k].h + b->seg.f2_off), *mis = reinterpret_cast<float *>(b->seg.buf[k].h + b->seg.raw_off);
+    int nrec = 0, nret = 0, nmis = 0;
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_insert_scan &s = scans[j];
+        GridSlot &g = b->grids[(size_t)s.grid];
+        Pending &P = fresh_pending(b, j);
+        // rgrid_grow_as_needed: on the host, from the points that are copied anyway; the move itself is the workgroup's first phase
+        int nx = g.nx, ny = g.ny, off_x = 0, off_y = 0;
+        double max_x = g.max_x, max_y = g.max_y;
+        P.status = plan_growth(s.origin_xy, s.returns_xy, s.n_returns, s.misses_xy, s.n_misses, g.resolution, (long long)b->max_cells, nx, ny,
+                               max_x, max_y, off_x, off_y);
+        if (P.status != RGRID_OK) continue;                                        // the slot stays as it is
+        // rgrid_insert: more points than the handle stages.  The pair has grown the grid by then, so this scan's workgroup grows it too
+        const bool fits = s.n_returns <= b->max_points && s.n_misses <= b->max_points;
+        if (!fits) P.status = RGRID_ERR_CAPACITY;
+        if (!fits && nx == g.nx && ny == g.ny) continue;
+        InsertRec &R = recs[nrec];
+        std::memset(&R, 0, sizeof(R));
+        R.A.nx = nx; R.A.ny = ny; R.A.n_ret = fits ? s.n_returns : 0; R.A.n_miss = fits ? s.n_misses : 0;
+        R.A.max_x = max_x; R.A.max_y = max_y; R.A.rs = g.resolution / SUBPX;
+        R.A.ox = s.origin_xy[0]; R.A.oy = s.origin_xy[1];
+        R.cells_off = cells_offset(b, s.grid);
+        R.old_nx = g.nx; R.old_ny = g.ny; R.off_x = off_x; R.off_y = off_y;
+        R.ret_off = nret; R.mis_off = nmis;
+        if (R.A.n_ret > 0) std::memcpy(ret + 2 * (size_t)nret, s.returns_xy, sizeof(float) * 2 * (size_t)R.A.n_ret);   // forward, straight into the segment
+        if (R.A.n_miss > 0) std::memcpy(mis + 2 * (size_t)nmis, s.misses_xy, sizeof(float) * 2 * (size_t)R.A.n_miss);
+        nret += R.A.n_ret; nmis += R.A.n_miss;
+        g.nx = nx; g.ny = ny; g.max_x = max_x; g.max_y = max_y;                    // what later submits' records are filled from
+        P.rec = nrec;
+        ++nrec;
+    }
+    return nrec;
 }
 
 // points per cloud of a filter submit: what the handle stages and what one workgroup of kgb_filter holds
@@ -993,61 +1128,47 @@ bool all_finite(const float *v, size_t n)
     return !bad;
 }
 
-// the filter's staging: records and input points for max_scans scans of two clouds, three output clouds per scan, three counts
+// The filter's staging: records and input points for max_scans scans of two clouds, three output clouds per scan, three counts.
+// A call that fails part-way keeps what it allocated, and the next one goes on from there.
 int filter_staging(rgrid_batch_t *b)
 {
     const size_t nS = (size_t)b->max_scans, nP = (size_t)filter_point_cap(b);
-    b->fpts_off = align_up(sizeof(FilterRec) * nS, 256);
-    const size_t in_bytes = b->fpts_off + sizeof(float2) * 2 * nS * nP, out_points = 3 * nS * nP;
+    b->fil.pts_off = align_up(sizeof(FilterRec) * nS, 256);
+    const size_t in_bytes = b->fil.pts_off + sizeof(float2) * 2 * nS * nP, out_points = 3 * nS * nP;
     if (out_points > 0x7fffffffu) return RGRID_ERR_CAPACITY;                       // a record's offsets are ints
-    if (b->pack.size() < sizeof(FilterRec) * nS) b->pack.resize(sizeof(FilterRec) * nS);
-    b->fsub.resize(nS);
-    void *dv = nullptr;
-    if (!b->h_fin) {
-        b->h_fin = (unsigned char *)host_visible::alloc(in_bytes);
-        if (b->h_fin) { b->fin_in_vram = true; b->dv_fin = b->h_fin; }
-        else {
-            G_TRY(b, hipHostMalloc((void **)&b->h_fin, in_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-            G_TRY(b, hipHostGetDevicePointer(&dv, b->h_fin, 0)); b->dv_fin = (const unsigned char *)dv;
-        }
-    }
-    if (!b->h_fout) {
-        G_TRY(b, hipHostMalloc((void **)&b->h_fout, sizeof(float2) * out_points, hipHostMallocMapped | hipHostMallocCoherent));
-        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_fout, 0)); b->dv_fout = (float2 *)dv;
-    }
+    if (b->seg.pack.size() < sizeof(FilterRec) * nS) b->seg.pack.resize(sizeof(FilterRec) * nS);
+    b->fil.sub.resize(nS);
+    if (!b->fil.in.h) G_TRY(b, b->fil.in.alloc(in_bytes));
+    if (!b->fil.out.h) G_TRY(b, b->fil.out.alloc(out_points));
     // the keys and the table of an 8192-point cloud: 128 KB of LDS, above the 64 KB a launch gets unasked
     G_TRY(b, hipFuncSetAttribute((const void *)kgb_filter, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)(KGF_SCRATCH + sizeof(int2) * (KGF_MAX_POINTS + 16) + sizeof(int) * (size_t)kgf_table_size(KGF_MAX_POINTS))));
-    if (!b->h_fcnt) G_TRY(b, hipHostMalloc((void **)&b->h_fcnt, sizeof(int) * 3 * nS, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(b->h_fcnt, 0, sizeof(int) * 3 * nS);
-    G_TRY(b, hipHostGetDevicePointer(&dv, b->h_fcnt, 0)); b->dv_fcnt = (int *)dv;   // last: it marks the staging as complete
+    G_TRY(b, b->fil.cnt.alloc(3 * nS));
+    std::memset(b->fil.cnt.h, 0, sizeof(int) * 3 * nS);
     return RGRID_OK;
 }
 
 // the texture's staging for a call that writes `pairs` pairs: the table and the box records once, the output area when it is too small
 int texture_staging(rgrid_batch_t *b, size_t pairs)
 {
-    void *dv = nullptr;
-    if (!b->d_tex) {
+    if (!b->tex.d_table) {
         std::vector<unsigned short> t(32768);
         texture_table(t.data());
         unsigned short *d = nullptr;
         G_TRY(b, hipMalloc((void **)&d, 2 * 32768));
         if (hipMemcpy(d, t.data(), 2 * 32768, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); b->hip_error = "texture table: upload failed"; return RGRID_ERR_HIP; }
-        b->d_tex = d;
+        b->tex.d_table = d;
     }
-    if (!b->h_tbox) {
-        b->tsub.resize((size_t)b->max_scans);
-        G_TRY(b, hipHostMalloc((void **)&b->h_tbox, sizeof(int) * 4 * (size_t)b->max_scans, hipHostMallocMapped | hipHostMallocCoherent));
-        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_tbox, 0)); b->dv_tbox = (int *)dv;
+    if (!b->tex.box.h) {
+        b->tex.sub.resize((size_t)b->max_scans);
+        G_TRY(b, b->tex.box.alloc(4 * (size_t)b->max_scans));
     }
-    if (pairs > b->tout_pairs) {
+    if (pairs > b->tex.out_pairs) {                                                // it never shrinks
         G_TRY(b, hipStreamSynchronize(b->stream));                                 // (nothing is pending: the area is idle)
-        if (b->h_tout) (void)hipHostFree(b->h_tout);
-        b->h_tout = nullptr; b->dv_tout = nullptr; b->tout_pairs = 0;
-        G_TRY(b, hipHostMalloc((void **)&b->h_tout, sizeof(unsigned short) * pairs, hipHostMallocMapped | hipHostMallocCoherent));
-        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_tout, 0)); b->dv_tout = (unsigned short *)dv;
-        b->tout_pairs = pairs;
+        b->tex.out.release();
+        b->tex.out_pairs = 0;
+        G_TRY(b, b->tex.out.alloc(pairs));
+        b->tex.out_pairs = pairs;
     }
     return RGRID_OK;
 }
@@ -1082,41 +1203,29 @@ int rgrid_batch_create(int max_scans, int max_points, int num_grids, long max_ce
     if (!b) return RGRID_ERR_INVALID;
     b->max_scans = max_scans; b->max_points = max_points; b->num_grids = num_grids; b->max_cells = max_cells;
     b->max_rotations = max_rotations; b->device = device;
-    b->wgmap_off = wgmap_off; b->f2_off = f2_off; b->rrec_off = rrec_off; b->raw_off = raw_off; b->seg_bytes = seg_bytes;
+    b->seg.wgmap_off = wgmap_off; b->seg.f2_off = f2_off; b->seg.rrec_off = rrec_off; b->seg.raw_off = raw_off;
     b->grids.resize((size_t)num_grids);
-    b->slot_call.assign((size_t)num_grids, 0ull);
+    b->ins.slot_call.assign((size_t)num_grids, 0ull);
     b->sub.resize(nS);
-    b->pack.resize(raw_off);               // (the raw points go straight into the segment)
+    b->seg.pack.resize(raw_off);           // (the raw points go straight into the segment)
     int rc = [&]() -> int {
         G_TRY(b, hipSetDevice(device));
         G_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-        for (int k = 0; k < KGB_SEGMENTS; ++k) {
-            b->h_seg[k] = (k == 0 || b->seg_in_vram) ? (unsigned char *)host_visible::alloc(seg_bytes) : nullptr;
-            if (b->h_seg[k]) {
-                b->seg_in_vram = true;
-                b->dv_seg[k] = b->h_seg[k];
-            } else {
-                if (k > 0 && b->seg_in_vram) { b->hip_error = "host-visible device memory: second segment refused"; return RGRID_ERR_HIP; }
-                void *dv = nullptr;
-                G_TRY(b, hipHostMalloc((void **)&b->h_seg[k], seg_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-                G_TRY(b, hipHostGetDevicePointer(&dv, b->h_seg[k], 0)); b->dv_seg[k] = (const unsigned char *)dv;
-            }
-        }
-        void *dv = nullptr;
-        G_TRY(b, hipHostMalloc((void **)&b->h_out, sizeof(BestRec) * nS, hipHostMallocMapped | hipHostMallocCoherent));
-        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_out, 0)); b->dv_out = (BestRec *)dv;
-        std::memset(b->h_out, 0, sizeof(BestRec) * nS);
-        G_TRY(b, hipHostMalloc((void **)&b->h_rout, sizeof(RefineOut) * nS, hipHostMallocMapped | hipHostMallocCoherent));
-        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_rout, 0)); b->dv_rout = (RefineOut *)dv;
-        std::memset(b->h_rout, 0, sizeof(RefineOut) * nS);
-        G_TRY(b, hipHostMalloc((void **)&b->h_bad, sizeof(int) * nS, hipHostMallocMapped | hipHostMallocCoherent));
-        G_TRY(b, hipHostGetDevicePointer(&dv, b->h_bad, 0)); b->dv_bad = (int *)dv;
-        std::memset(b->h_bad, 0, sizeof(int) * nS);
-        G_TRY(b, hipMalloc((void **)&b->d_hit, 2 * 32768)); G_TRY(b, hipMalloc((void **)&b->d_miss, 2 * 32768));
+        // both segments of one kind: host-visible device memory is tried for the second only when the first got it, and must not fail then
+        G_TRY(b, b->seg.buf[0].alloc(seg_bytes));
+        G_TRY(b, b->seg.buf[0].in_vram ? b->seg.buf[1].alloc(seg_bytes) : b->seg.buf[1].alloc_pinned(seg_bytes));
+        if (b->seg.buf[0].in_vram && !b->seg.buf[1].in_vram) { b->hip_error = "host-visible device memory: second segment refused"; return RGRID_ERR_HIP; }
+        G_TRY(b, b->res.best.alloc(nS));
+        std::memset(b->res.best.h, 0, sizeof(BestRec) * nS);
+        G_TRY(b, b->res.fine.alloc(nS));
+        std::memset(b->res.fine.h, 0, sizeof(RefineOut) * nS);
+        G_TRY(b, b->ins.bad.alloc(nS));
+        std::memset(b->ins.bad.h, 0, sizeof(int) * nS);
+        G_TRY(b, hipMalloc((void **)&b->ins.d_hit, 2 * 32768)); G_TRY(b, hipMalloc((void **)&b->ins.d_miss, 2 * 32768));
         G_TRY(b, hipMalloc((void **)&b->d_cells, sizeof(unsigned short) * (size_t)num_grids * (size_t)max_cells));
-        G_TRY(b, hipMalloc((void **)&b->d_bb, sizeof(unsigned long long) * nS * nR));
-        G_TRY(b, hipMalloc((void **)&b->d_arrived, sizeof(int) * nS));
-        G_TRY(b, hipMemsetAsync(b->d_arrived, 0, sizeof(int) * nS, b->stream));
+        G_TRY(b, hipMalloc((void **)&b->res.d_bb, sizeof(unsigned long long) * nS * nR));
+        G_TRY(b, hipMalloc((void **)&b->res.d_arrived, sizeof(int) * nS));
+        G_TRY(b, hipMemsetAsync(b->res.d_arrived, 0, sizeof(int) * nS, b->stream));
         // the rotated scan's indices in LDS: 8 B per point, 64 KB at 8192 points
         const int lds_max = (int)(sizeof(int2) * (nP + KGB_PF));
         G_TRY(b, hipFuncSetAttribute((const void *)kgb_match<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
@@ -1133,18 +1242,12 @@ void rgrid_batch_destroy(rgrid_batch_t *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    (void)hipFree(b->d_cells); (void)hipFree(b->d_bb); (void)hipFree(b->d_arrived); (void)hipFree(b->d_hit); (void)hipFree(b->d_miss);
-    for (int k = 0; k < KGB_SEGMENTS; ++k)
-        if (b->h_seg[k]) { if (b->seg_in_vram) (void)hipFree(b->h_seg[k]); else (void)hipHostFree(b->h_seg[k]); }
-    if (b->h_out) (void)hipHostFree(b->h_out);
-    if (b->h_rout) (void)hipHostFree(b->h_rout);
-    if (b->h_bad) (void)hipHostFree(b->h_bad);
-    if (b->h_fin) { if (b->fin_in_vram) (void)hipFree(b->h_fin); else (void)hipHostFree(b->h_fin); }
-    if (b->h_fout) (void)hipHostFree(b->h_fout);
-    if (b->h_fcnt) (void)hipHostFree(b->h_fcnt);
-    (void)hipFree(b->d_tex);
-    if (b->h_tout) (void)hipHostFree(b->h_tout);
-    if (b->h_tbox) (void)hipHostFree(b->h_tbox);
+    (void)hipFree(b->d_cells); (void)hipFree(b->res.d_bb); (void)hipFree(b->res.d_arrived);
+    (void)hipFree(b->ins.d_hit); (void)hipFree(b->ins.d_miss); (void)hipFree(b->tex.d_table);
+    for (auto &s : b->seg.buf) s.release();
+    b->res.best.release(); b->res.fine.release(); b->ins.bad.release();
+    b->fil.in.release(); b->fil.out.release(); b->fil.cnt.release();
+    b->tex.out.release(); b->tex.box.release();
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -1163,7 +1266,7 @@ int rgrid_batch_set_grid(rgrid_batch_t *b, int grid, const uint16_t *cells, int 
         return RGRID_ERR_INVALID;
     if ((long long)num_x_cells * num_y_cells > (long long)b->max_cells) return RGRID_ERR_CAPACITY;
     G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipMemcpyAsync(b->d_cells + (size_t)grid * (size_t)b->max_cells, cells, sizeof(uint16_t) * (size_t)num_x_cells * num_y_cells,
+    G_TRY(b, hipMemcpyAsync(b->d_cells + cells_offset(b, grid), cells, sizeof(uint16_t) * (size_t)num_x_cells * num_y_cells,
                             hipMemcpyHostToDevice, b->stream));
     G_TRY(b, hipStreamSynchronize(b->stream));
     GridSlot &g = b->grids[(size_t)grid];
@@ -1177,41 +1280,23 @@ int rgrid_batch_match_submit(rgrid_batch_t *b, const rgrid_match_options *opt, c
     if (!match_scans_ok(b, scans, count)) return RGRID_ERR_INVALID;
     const auto t_begin = std::chrono::steady_clock::now();
     const MatchWork W = pack_match(b, opt, scans, count);
-    b->sub_count = count;
-    if (W.nrec == 0) {
-        b->outstanding = true; b->kind = KIND_MATCH;
-        b->prepare_seconds = seconds_since(t_begin);
-        return RGRID_OK;
+    int k = 0;
+    if (W.nrec > 0) {
+        G_TRY(b, hipSetDevice(b->device));
+        k = take_segment(b);
+        stage_match(b, k, W);
     }
-    G_TRY(b, hipSetDevice(b->device));
-    const int k = (int)(b->n_submit++ % KGB_SEGMENTS);
-    stage_match(b, k, W);
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
-    b->prepare_seconds = seconds_since(t_begin);
-    launch_match(b, k, W);
-    G_TRY(b, hipGetLastError());
-    b->outstanding = true; b->kind = KIND_MATCH;
-    return RGRID_OK;
+    return submit_tail(b, KIND_MATCH, count, W.nrec, t_begin, [&] { launch_match(b, k, W); });
 }
 
 int rgrid_batch_match_collect(rgrid_batch_t *b, int *status, double *pose_estimates, double *scores, int *best3, int *info3)
 {
-    if (!b || !b->outstanding || b->kind != KIND_MATCH) return RGRID_ERR_INVALID;
-    const int count = b->sub_count;
-    if (count > 0 && (!status || !pose_estimates || !scores)) return RGRID_ERR_INVALID;
-    b->outstanding = false;
-    G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipStreamSynchronize(b->stream));
+    int count = 0;
+    const int rc = collect_head(b, KIND_MATCH, status && pose_estimates && scores, true, &count);
+    if (rc != RGRID_OK) return rc;
     for (int j = 0; j < count; ++j) {
-        const Pending &P = b->sub[(size_t)j];
-        status[j] = P.status;
-        pose_estimates[3 * j] = pose_estimates[3 * j + 1] = pose_estimates[3 * j + 2] = 0.;
-        scores[j] = 0.;
-        if (best3) best3[3 * j] = best3[3 * j + 1] = best3[3 * j + 2] = 0;
-        if (info3) info3[3 * j] = info3[3 * j + 1] = info3[3 * j + 2] = 0;
-        if (P.status != RGRID_OK) continue;
-        decode_best(P.plan, P.pose, b->h_out[P.rec], &pose_estimates[3 * j], &scores[j], best3 ? &best3[3 * j] : nullptr,
-                    info3 ? &info3[3 * j] : nullptr);
+        status[j] = b->sub[(size_t)j].status;
+        match_result(b, j, pose_estimates, scores, best3, info3);
     }
     return RGRID_OK;
 }
@@ -1219,60 +1304,36 @@ int rgrid_batch_match_collect(rgrid_batch_t *b, int *status, double *pose_estima
 int rgrid_batch_refine_submit(rgrid_batch_t *b, const rgrid_refine_options *opt, const rgrid_batch_refine_scan *scans, int count)
 {
     if (!b || !opt || count < 0 || count > b->max_scans || (count > 0 && !scans) || b->outstanding || !refine_options_ok(opt)) return RGRID_ERR_INVALID;
-    for (int j = 0; j < count; ++j) {
-        const rgrid_batch_refine_scan &s = scans[j];
-        if (s.grid < 0 || s.grid >= b->num_grids || !b->grids[(size_t)s.grid].set || s.n < 0 || (s.n > 0 && !s.points_xy)) return RGRID_ERR_INVALID;
-    }
+    for (int j = 0; j < count; ++j)
+        if (!cloud_ok(b, scans[j].grid, scans[j].points_xy, scans[j].n)) return RGRID_ERR_INVALID;
     const auto t_begin = std::chrono::steady_clock::now();
-    const int k = (int)(b->n_submit % KGB_SEGMENTS);
-    RefineRec *rr = reinterpret_cast<RefineRec *>(b->pack.data() + b->rrec_off);
-    float *raw = reinterpret_cast<float *>(b->h_seg[k] + b->raw_off);
+    const int k = next_segment(b);
     int nrec = 0, nraw = 0, threads = 0;
     for (int j = 0; j < count; ++j) {
         const rgrid_batch_refine_scan &s = scans[j];
-        Pending &P = b->sub[(size_t)j];
-        std::memset(&P, 0, sizeof(P));
-        P.rec = -1;
+        Pending &P = fresh_pending(b, j);
         if (s.n == 0) { P.status = RGRID_ERR_EMPTY; continue; }
         if (s.n > b->max_points) { P.status = RGRID_ERR_CAPACITY; continue; }
-        RefineRec &R = rr[nrec];
-        std::memset(&R, 0, sizeof(R));
-        refine_args(R.A, b->grids[(size_t)s.grid], opt, s.n);
+        RefineRec &R = pack_refine(b, k, nrec, opt, s.grid, s.points_xy, s.n, nraw, threads);
         R.A.tx = s.target_translation[0]; R.A.ty = s.target_translation[1];
         R.A.x0 = s.initial_pose[0]; R.A.y0 = s.initial_pose[1]; R.A.a0 = s.initial_pose[2];
-        R.cells_off = (long long)s.grid * (long long)b->max_cells;
-        R.pts_off = nraw; R.match_rec = -1;
-        std::memcpy(raw + 2 * (size_t)nraw, s.points_xy, sizeof(float) * 2 * (size_t)s.n);   // forward, straight into the segment
-        nraw += s.n;
-        if (refine_threads(s.n) > threads) threads = refine_threads(s.n);
+        R.match_rec = -1;
         P.status = RGRID_OK; P.rec = nrec;
         ++nrec;
     }
-    b->sub_count = count;
-    if (nrec == 0) {
-        b->outstanding = true; b->kind = KIND_REFINE;
-        b->prepare_seconds = seconds_since(t_begin);
-        return RGRID_OK;
+    if (nrec > 0) {
+        G_TRY(b, hipSetDevice(b->device));
+        take_segment(b);
+        std::memcpy(b->seg.buf[k].h + b->seg.rrec_off, b->seg.pack.data() + b->seg.rrec_off, sizeof(RefineRec) * (size_t)nrec);
     }
-    G_TRY(b, hipSetDevice(b->device));
-    ++b->n_submit;
-    std::memcpy(b->h_seg[k] + b->rrec_off, rr, sizeof(RefineRec) * (size_t)nrec);
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
-    b->prepare_seconds = seconds_since(t_begin);
-    launch_refine(b, k, nrec, threads);
-    G_TRY(b, hipGetLastError());
-    b->outstanding = true; b->kind = KIND_REFINE;
-    return RGRID_OK;
+    return submit_tail(b, KIND_REFINE, count, nrec, t_begin, [&] { launch_refine(b, k, nrec, threads); });
 }
 
 int rgrid_batch_refine_collect(rgrid_batch_t *b, int *status, double *pose_estimates, rgrid_refine_summary *summaries)
 {
-    if (!b || !b->outstanding || b->kind != KIND_REFINE) return RGRID_ERR_INVALID;
-    const int count = b->sub_count;
-    if (count > 0 && (!status || !pose_estimates)) return RGRID_ERR_INVALID;
-    b->outstanding = false;
-    G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipStreamSynchronize(b->stream));
+    int count = 0;
+    const int rc = collect_head(b, KIND_REFINE, status && pose_estimates, true, &count);
+    if (rc != RGRID_OK) return rc;
     for (int j = 0; j < count; ++j) {
         status[j] = b->sub[(size_t)j].status;
         refine_result(b, b->sub[(size_t)j], &pose_estimates[3 * j], summaries ? &summaries[j] : nullptr);
@@ -1288,71 +1349,46 @@ int rgrid_batch_scan_match_submit(rgrid_batch_t *b, const rgrid_match_options *m
     if (!match_scans_ok(b, scans, count)) return RGRID_ERR_INVALID;
     const auto t_begin = std::chrono::steady_clock::now();
     const MatchWork W = pack_match(b, mopt, scans, count);
-    b->sub_count = count;
-    if (W.nrec == 0) {
-        b->outstanding = true; b->kind = KIND_SCAN_MATCH;
-        b->prepare_seconds = seconds_since(t_begin);
-        return RGRID_OK;
+    int k = 0, nraw = 0, threads = 0;
+    if (W.nrec > 0) {
+        G_TRY(b, hipSetDevice(b->device));
+        k = take_segment(b);
+        // a refine record per match record, same index: the start pose is the match's winner, decoded on the device
+        for (int j = 0; j < count; ++j) {
+            const Pending &P = b->sub[(size_t)j];
+            if (P.status != RGRID_OK) continue;
+            const rgrid_batch_scan &s = scans[j];
+            RefineRec &R = pack_refine(b, k, P.rec, ropt, s.grid, s.points_xy, s.n, nraw, threads);
+            R.plan_res = P.plan.res; R.plan_step = P.plan.step;
+            R.ip[0] = s.initial_pose[0]; R.ip[1] = s.initial_pose[1]; R.ip[2] = s.initial_pose[2];
+            R.match_rec = P.rec; R.num_linear = P.plan.num_linear; R.num_angular = P.plan.num_angular;
+        }
+        stage_match(b, k, W);
+        std::memcpy(b->seg.buf[k].h + b->seg.rrec_off, b->seg.pack.data() + b->seg.rrec_off, sizeof(RefineRec) * (size_t)W.nrec);
     }
-    G_TRY(b, hipSetDevice(b->device));
-    const int k = (int)(b->n_submit++ % KGB_SEGMENTS);
-    // a refine record per match record, same index: the start pose is the match's winner, decoded on the device
-    RefineRec *rr = reinterpret_cast<RefineRec *>(b->pack.data() + b->rrec_off);
-    float *raw = reinterpret_cast<float *>(b->h_seg[k] + b->raw_off);
-    int nraw = 0, threads = 0;
-    for (int j = 0; j < count; ++j) {
-        const Pending &P = b->sub[(size_t)j];
-        if (P.status != RGRID_OK) continue;
-        const rgrid_batch_scan &s = scans[j];
-        RefineRec &R = rr[P.rec];
-        std::memset(&R, 0, sizeof(R));
-        refine_args(R.A, b->grids[(size_t)s.grid], ropt, s.n);
-        R.cells_off = (long long)s.grid * (long long)b->max_cells;
-        R.plan_res = P.plan.res; R.plan_step = P.plan.step;
-        R.ip[0] = s.initial_pose[0]; R.ip[1] = s.initial_pose[1]; R.ip[2] = s.initial_pose[2];
-        R.pts_off = nraw; R.match_rec = P.rec; R.num_linear = P.plan.num_linear; R.num_angular = P.plan.num_angular;
-        std::memcpy(raw + 2 * (size_t)nraw, s.points_xy, sizeof(float) * 2 * (size_t)s.n);
-        nraw += s.n;
-        if (refine_threads(s.n) > threads) threads = refine_threads(s.n);
-    }
-    stage_match(b, k, W);
-    std::memcpy(b->h_seg[k] + b->rrec_off, rr, sizeof(RefineRec) * (size_t)W.nrec);
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
-    b->prepare_seconds = seconds_since(t_begin);
-    launch_match(b, k, W);                                    // the stream orders the refinement behind the match: no host wait between them
-    launch_refine(b, k, W.nrec, threads);
-    G_TRY(b, hipGetLastError());
-    b->outstanding = true; b->kind = KIND_SCAN_MATCH;
-    return RGRID_OK;
+    return submit_tail(b, KIND_SCAN_MATCH, count, W.nrec, t_begin, [&] {
+        launch_match(b, k, W);                                // the stream orders the refinement behind the match: no host wait between them
+        launch_refine(b, k, W.nrec, threads);
+    });
 }
 
 int rgrid_batch_scan_match_collect(rgrid_batch_t *b, int *status, double *coarse_poses, double *scores, int *best3, int *info3,
                                    double *pose_estimates, rgrid_refine_summary *summaries)
 {
-    if (!b || !b->outstanding || b->kind != KIND_SCAN_MATCH) return RGRID_ERR_INVALID;
-    const int count = b->sub_count;
-    if (count > 0 && (!status || !coarse_poses || !scores || !pose_estimates)) return RGRID_ERR_INVALID;
-    b->outstanding = false;
-    G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipStreamSynchronize(b->stream));
+    int count = 0;
+    const int rc = collect_head(b, KIND_SCAN_MATCH, status && coarse_poses && scores && pose_estimates, true, &count);
+    if (rc != RGRID_OK) return rc;
     for (int j = 0; j < count; ++j) {
-        const Pending &P = b->sub[(size_t)j];
-        status[j] = P.status;
-        zero3(&coarse_poses[3 * j]);
-        scores[j] = 0.;
-        zero3(best3 ? &best3[3 * j] : nullptr);
-        zero3(info3 ? &info3[3 * j] : nullptr);
-        refine_result(b, P, &pose_estimates[3 * j], summaries ? &summaries[j] : nullptr);
-        if (P.status != RGRID_OK) continue;
-        decode_best(P.plan, P.pose, b->h_out[P.rec], &coarse_poses[3 * j], &scores[j], best3 ? &best3[3 * j] : nullptr,
-                    info3 ? &info3[3 * j] : nullptr);
+        status[j] = b->sub[(size_t)j].status;
+        match_result(b, j, coarse_poses, scores, best3, info3);
+        refine_result(b, b->sub[(size_t)j], &pose_estimates[3 * j], summaries ? &summaries[j] : nullptr);
     }
     return RGRID_OK;
 }
 
 int rgrid_batch_get_limits(rgrid_batch_t *b, int grid, int *num_x_cells, int *num_y_cells, double *resolution, double *max_x, double *max_y)
 {
-    if (!b || grid < 0 || grid >= b->num_grids || !b->grids[(size_t)grid].set || b->outstanding) return RGRID_ERR_INVALID;
+    if (!b || !slot_ok(b, grid) || b->outstanding) return RGRID_ERR_INVALID;
     const GridSlot &g = b->grids[(size_t)grid];
     if (num_x_cells) *num_x_cells = g.nx;
     if (num_y_cells) *num_y_cells = g.ny;
@@ -1364,110 +1400,66 @@ int rgrid_batch_get_limits(rgrid_batch_t *b, int grid, int *num_x_cells, int *nu
 
 int rgrid_batch_get_grid(rgrid_batch_t *b, int grid, uint16_t *cells, long cap)
 {
-    if (!b || !cells || grid < 0 || grid >= b->num_grids || !b->grids[(size_t)grid].set || b->outstanding) return RGRID_ERR_INVALID;
+    if (!b || !cells || !slot_ok(b, grid) || b->outstanding) return RGRID_ERR_INVALID;
     const GridSlot &g = b->grids[(size_t)grid];
     const long long ncells = (long long)g.nx * g.ny;
     if (cap < ncells) return RGRID_ERR_BUFFER;
     G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipMemcpyAsync(cells, b->d_cells + (size_t)grid * (size_t)b->max_cells, sizeof(uint16_t) * (size_t)ncells, hipMemcpyDeviceToHost,
-                            b->stream));
+    G_TRY(b, hipMemcpyAsync(cells, b->d_cells + cells_offset(b, grid), sizeof(uint16_t) * (size_t)ncells, hipMemcpyDeviceToHost, b->stream));
     G_TRY(b, hipStreamSynchronize(b->stream));
     return RGRID_OK;
 }
 
 int rgrid_batch_insert_submit(rgrid_batch_t *b, const rgrid_insert_options *opt, const rgrid_batch_insert_scan *scans, int count)
 {
+    // (scans == NULL is refused at count == 0 too, unlike the match, the refinement and the texture: callers may rely on it)
     if (!b || !opt || !scans || count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
     if (!(opt->hit_probability > 0.f && opt->hit_probability < 1.f) || !(opt->miss_probability > 0.f && opt->miss_probability < 1.f))
         return RGRID_ERR_INVALID;
     for (int j = 0; j < count; ++j) {
         const rgrid_batch_insert_scan &s = scans[j];
-        if (s.grid < 0 || s.grid >= b->num_grids || !b->grids[(size_t)s.grid].set || s.n_returns < 0 || s.n_misses < 0 ||
-            (s.n_returns > 0 && !s.returns_xy) || (s.n_misses > 0 && !s.misses_xy))
-            return RGRID_ERR_INVALID;
+        if (!slot_ok(b, s.grid) || !two_clouds_ok(s.returns_xy, s.n_returns, s.misses_xy, s.n_misses)) return RGRID_ERR_INVALID;
     }
-    // a slot at most once per call: two insertions into one grid in one launch have no reference meaning (FinishUpdate lies between)
-    ++b->n_insert;
+    // a slot at most once per call: two insertions into one grid in one launch have no reference meaning (FinishUpdate lies between).
+    // The call is counted, and its slots marked, before anything else can refuse it
+    ++b->ins.n_calls;
     for (int j = 0; j < count; ++j) {
-        unsigned long long &seen = b->slot_call[(size_t)scans[j].grid];
-        if (seen == b->n_insert) return RGRID_ERR_INVALID;
-        seen = b->n_insert;
+        unsigned long long &seen = b->ins.slot_call[(size_t)scans[j].grid];
+        if (seen == b->ins.n_calls) return RGRID_ERR_INVALID;
+        seen = b->ins.n_calls;
     }
     const auto t_begin = std::chrono::steady_clock::now();
     G_TRY(b, hipSetDevice(b->device));
-    if (opt->hit_probability != b->tab_hit_p || opt->miss_probability != b->tab_miss_p) {   // the tables only depend on the two options
+    if (opt->hit_probability != b->ins.tab_hit_p || opt->miss_probability != b->ins.tab_miss_p) {   // the tables only depend on the two options
         std::vector<unsigned short> t(32768);
         lookup_table(opt->hit_probability, t.data());
-        G_TRY(b, hipMemcpy(b->d_hit, t.data(), 2 * 32768, hipMemcpyHostToDevice));
+        G_TRY(b, hipMemcpy(b->ins.d_hit, t.data(), 2 * 32768, hipMemcpyHostToDevice));
         lookup_table(opt->miss_probability, t.data());
-        G_TRY(b, hipMemcpy(b->d_miss, t.data(), 2 * 32768, hipMemcpyHostToDevice));
-        b->tab_hit_p = opt->hit_probability; b->tab_miss_p = opt->miss_probability;
+        G_TRY(b, hipMemcpy(b->ins.d_miss, t.data(), 2 * 32768, hipMemcpyHostToDevice));
+        b->ins.tab_hit_p = opt->hit_probability; b->ins.tab_miss_p = opt->miss_probability;
     }
-    const int k = (int)(b->n_submit % KGB_SEGMENTS);
-    InsertRec *recs = reinterpret_cast<InsertRec *>(b->pack.data());
-    float *ret = reinterpret_cast<float *>(b->h_seg[k] + b->f2_off), *mis = reinterpret_cast<float *>(b->h_seg[k] + b->raw_off);
-    int nrec = 0, nret = 0, nmis = 0;
-    for (int j = 0; j < count; ++j) {
-        const rgrid_batch_insert_scan &s = scans[j];
-        GridSlot &g = b->grids[(size_t)s.grid];
-        Pending &P = b->sub[(size_t)j];
-        std::memset(&P, 0, sizeof(P));
-        P.rec = -1;
-        // rgrid_grow_as_needed: on the host, from the points that are copied anyway; the move itself is the workgroup's first phase
-        int nx = g.nx, ny = g.ny, off_x = 0, off_y = 0;
-        double max_x = g.max_x, max_y = g.max_y;
-        P.status = plan_growth(s.origin_xy, s.returns_xy, s.n_returns, s.misses_xy, s.n_misses, g.resolution, (long long)b->max_cells, nx, ny,
-                               max_x, max_y, off_x, off_y);
-        if (P.status != RGRID_OK) continue;                                        // the slot stays as it is
-        // rgrid_insert: more points than the handle stages.  The pair has grown the grid by then, so this scan's workgroup grows it too
-        const bool fits = s.n_returns <= b->max_points && s.n_misses <= b->max_points;
-        if (!fits) P.status = RGRID_ERR_CAPACITY;
-        if (!fits && nx == g.nx && ny == g.ny) continue;
-        InsertRec &R = recs[nrec];
-        std::memset(&R, 0, sizeof(R));
-        R.A.nx = nx; R.A.ny = ny; R.A.n_ret = fits ? s.n_returns : 0; R.A.n_miss = fits ? s.n_misses : 0;
-        R.A.max_x = max_x; R.A.max_y = max_y; R.A.rs = g.resolution / SUBPX;
-        R.A.ox = s.origin_xy[0]; R.A.oy = s.origin_xy[1];
-        R.cells_off = (long long)s.grid * (long long)b->max_cells;
-        R.old_nx = g.nx; R.old_ny = g.ny; R.off_x = off_x; R.off_y = off_y;
-        R.ret_off = nret; R.mis_off = nmis;
-        if (R.A.n_ret > 0) std::memcpy(ret + 2 * (size_t)nret, s.returns_xy, sizeof(float) * 2 * (size_t)R.A.n_ret);   // forward, straight into the segment
-        if (R.A.n_miss > 0) std::memcpy(mis + 2 * (size_t)nmis, s.misses_xy, sizeof(float) * 2 * (size_t)R.A.n_miss);
-        nret += R.A.n_ret; nmis += R.A.n_miss;
-        g.nx = nx; g.ny = ny; g.max_x = max_x; g.max_y = max_y;                    // what later submits' records are filled from
-        P.rec = nrec;
-        ++nrec;
+    const int k = next_segment(b);
+    const int nrec = pack_insert(b, k, scans, count);
+    if (nrec > 0) {
+        take_segment(b);
+        std::memcpy(b->seg.buf[k].h, b->seg.pack.data(), sizeof(InsertRec) * (size_t)nrec);
     }
-    b->sub_count = count;
-    if (nrec == 0) {
-        b->outstanding = true; b->kind = KIND_INSERT;
-        b->prepare_seconds = seconds_since(t_begin);
-        return RGRID_OK;
-    }
-    ++b->n_submit;
-    std::memcpy(b->h_seg[k], recs, sizeof(InsertRec) * (size_t)nrec);
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
-    b->prepare_seconds = seconds_since(t_begin);
-    InsertBufs If;
-    If.seg = b->dv_seg[k]; If.f2_off = (int)b->f2_off; If.raw_off = (int)b->raw_off;
-    If.cells = b->d_cells; If.hit = b->d_hit; If.miss = b->d_miss; If.bad = b->dv_bad; If.free_space = opt->insert_free_space ? 1 : 0;
-    hipLaunchKernelGGL(kgb_insert, dim3((unsigned)nrec), dim3(KGI_THREADS), 0, b->stream, If);
-    G_TRY(b, hipGetLastError());
-    b->outstanding = true; b->kind = KIND_INSERT;
-    return RGRID_OK;
+    return submit_tail(b, KIND_INSERT, count, nrec, t_begin, [&] {
+        InsertBufs If;
+        If.seg = b->seg.buf[k].dv; If.f2_off = (int)b->seg.f2_off; If.raw_off = (int)b->seg.raw_off;
+        If.cells = b->d_cells; If.hit = b->ins.d_hit; If.miss = b->ins.d_miss; If.bad = b->ins.bad.dv; If.free_space = opt->insert_free_space ? 1 : 0;
+        hipLaunchKernelGGL(kgb_insert, dim3((unsigned)nrec), dim3(KGI_THREADS), 0, b->stream, If);
+    });
 }
 
 int rgrid_batch_insert_collect(rgrid_batch_t *b, int *status)
 {
-    if (!b || !b->outstanding || b->kind != KIND_INSERT) return RGRID_ERR_INVALID;
-    const int count = b->sub_count;
-    if (count > 0 && !status) return RGRID_ERR_INVALID;
-    b->outstanding = false;
-    G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipStreamSynchronize(b->stream));
+    int count = 0;
+    const int rc = collect_head(b, KIND_INSERT, status != nullptr, true, &count);
+    if (rc != RGRID_OK) return rc;
     for (int j = 0; j < count; ++j) {
         const Pending &P = b->sub[(size_t)j];
-        status[j] = (P.status == RGRID_OK && b->h_bad[P.rec]) ? RGRID_ERR_CAPACITY : P.status;   // an end point outside the grid after growth
+        status[j] = (P.status == RGRID_OK && b->ins.bad.h[P.rec]) ? RGRID_ERR_CAPACITY : P.status;   // an end point outside the grid after growth
     }
     return RGRID_OK;
 }
@@ -1478,25 +1470,24 @@ int rgrid_batch_sizeof_filter_scan(void) { return (int)sizeof(rgrid_batch_filter
 
 int rgrid_batch_filter_submit(rgrid_batch_t *b, const rgrid_filter_options *opt, const rgrid_batch_filter_scan *scans, int count)
 {
+    // (scans == NULL is refused at count == 0 too, as by the inserter)
     if (!b || !opt || !scans || count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
     if (!(opt->voxel_filter_size > 0.f) || !(opt->adaptive_max_length > 0.)) return RGRID_ERR_INVALID;
-    for (int j = 0; j < count; ++j) {
-        const rgrid_batch_filter_scan &s = scans[j];
-        if (s.n_returns < 0 || s.n_misses < 0 || (s.n_returns > 0 && !s.returns_xy) || (s.n_misses > 0 && !s.misses_xy)) return RGRID_ERR_INVALID;
-    }
+    for (int j = 0; j < count; ++j)
+        if (!two_clouds_ok(scans[j].returns_xy, scans[j].n_returns, scans[j].misses_xy, scans[j].n_misses)) return RGRID_ERR_INVALID;
     const auto t_begin = std::chrono::steady_clock::now();
     G_TRY(b, hipSetDevice(b->device));
     const int cap = filter_point_cap(b);
-    if (!b->dv_fcnt) {                                                             // the first filter submit of this handle
+    if (!b->fil.cnt.h) {                                                           // the first filter submit of this handle
         const int rc = filter_staging(b);
         if (rc != RGRID_OK) return rc;
     }
-    FilterRec *recs = reinterpret_cast<FilterRec *>(b->pack.data());               // (the image of a match's records: free between submits)
-    float *pts = reinterpret_cast<float *>(b->h_fin + b->fpts_off);
+    FilterRec *recs = reinterpret_cast<FilterRec *>(b->seg.pack.data());           // (the image of a match's records: free between submits)
+    float *pts = reinterpret_cast<float *>(b->fil.in.h + b->fil.pts_off);
     int nrec = 0, nin = 0, nout = 0, n_max = 0;
     for (int j = 0; j < count; ++j) {
         const rgrid_batch_filter_scan &s = scans[j];
-        FilterPending &P = b->fsub[(size_t)j];
+        FilterPending &P = b->fil.sub[(size_t)j];
         P.status = RGRID_OK; P.rec = -1; P.out_off = 0; P.n_ret = s.n_returns; P.n_mis = s.n_misses;
         if (s.n_returns > cap || s.n_misses > cap) { P.status = RGRID_ERR_CAPACITY; continue; }
         if (!all_finite(s.returns_xy, 2 * (size_t)s.n_returns) || !all_finite(s.misses_xy, 2 * (size_t)s.n_misses)) { P.status = RGRID_ERR_INVALID; continue; }
@@ -1511,50 +1502,40 @@ int rgrid_batch_filter_submit(rgrid_batch_t *b, const rgrid_filter_options *opt,
         P.rec = nrec; P.out_off = R.out_off;
         ++nrec;
     }
-    b->sub_count = count;
-    if (nrec == 0) {
-        b->outstanding = true; b->kind = KIND_FILTER;
-        b->prepare_seconds = seconds_since(t_begin);
-        return RGRID_OK;
-    }
-    std::memcpy(b->h_fin, recs, sizeof(FilterRec) * (size_t)nrec);
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
-    b->prepare_seconds = seconds_since(t_begin);
-    FilterBufs Ff;
-    Ff.in = b->dv_fin; Ff.pts_off = (int)b->fpts_off; Ff.key_cap = (n_max + 15) / 16 * 16 + 16;
-    Ff.out = b->dv_fout; Ff.counts = b->dv_fcnt;
-    Ff.min_pts = opt->adaptive_min_num_points;
-    Ff.vsize = opt->voxel_filter_size; Ff.maxl = (float)opt->adaptive_max_length; Ff.max_range = (float)opt->adaptive_max_range;
-    const size_t lds = KGF_SCRATCH + sizeof(int2) * (size_t)Ff.key_cap + sizeof(int) * (size_t)kgf_table_size(n_max);
-    hipLaunchKernelGGL(kgb_filter, dim3((unsigned)nrec), dim3(KGF_THREADS), lds, b->stream, Ff);
-    G_TRY(b, hipGetLastError());
-    b->outstanding = true; b->kind = KIND_FILTER;
-    return RGRID_OK;
+    std::memcpy(b->fil.in.h, recs, sizeof(FilterRec) * (size_t)nrec);              // (its own staging: no segment is taken)
+    return submit_tail(b, KIND_FILTER, count, nrec, t_begin, [&] {
+        FilterBufs Ff;
+        Ff.in = b->fil.in.dv; Ff.pts_off = (int)b->fil.pts_off; Ff.key_cap = (n_max + 15) / 16 * 16 + 16;
+        Ff.out = b->fil.out.dv; Ff.counts = b->fil.cnt.dv;
+        Ff.min_pts = opt->adaptive_min_num_points;
+        Ff.vsize = opt->voxel_filter_size; Ff.maxl = (float)opt->adaptive_max_length; Ff.max_range = (float)opt->adaptive_max_range;
+        const size_t lds = KGF_SCRATCH + sizeof(int2) * (size_t)Ff.key_cap + sizeof(int) * (size_t)kgf_table_size(n_max);
+        hipLaunchKernelGGL(kgb_filter, dim3((unsigned)nrec), dim3(KGF_THREADS), lds, b->stream, Ff);
+    });
 }
 
 int rgrid_batch_filter_collect(rgrid_batch_t *b, int *status, int *counts, float *out_xy, long out_cap_points)
 {
-    if (!b || !b->outstanding || b->kind != KIND_FILTER) return RGRID_ERR_INVALID;
-    const int count = b->sub_count;
-    if ((count > 0 && (!status || !counts)) || out_cap_points < 0) return RGRID_ERR_INVALID;
-    G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipStreamSynchronize(b->stream));
+    if (out_cap_points < 0) return RGRID_ERR_INVALID;
+    int count = 0;
+    const int rc = collect_head(b, KIND_FILTER, status && counts, false, &count);
+    if (rc != RGRID_OK) return rc;
     long total = 0;
     for (int j = 0; j < count; ++j) {
-        const FilterPending &P = b->fsub[(size_t)j];
+        const FilterPending &P = b->fil.sub[(size_t)j];
         status[j] = P.status;
-        for (int c = 0; c < 3; ++c) total += counts[3 * j + c] = P.rec >= 0 ? b->h_fcnt[3 * P.rec + c] : 0;
+        for (int c = 0; c < 3; ++c) total += counts[3 * j + c] = P.rec >= 0 ? b->fil.cnt.h[3 * P.rec + c] : 0;
     }
     if (total > out_cap_points || (total > 0 && !out_xy)) return RGRID_ERR_BUFFER;         // the submit stays pending: come again with room
     b->outstanding = false;
     float *dst = out_xy;
     for (int j = 0; j < count; ++j) {
-        const FilterPending &P = b->fsub[(size_t)j];
+        const FilterPending &P = b->fil.sub[(size_t)j];
         if (P.rec < 0) continue;
         const int off[3] = {P.out_off, P.out_off + P.n_ret, P.out_off + P.n_ret + P.n_mis};   // fr, fm, av as the kernel laid them out
         for (int c = 0; c < 3; ++c) {
             const size_t k = (size_t)counts[3 * j + c];
-            if (k > 0) std::memcpy(dst, b->h_fout + off[c], sizeof(float2) * k);
+            if (k > 0) std::memcpy(dst, b->fil.out.h + off[c], sizeof(float2) * k);
             dst += 2 * k;
         }
     }
@@ -1566,53 +1547,45 @@ int rgrid_batch_texture_submit(rgrid_batch_t *b, const int *grids, int count)
     if (!b || count < 0 || count > b->max_scans || (count > 0 && !grids) || b->outstanding) return RGRID_ERR_INVALID;
     size_t pairs = 0;
     for (int j = 0; j < count; ++j) {
-        if (grids[j] < 0 || grids[j] >= b->num_grids || !b->grids[(size_t)grids[j]].set) return RGRID_ERR_INVALID;
+        if (!slot_ok(b, grids[j])) return RGRID_ERR_INVALID;
         const GridSlot &g = b->grids[(size_t)grids[j]];
         pairs += align_up((size_t)g.nx * (size_t)g.ny, 8);                          // every region starts on a 16-byte boundary
     }
     const auto t_begin = std::chrono::steady_clock::now();
-    b->sub_count = count;
-    if (count == 0) {
-        b->outstanding = true; b->kind = KIND_TEXTURE;
-        b->prepare_seconds = seconds_since(t_begin);
-        return RGRID_OK;
+    int k = 0;
+    if (count > 0) {                                                               // (a call without a slot allocates nothing and takes no segment)
+        G_TRY(b, hipSetDevice(b->device));
+        const int rc = texture_staging(b, pairs);
+        if (rc != RGRID_OK) return rc;
+        k = take_segment(b);
+        TextureRec *recs = reinterpret_cast<TextureRec *>(b->seg.pack.data());
+        long long at = 0;
+        for (int j = 0; j < count; ++j) {
+            const GridSlot &g = b->grids[(size_t)grids[j]];
+            TextureRec &R = recs[j];
+            R.cells_off = cells_offset(b, grids[j]);
+            R.out_off = at; R.nx = g.nx; R.ny = g.ny;
+            b->tex.sub[(size_t)j] = TexturePending{grids[j], at};
+            at += (long long)align_up((size_t)g.nx * (size_t)g.ny, 8);
+        }
+        std::memcpy(b->seg.buf[k].h, recs, sizeof(TextureRec) * (size_t)count);
     }
-    G_TRY(b, hipSetDevice(b->device));
-    const int rc = texture_staging(b, pairs);
-    if (rc != RGRID_OK) return rc;
-    const int k = (int)(b->n_submit++ % KGB_SEGMENTS);
-    TextureRec *recs = reinterpret_cast<TextureRec *>(b->pack.data());
-    long long at = 0;
-    for (int j = 0; j < count; ++j) {
-        const GridSlot &g = b->grids[(size_t)grids[j]];
-        TextureRec &R = recs[j];
-        R.cells_off = (long long)grids[j] * (long long)b->max_cells;
-        R.out_off = at; R.nx = g.nx; R.ny = g.ny;
-        b->tsub[(size_t)j] = TexturePending{grids[j], at};
-        at += (long long)align_up((size_t)g.nx * (size_t)g.ny, 8);
-    }
-    std::memcpy(b->h_seg[k], recs, sizeof(TextureRec) * (size_t)count);
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // write-combined stores drained before the doorbell
-    b->prepare_seconds = seconds_since(t_begin);
-    TextureBufs Tf;
-    Tf.seg = b->dv_seg[k]; Tf.cells = b->d_cells; Tf.table = b->d_tex; Tf.out = b->dv_tout; Tf.box = b->dv_tbox;
-    hipLaunchKernelGGL(kgb_texture, dim3((unsigned)count), dim3(KGT_THREADS), 0, b->stream, Tf);
-    G_TRY(b, hipGetLastError());
-    b->outstanding = true; b->kind = KIND_TEXTURE;
-    return RGRID_OK;
+    return submit_tail(b, KIND_TEXTURE, count, count, t_begin, [&] {
+        TextureBufs Tf;
+        Tf.seg = b->seg.buf[k].dv; Tf.cells = b->d_cells; Tf.table = b->tex.d_table; Tf.out = b->tex.out.dv; Tf.box = b->tex.box.dv;
+        hipLaunchKernelGGL(kgb_texture, dim3((unsigned)count), dim3(KGT_THREADS), 0, b->stream, Tf);
+    });
 }
 
 int rgrid_batch_texture_collect(rgrid_batch_t *b, int *boxes, double *slice_max, long *offsets, uint8_t *cells, long cap)
 {
-    if (!b || !b->outstanding || b->kind != KIND_TEXTURE) return RGRID_ERR_INVALID;
-    const int count = b->sub_count;
-    if (count > 0 && (!boxes || !slice_max || !offsets)) return RGRID_ERR_INVALID;
-    G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipStreamSynchronize(b->stream));                // the one wait: the kernel wrote boxes and pairs into host memory
+    int count = 0;
+    const int rc = collect_head(b, KIND_TEXTURE, boxes && slice_max && offsets, false, &count);   // the one wait: the kernel wrote boxes and pairs into host memory
+    if (rc != RGRID_OK) return rc;
     long total = 0;
     for (int j = 0; j < count; ++j) {
-        const GridSlot &g = b->grids[(size_t)b->tsub[(size_t)j].grid];
-        const int *box = b->h_tbox + 4 * j;
+        const GridSlot &g = b->grids[(size_t)b->tex.sub[(size_t)j].grid];
+        const int *box = b->tex.box.h + 4 * j;
         const int x0 = box[0], y0 = box[1];
         for (int c = 0; c < 4; ++c) boxes[4 * j + c] = box[c];
         slice_max[2 * j] = g.max_x - g.resolution * y0;                             // (probability_grid.cc:122-123), rgrid_draw_texture's expressions
@@ -1623,7 +1596,7 @@ int rgrid_batch_texture_collect(rgrid_batch_t *b, int *boxes, double *slice_max,
     if (total > cap || (total > 0 && !cells)) return RGRID_ERR_BUFFER;             // the submit stays pending: come again with room
     b->outstanding = false;
     for (int j = 0; j < count; ++j)
-        std::memcpy(cells + offsets[j], b->h_tout + b->tsub[(size_t)j].out_off, 2 * (size_t)boxes[4 * j + 2] * (size_t)boxes[4 * j + 3]);
+        std::memcpy(cells + offsets[j], b->tex.out.h + b->tex.sub[(size_t)j].out_off, 2 * (size_t)boxes[4 * j + 2] * (size_t)boxes[4 * j + 3]);
     return RGRID_OK;
 }
 

@@ -245,6 +245,89 @@ def test_per_scan_status_and_whole_call_refusals(fm, single):
     assert fm.last_prepare_seconds() > 0.0
 
 
+def test_a_pending_submit_of_any_of_the_six_kinds_refuses_everything_but_its_own_collect():
+    """Kind x kind over match, refine, scan_match, insert, filter and texture, each pending once with a launch and once as a submit
+    whose every scan is refused (nothing is launched, the collect gives the per-scan statuses): every submit, every other collect,
+    SetGrid, set_reduction, GetLimits and GetGrid are refused and leave it pending; its own collect succeeds once."""
+    from reflector_ekf_slam_amd import fleet_match as M
+    from tests import fleet_filter_scan_cases as FC
+    from tests import fleet_texture_cases as TC
+    grids = MC.grids()
+    spare = 2                                                                      # the insert's slot: no match or texture names it
+    m = M.ScanMatchFleet(max_scans=4, max_points=64, num_grids=3, max_cells=480 * 480)
+    for slot in (0, 1, spare):
+        m.SetGrid(slot, *grids[slot % 2][:3])
+    mgood = MC.tile_scans(3, 64)
+    rgood = [(slot, pose[:2].copy(), pose, pts) for slot, pose, pts in mgood]
+    igood = [(spare, (0.0, 0.0), grids[0][3][:40].astype(np.float32), None)]
+    fgood = [(pts, None) for _, _, pts in mgood]
+    tgood = [0, 1, 0]
+    # what each kind gives with nothing else going on, computed once
+    want = {"match": m.match(mgood), "refine": m.refine(rgood), "scan_match": m.scan_match(mgood), "filter": m.filter(fgood),
+            "texture": m.draw_textures(tgood)}
+    assert m.insert(igood) == [0]
+    inserted = m.GetGrid(spare)
+    assert not np.array_equal(inserted, grids[0][0])
+    m.SetGrid(spare, *grids[0][:3])
+    same = {"match": lambda out, w: all(MC.same_bits(a, b) for a, b in zip(out, w)),
+            "refine": lambda out, w: all(RC.same_refine_bits(a, b) for a, b in zip(out, w)),
+            "scan_match": lambda out, w: all(MC.same_bits(a.coarse, b.coarse) and RC.same_refine_bits(a.fine, b.fine) for a, b in zip(out, w)),
+            "filter": lambda out, w: all(FC.same_results(a, b) for a, b in zip(out, w)),
+            "texture": lambda out, w: all(TC.same_texture(a, b) for a, b in zip(out, w))}
+    submits = {"match": lambda: m.submit_code(mgood), "refine": lambda: m.submit_refine_code(rgood),
+               "scan_match": lambda: m.submit_scan_match_code(mgood), "insert": lambda: m.submit_insert_code(igood),
+               "filter": lambda: m.submit_filter_code(fgood), "texture": lambda: m.submit_texture_code(tgood)}
+    collects = {"match": m.collect_code, "refine": m.collect_refine_code, "scan_match": m.collect_scan_match_code,
+                "insert": m.collect_insert_code, "filter": m.collect_filter_code, "texture": m.collect_texture_code}
+    # a submit of each kind that launches nothing, and the statuses its collect gives (the texture has no per-slot refusal: no slot)
+    none, too_many, nan = np.zeros((0, 2), np.float32), np.zeros((65, 2), np.float32), np.array([[np.nan, 0.0]], np.float32)
+    refused = {"match": (lambda: m.submit_code([(0, np.zeros(3), none), (0, np.zeros(3), too_many)]), [EMPTY, CAPACITY]),
+               "refine": (lambda: m.submit_refine_code([(0, np.zeros(2), np.zeros(3), none), (0, np.zeros(2), np.zeros(3), too_many)]), [EMPTY, CAPACITY]),
+               "scan_match": (lambda: m.submit_scan_match_code([(0, np.zeros(3), none), (0, np.zeros(3), too_many)]), [EMPTY, CAPACITY]),
+               "insert": (lambda: m.submit_insert_code([(spare, (0.0, 0.0), nan, None), (0, (0.0, 0.0), np.array([[500.0, 0.0]], np.float32), None)]),
+                          [INVALID, CAPACITY]),
+               "filter": (lambda: m.submit_filter_code([(too_many, None), (nan, None)]), [CAPACITY, INVALID]),
+               "texture": (lambda: m.submit_texture_code([]), [])}
+    room = np.zeros(480 * 480, np.uint16)
+
+    def everything_else_is_refused(kind):
+        for other in submits:
+            assert submits[other]() == INVALID, (kind, other)
+        assert m.SetGrid_code(0, *grids[0][:3]) == INVALID                          # no grid changes under a launch
+        with pytest.raises(M.RgridError):
+            m.set_reduction(M.REDUCE_LAUNCH)
+        assert m.GetLimits_code(0)[0] == INVALID and m.GetGrid_code(0)[0] == INVALID
+        assert M._insert_lib().rgrid_batch_get_grid(m._h, 0, room.ctypes.data, room.size) == INVALID
+        for other in collects:
+            if other != kind:
+                assert collects[other]()[0] == INVALID, (kind, other)
+
+    for kind in submits:
+        assert submits[kind]() == 0
+        everything_else_is_refused(kind)
+        rc, out = collects[kind]()                                                 # ... and all of that left it pending
+        assert rc == 0 and len(out) == len(igood if kind == "insert" else mgood)
+        if kind == "insert":
+            assert out == [0] and np.array_equal(m.GetGrid(spare), inserted)
+            m.SetGrid(spare, *grids[0][:3])
+        else:
+            assert same[kind](out, want[kind]), kind
+        assert collects[kind]()[0] == INVALID                                      # collected: nothing is pending
+        submit, statuses = refused[kind]
+        assert submit() == 0
+        everything_else_is_refused(kind)
+        rc, out = collects[kind]()
+        assert rc == 0 and [r if kind == "insert" else r.status for r in out] == statuses, kind
+        assert collects[kind]()[0] == INVALID
+    for slot in (0, 1, spare):                                                     # no refused scan touched its slot
+        assert np.array_equal(m.GetGrid(slot), grids[slot % 2][0])
+    for kind in want:
+        assert submits[kind]() == 0
+        rc, out = collects[kind]()
+        assert rc == 0 and same[kind](out, want[kind]), kind
+    m.close()
+
+
 def test_end_to_end_into_the_fleet_filter():
     """predict_poses -> ScanMatchFleet.scan_match -> pose_fixes -> scan_event(pose_fix=...) -> submit for six members, against a
     twin fleet whose fixes come from six GridFrontEnd handles (Match, then RefineMatch): the same bits in mu and in the pose
