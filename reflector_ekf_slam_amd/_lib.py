@@ -29,25 +29,104 @@ def lib_path(name: str) -> str:
     return os.path.join(_HERE, name)
 
 
-_rekf = None
+_REBUILD = "rebuild it (python __graft_entry__.py); there is no CPU fallback"
 
 
-def rekf():
-    """librekf.so with argtypes set.  Raises LibraryMissing when it was not built."""
-    global _rekf
-    if _rekf is not None:
-        return _rekf
-    path = lib_path("librekf.so")
-    if not os.path.exists(path):
-        raise LibraryMissing(f"{path} not found: the HIP extension is not built "
-                             "(run `python __graft_entry__.py`); there is no CPU fallback")
-    L = C.CDLL(path)
+class _Loader:
+    """A library with its argtypes set, made on the first call and kept in ``ready``; a call that raises leaves ``ready`` None."""
+    ready = None
+
+    def __call__(self):
+        if self.ready is None:
+            self.ready = self._load()
+        return self.ready
+
+    def _checked(self, L, name):
+        """L after the by-name and structure-size checks and ``declare``."""
+        missing = [n for n in (*self.names, *(call for call, _ in self.sizes)) if not hasattr(L, n)]
+        if missing:
+            raise LibraryMissing(f"{name} has no {', '.join(missing)}: {_REBUILD}")
+        for call, struct in self.sizes:
+            have = getattr(L, call)()
+            if have != C.sizeof(struct):
+                raise LibraryMissing(f"{name}: {call}() is {have} bytes, this package packs {struct.__name__} in {C.sizeof(struct)}: {_REBUILD}")
+        self.declare(L)
+        return L
+
+
+class Library(_Loader):
+    """Root loader of ``file_name``: the file exists, loads, answers ``abi = (call, version)`` when one is given, and agrees on every
+    ``(sizeof call, ctypes.Structure)`` of ``sizes``; then ``declare(L)`` sets the argtypes."""
+
+    def __init__(self, file_name, abi, declare, sizes=()):
+        self.file_name, self.abi, self.declare, self.names, self.sizes = file_name, abi, declare, (), sizes
+        self.__doc__ = declare.__doc__
+
+    def _load(self):
+        path = lib_path(self.file_name)
+        if not os.path.exists(path):
+            raise LibraryMissing(f"{path} not found, the HIP extension is not built: {_REBUILD}")
+        L = C.CDLL(path)
+        if self.abi is not None:
+            have = getattr(L, self.abi[0])()
+            if have != self.abi[1]:
+                raise LibraryMissing(f"{path} has ABI version {have}, this package speaks {self.abi[1]}: {_REBUILD}")
+        return self._checked(L, path)
+
+
+class Feature(_Loader):
+    """Calls that were added to a library without a new ABI version and are looked up by name: ``base()`` (a Library or a Feature)
+    must have every one of ``names`` and agree on every ``(sizeof call, ctypes.Structure)`` of ``sizes``; then ``declare(L)`` sets
+    their argtypes.  A library without them is reported on their first use only; every other call keeps working."""
+
+    def __init__(self, base, library_name, names, sizes, declare):
+        self.base, self.library_name, self.names, self.sizes, self.declare = base, library_name, names, sizes, declare
+        self.__doc__ = declare.__doc__
+
+    def _load(self):
+        return self._checked(self.base(), self.library_name)
+
+
+class Handle:
+    """Owner of one C handle: ``_L`` the library, ``_h`` the handle, ``_destroy`` the name of the call that frees it.  A class
+    says in ``_error`` which exception ``_chk`` raises for a code; one with submit/collect pairs keeps the submit that has not been
+    collected in ``_pending``."""
+    _L = _h = _destroy = _pending = None
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _error(self, rc, where):
+        return RuntimeError(f"{where}: error {rc}")
+
+    def _chk(self, rc, where):
+        if rc != 0:
+            raise self._error(rc, where)
+
+    def _submitted(self, rc, pending):
+        """The tail of a submit: one that returned 0 is the pending one."""
+        if rc == 0:
+            self._pending = pending
+        return rc
+
+    def _collected(self, rc):
+        """The head of a collect: one that returned 0 has taken the pending submit."""
+        if rc == 0:
+            self._pending = None
+        return rc
+
+
+def _declare_rekf(L):
+    """librekf.so with argtypes set.  Raises LibraryMissing when it was not built or speaks another ABI version."""
     vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
-    L.rekf_abi_version.restype = C.c_int
-    have = L.rekf_abi_version()
-    if have != REKF_ABI_VERSION:
-        raise LibraryMissing(f"{path} has ABI version {have}, this package speaks {REKF_ABI_VERSION}: rebuild it "
-                             "(python __graft_entry__.py); there is no CPU fallback")
     L.rekf_strerror.restype = C.c_char_p
     L.rekf_strerror.argtypes = [C.c_int]
     L.rekf_last_hip_error.restype = C.c_char_p
@@ -85,5 +164,6 @@ def rekf():
         L.rekf_debug_inject_failure.argtypes = [vp, C.c_int]
     if hasattr(L, "rekf_debug_set_grid"):
         L.rekf_debug_set_grid.argtypes = [vp, C.c_int, C.c_double, C.c_int]
-    _rekf = L
-    return L
+
+
+rekf = Library("librekf.so", ("rekf_abi_version", REKF_ABI_VERSION), _declare_rekf)

@@ -6,7 +6,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -32,17 +31,8 @@ class Rdet3dOptions(C.Structure):
     _fields_ = [("intensity_min", C.c_double)]
 
 
-_lib_rdet = None
-
-
-def _rdet():
-    global _lib_rdet
-    if _lib_rdet is not None:
-        return _lib_rdet
-    path = _lib.lib_path("librdet.so")
-    if not os.path.exists(path):
-        raise _lib.LibraryMissing(f"{path} not found: run `python __graft_entry__.py`; there is no CPU fallback")
-    L = C.CDLL(path)
+def _declare_rdet(L):
+    """librdet.so with argtypes set.  Raises LibraryMissing when it was not built."""
     vp, fp, dp, ip = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)
     L.rdet_strerror.restype = C.c_char_p
     L.rdet_strerror.argtypes = [C.c_int]
@@ -63,8 +53,9 @@ def _rdet():
         L.rdet3d_collect.argtypes = [vp, vp, C.c_int, vp, vp]
         L.rdet3d_debug_set_path.argtypes = [vp, C.c_int]
         L.rdet3d_debug_path_counts.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
-    _lib_rdet = L
-    return L
+
+
+_rdet = _lib.Library("librdet.so", None, _declare_rdet)
 
 
 @dataclass
@@ -131,8 +122,9 @@ def _result_slots(det):
     return out
 
 
-class LaserReflectorDetect:
+class LaserReflectorDetect(_lib.Handle):
     """reflector_detect::LaserReflectorDetect (laser_reflector_detect.h:17-31)."""
+    _destroy = "rdet2d_destroy"
 
     def __init__(self, options: ReflectorDetectOptions, max_beams: int = 8192, device: int = 0,
                  sensor_to_base_link=(0.0, 0.0, 0.0)):
@@ -147,17 +139,6 @@ class LaserReflectorDetect:
             raise RdetError(rc, "rdet2d_create")
         self._h = h
         self._s2b = np.array(sensor_to_base_link, dtype=np.float64)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.rdet2d_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def SetSensorToBaseLinkTransform(self, xyyaw):
         """Takes the transform already projected with ``project2d`` (x, y, yaw)."""
@@ -203,8 +184,9 @@ class LaserReflectorDetect:
         return RangeData(np.array(origin[:], dtype=np.float32), ret[: n.value].copy())
 
 
-class PointCloudReflectorDetect:
+class PointCloudReflectorDetect(_lib.Handle):
     """reflector_detect::PointCloudReflectorDetect (point_cloud_reflector_detect.h:42-52)."""
+    _destroy = "rdet3d_destroy"
 
     def __init__(self, options: PointCloudOptions, max_points: int = 65536, device: int = 0,
                  sensor_to_base_link=(0.0, 0.0, 0.0)):
@@ -217,17 +199,6 @@ class PointCloudReflectorDetect:
         if rc != 0:
             raise RdetError(rc, "rdet3d_create")
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.rdet3d_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def HandlePointCloud(self, stamp: float, xyzi) -> Observation:
         pts = _as_f32(xyzi)

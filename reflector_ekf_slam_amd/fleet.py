@@ -12,7 +12,6 @@ All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fa
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -32,29 +31,9 @@ class RfleetEvent(C.Structure):
                 ("xy", C.c_void_p), ("K", C.c_int), ("has_pose_fix", C.c_int), ("pose_fix", C.c_double * 3)]
 
 
-_rfleet = None
-
-
-def rfleet():
+def _declare_rfleet(L):
     """librfleet.so with argtypes set.  Raises LibraryMissing when it was not built or speaks another ABI version."""
-    global _rfleet
-    if _rfleet is not None:
-        return _rfleet
-    path = _lib.lib_path("librfleet.so")
-    if not os.path.exists(path):
-        raise _lib.LibraryMissing(f"{path} not found: the HIP extension is not built "
-                                  "(run `python __graft_entry__.py`); there is no CPU fallback")
-    L = C.CDLL(path)
     vp, ip = C.c_void_p, C.POINTER(C.c_int)
-    L.rfleet_abi_version.restype = C.c_int
-    have = L.rfleet_abi_version()
-    if have != RFLEET_ABI_VERSION:
-        raise _lib.LibraryMissing(f"{path} has ABI version {have}, this package speaks {RFLEET_ABI_VERSION}: rebuild it "
-                                  "(python __graft_entry__.py); there is no CPU fallback")
-    L.rfleet_sizeof_event.restype = C.c_int
-    if L.rfleet_sizeof_event() != C.sizeof(RfleetEvent):
-        raise _lib.LibraryMissing(f"{path}: struct rfleet_event has {L.rfleet_sizeof_event()} bytes, this package packs "
-                                  f"{C.sizeof(RfleetEvent)}: rebuild it (python __graft_entry__.py)")
     L.rfleet_last_hip_error.restype = C.c_char_p
     L.rfleet_last_hip_error.argtypes = [vp]
     L.rfleet_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -70,27 +49,19 @@ def rfleet():
     L.rfleet_get_last_match.argtypes = [vp, C.c_int, ip, vp, ip, vp, ip, vp]
     L.rfleet_sync.argtypes = [vp]
     L.rfleet_size.argtypes = [vp, ip, ip]
-    _rfleet = L
-    return L
 
 
-_map_ready = None
+rfleet = _lib.Library("librfleet.so", ("rfleet_abi_version", RFLEET_ABI_VERSION), _declare_rfleet, [("rfleet_sizeof_event", RfleetEvent)])
 
 
-def _map_lib():
+def _declare_map(L):
     """``rfleet()`` with the argtypes of the map calls set.  They were added without a new ABI version and are looked up by name:
     raises LibraryMissing when the built library has none; every other call keeps working then."""
-    global _map_ready
-    if _map_ready is not None:
-        return _map_ready
-    L = rfleet()
-    missing = [n for n in ("rfleet_set_map", "rfleet_get_map_size") if not hasattr(L, n)]
-    if missing:
-        raise _lib.LibraryMissing(f"librfleet.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
     L.rfleet_set_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.rfleet_get_map_size.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-    _map_ready = L
-    return L
+
+
+_map_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_set_map", "rfleet_get_map_size"), (), _declare_map)
 
 
 def odom_event(member, t, vx, vy, wz):
@@ -104,8 +75,9 @@ def scan_event(member, t, cloud, pose_fix=None):
     return (int(member), EV_SCAN, float(t), (0.0, 0.0, 0.0), cloud, tuple(float(v) for v in pose_fix))
 
 
-class ReflectorEKFSLAMFleet:
+class ReflectorEKFSLAMFleet(_lib.Handle):
     """B independent ekf::ReflectorEKFSLAM filters on one MI355X, one kernel launch per ``submit``."""
+    _destroy = "rfleet_destroy"
 
     def __init__(self, options_list, max_landmarks: int = MAX_LANDMARKS, device: int = 0):
         self._L = rfleet()
@@ -131,24 +103,11 @@ class ReflectorEKFSLAMFleet:
         self.B = B
         self.max_landmarks = int(max_landmarks)
 
-    # -- lifetime -----------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.rfleet_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def __len__(self):
         return self.B
 
-    def _chk(self, rc, where):
-        if rc != 0:
-            raise RekfError(rc, where, self._L.rfleet_last_hip_error(self._h).decode())
+    def _error(self, rc, where):
+        return RekfError(rc, where, self._L.rfleet_last_hip_error(self._h).decode())
 
     # -- the fleet interface --------------------------------------------------
     @staticmethod

@@ -46,23 +46,9 @@ class PointCloud:
     xyzi: np.ndarray
 
 
-_ready = None
-_ready3 = None
-
-
-def _batch_lib():
+def _declare_batch(L):
     """librdet.so with the rdet2d_batch_* argtypes set.  Raises LibraryMissing when it was not built, or was built without them."""
-    global _ready
-    if _ready is not None:
-        return _ready
-    L = _rdet()
-    if not hasattr(L, "rdet2d_batch_create"):
-        raise _lib.LibraryMissing("librdet.so has no rdet2d_batch_*: rebuild it (python __graft_entry__.py); there is no CPU fallback")
     vp, ip = C.c_void_p, C.POINTER(C.c_int)
-    L.rdet2d_batch_sizeof_scan.restype = C.c_int
-    if L.rdet2d_batch_sizeof_scan() != C.sizeof(Rdet2dScan):
-        raise _lib.LibraryMissing(f"librdet.so: struct rdet2d_scan has {L.rdet2d_batch_sizeof_scan()} bytes, this package packs "
-                                  f"{C.sizeof(Rdet2dScan)}: rebuild it (python __graft_entry__.py)")
     L.rdet2d_batch_last_hip_error.restype = C.c_char_p
     L.rdet2d_batch_last_hip_error.argtypes = [vp]
     L.rdet2d_batch_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -74,23 +60,14 @@ def _batch_lib():
     L.rdet2d_batch_submit.argtypes = [vp, vp, C.c_int]
     L.rdet2d_batch_collect.argtypes = [vp, vp, vp, vp, C.c_int, vp]
     L.rdet2d_batch_get_range_data.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip]
-    _ready = L
-    return L
 
 
-def _batch3_lib():
+_batch_lib = _lib.Feature(_rdet, "librdet.so", ("rdet2d_batch_create",), [("rdet2d_batch_sizeof_scan", Rdet2dScan)], _declare_batch)
+
+
+def _declare_batch3(L):
     """librdet.so with the rdet3d_batch_* argtypes set.  Raises LibraryMissing when it was not built, or was built without them."""
-    global _ready3
-    if _ready3 is not None:
-        return _ready3
-    L = _rdet()
-    if not hasattr(L, "rdet3d_batch_create") or not hasattr(L, "rdet3d_batch_sizeof_cloud"):
-        raise _lib.LibraryMissing("librdet.so has no rdet3d_batch_*: rebuild it (python __graft_entry__.py); there is no CPU fallback")
     vp = C.c_void_p
-    L.rdet3d_batch_sizeof_cloud.restype = C.c_int
-    if L.rdet3d_batch_sizeof_cloud() != C.sizeof(Rdet3dCloud):
-        raise _lib.LibraryMissing(f"librdet.so: struct rdet3d_cloud has {L.rdet3d_batch_sizeof_cloud()} bytes, this package packs "
-                                  f"{C.sizeof(Rdet3dCloud)}: rebuild it (python __graft_entry__.py)")
     L.rdet3d_batch_last_hip_error.restype = C.c_char_p
     L.rdet3d_batch_last_hip_error.argtypes = [vp]
     L.rdet3d_batch_max_bright.restype = C.c_int
@@ -101,8 +78,9 @@ def _batch3_lib():
     L.rdet3d_batch_staging.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.rdet3d_batch_submit.argtypes = [vp, vp, C.c_int]
     L.rdet3d_batch_collect.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
-    _ready3 = L
-    return L
+
+
+_batch3_lib = _lib.Feature(_rdet, "librdet.so", ("rdet3d_batch_create",), [("rdet3d_batch_sizeof_cloud", Rdet3dCloud)], _declare_batch3)
 
 
 def cloud_events(clouds, observations):
@@ -124,60 +102,96 @@ def scan_events(scans, observations):
     return [fleet.scan_event(member, obs.time_, obs.cloud_) for (member, _), (status, obs) in zip(scans, observations) if status == 0]
 
 
-class LaserReflectorDetectFleet:
-    """B reflector_detect::LaserReflectorDetect on one MI355X, one kernel launch per ``submit``."""
 
-    def __init__(self, options_list, max_beams: int = MAX_BEAMS, device: int = 0, sensor_to_base_link=None):
-        self._L = _batch_lib()
-        self._h = None
-        self.options = list(options_list)
-        B = len(self.options)
-        opts = (Rdet2dOptions * max(B, 1))()
-        for i, o in enumerate(self.options):
-            opts[i] = Rdet2dOptions(o.intensity_min, o.reflector_min_length, o.reflector_length_error, o.range_min, o.range_max)
+class _DetectFleet(_lib.Handle):
+    """What the two detector fleets share: a handle of the ``_prefix`` calls, made for one ``_Options`` per member, whose submit
+    takes the records of ``pack``."""
+    _prefix = _Options = None
+
+    def _create(self, L, opts, capacity, device, sensor_to_base_link):
+        """The handle for ``opts`` (one ``_Options`` per member); ``sensor_to_base_link``: None, one (x, y, yaw) for all, or [B, 3]."""
+        self._L, self._h = L, None
+        B = len(opts)
+        arr = (self._Options * max(B, 1))(*opts)
         if sensor_to_base_link is None:
             s2b = np.zeros((B, 3))
         else:
             s2b = np.array(sensor_to_base_link, dtype=np.float64)
             s2b = np.ascontiguousarray(np.broadcast_to(s2b, (B, 3))) if s2b.ndim == 1 else np.ascontiguousarray(s2b.reshape(B, 3))
         h = C.c_void_p()
-        rc = self._L.rdet2d_batch_create(C.cast(opts, C.c_void_p), s2b.ctypes.data if B else None, B, int(max_beams), int(device), C.byref(h))
+        rc = self._call("create")(C.cast(arr, C.c_void_p), s2b.ctypes.data if B else None, B, int(capacity), int(device), C.byref(h))
         if rc != 0:
-            raise RdetError(rc, "rdet2d_batch_create")
+            raise RdetError(rc, self._prefix + "_create")
         self._h = h
         self.B = B
-        self.max_beams = int(max_beams)
         self._s2b = s2b
         self._pending = None          # the submit that has not been collected: (records, arrays they point into, count)
         self._staging = {}
 
-    # -- lifetime -----------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.rdet2d_batch_destroy(self._h)
-            self._h = None
-            self._staging = {}
+    def _call(self, name):
+        return getattr(self._L, f"{self._prefix}_{name}")
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def close(self):
+        if self._h:
+            self._staging = {}
+        super().close()
 
     def __len__(self):
         return self.B
 
-    def _chk(self, rc, where):
-        if rc != 0:
-            detail = self._L.rdet2d_batch_last_hip_error(self._h).decode() if rc == -2 else ""
-            raise RdetError(rc, where + (": " + detail if detail else ""))
+    def _error(self, rc, where):
+        detail = self._call("last_hip_error")(self._h).decode() if rc == -2 else ""
+        return RdetError(rc, where + (": " + detail if detail else ""))
 
     # -- per member ---------------------------------------------------------
     def SetSensorToBaseLinkTransform(self, member: int, xyyaw):
         """Takes the transform already projected with ``detect.project2d`` (x, y, yaw)."""
         v = np.ascontiguousarray(xyyaw, dtype=np.float64).reshape(3)
-        self._chk(self._L.rdet2d_batch_set_sensor_to_base_link(self._h, int(member), v.ctypes.data), "SetSensorToBaseLinkTransform")
+        self._chk(self._call("set_sensor_to_base_link")(self._h, int(member), v.ctypes.data), "SetSensorToBaseLinkTransform")
         self._s2b[int(member)] = v
+
+    # -- the fleet interface --------------------------------------------------
+    def submit_code(self, scans) -> int:
+        arr, count, keep = self.pack(scans)
+        return self._submitted(self._call("submit")(self._h, C.cast(arr, C.c_void_p), count), (arr, keep, count))
+
+    def submit(self, scans):
+        """One scan of any subset of members, at most one per member: ONE kernel launch; returns without waiting for it."""
+        self._chk(self.submit_code(scans), self._prefix + "_submit")
+
+    def _collect(self, max_centers, *more):
+        """``collect_code`` with the addresses of the class's further per-scan result arrays in ``more``."""
+        count = self._pending[2] if self._pending else 0
+        n = max(count, 1)
+        mc = max(0, min(int(max_centers), MAX_CENTERS))
+        status, K, t = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        cen = np.zeros((n, max(mc, 1), 2), np.float32)
+        rc = self._call("collect")(self._h, status.ctypes.data, K.ctypes.data, cen.ctypes.data, mc, t.ctypes.data, *more)
+        if self._collected(rc) != 0:
+            return rc, []
+        return 0, [(int(status[i]), Observation(float(t[i]), cen[i, : int(K[i])].copy())) for i in range(count)]
+
+    def collect(self, max_centers: int = MAX_CENTERS):
+        """Waits for the launch: [(status, Observation)] in the order of the submit, status 0 or the entry's own error."""
+        rc, out = self.collect_code(max_centers)
+        self._chk(rc, self._prefix + "_collect")
+        return out
+
+    def detect(self, scans, max_centers: int = MAX_CENTERS):
+        self.submit(scans)
+        return self.collect(max_centers)
+
+
+class LaserReflectorDetectFleet(_DetectFleet):
+    """B reflector_detect::LaserReflectorDetect on one MI355X, one kernel launch per ``submit``."""
+    _prefix, _destroy, _Options = "rdet2d_batch", "rdet2d_batch_destroy", Rdet2dOptions
+
+    def __init__(self, options_list, max_beams: int = MAX_BEAMS, device: int = 0, sensor_to_base_link=None):
+        L = _batch_lib()
+        self.options = list(options_list)
+        opts = [Rdet2dOptions(o.intensity_min, o.reflector_min_length, o.reflector_length_error, o.range_min, o.range_max) for o in self.options]
+        self._create(L, opts, max_beams, device, sensor_to_base_link)
+        self.max_beams = int(max_beams)
 
     def HandleOdometryData(self, member: int, msg: OdometryData):
         pos = (C.c_double * 2)(float(msg.position[0]), float(msg.position[1]))
@@ -206,7 +220,6 @@ class LaserReflectorDetectFleet:
                   "GetRangeData")
         return RangeData(np.array(origin[:], dtype=np.float32), ret[: n.value].copy())
 
-    # -- the fleet interface --------------------------------------------------
     @staticmethod
     def pack(scans):
         """scans: iterable of (member, LaserScan).  -> (ctypes array of rdet2d_scan, count, the float32 arrays it points into)."""
@@ -227,102 +240,32 @@ class LaserReflectorDetectFleet:
             s.intensities = inten.ctypes.data if s.N else None
         return arr, len(scans), keep
 
-    def submit_code(self, scans) -> int:
-        arr, count, keep = self.pack(scans)
-        rc = self._L.rdet2d_batch_submit(self._h, C.cast(arr, C.c_void_p), count)
-        if rc == 0:
-            self._pending = (arr, keep, count)
-        return rc
-
-    def submit(self, scans):
-        """One scan of any subset of members, at most one per member: ONE kernel launch; returns without waiting for it."""
-        self._chk(self.submit_code(scans), "rdet2d_batch_submit")
-
     def collect_code(self, max_centers: int = MAX_CENTERS):
         """-> (rc, [(status, Observation)]) of the submit that has not been collected."""
-        count = self._pending[2] if self._pending else 0
-        n = max(count, 1)
-        mc = max(0, min(int(max_centers), MAX_CENTERS))
-        status, K, t = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
-        cen = np.zeros((n, max(mc, 1), 2), np.float32)
-        rc = self._L.rdet2d_batch_collect(self._h, status.ctypes.data, K.ctypes.data, cen.ctypes.data, mc, t.ctypes.data)
-        if rc != 0:
-            return rc, []
-        self._pending = None
-        return 0, [(int(status[i]), Observation(float(t[i]), cen[i, : int(K[i])].copy())) for i in range(count)]
+        return self._collect(max_centers)
 
     def collect(self, max_centers: int = MAX_CENTERS):
         """Waits for the launch: [(status, Observation)] in the order of the submitted scans.  status 0, or the scan's own error
         (-3: a malformed message, K = 0; -5: more centres than ``max_centers``; -4: more than 256 reflectors)."""
-        rc, out = self.collect_code(max_centers)
-        self._chk(rc, "rdet2d_batch_collect")
-        return out
-
-    def detect(self, scans, max_centers: int = MAX_CENTERS):
-        self.submit(scans)
-        return self.collect(max_centers)
+        return super().collect(max_centers)
 
 
-class PointCloudReflectorDetectFleet:
+class PointCloudReflectorDetectFleet(_DetectFleet):
     """B reflector_detect::PointCloudReflectorDetect on one MI355X, one kernel launch per ``submit``."""
+    _prefix, _destroy, _Options = "rdet3d_batch", "rdet3d_batch_destroy", Rdet3dOptions
 
     def __init__(self, options_list, max_points: int = 65536, device: int = 0, sensor_to_base_link=None):
-        self._L = _batch3_lib()
-        self._h = None
+        L = _batch3_lib()
         self.options_list = list(options_list)
-        B = len(self.options_list)
-        opts = (Rdet3dOptions * max(B, 1))()
-        for i, o in enumerate(self.options_list):
-            opts[i] = Rdet3dOptions(o.intensity_min)
-        if sensor_to_base_link is None:
-            s2b = np.zeros((B, 3))
-        else:
-            s2b = np.array(sensor_to_base_link, dtype=np.float64)
-            s2b = np.ascontiguousarray(np.broadcast_to(s2b, (B, 3))) if s2b.ndim == 1 else np.ascontiguousarray(s2b.reshape(B, 3))
-        h = C.c_void_p()
-        rc = self._L.rdet3d_batch_create(C.cast(opts, C.c_void_p), s2b.ctypes.data if B else None, B, int(max_points), int(device), C.byref(h))
-        if rc != 0:
-            raise RdetError(rc, "rdet3d_batch_create")
-        self._h = h
-        self.B = B
+        self._create(L, [Rdet3dOptions(o.intensity_min) for o in self.options_list], max_points, device, sensor_to_base_link)
         self.max_points = int(max_points)
-        self.sensor_to_base_link = s2b
+        self.sensor_to_base_link = self._s2b          # (the public name of this class; one array)
         self.last_n_bright = []       # the survivors of the intensity gate, per cloud of the last collect
-        self._pending = None          # the submit that has not been collected: (records, arrays they point into, count)
-        self._staging = {}
-
-    # -- lifetime -----------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.rdet3d_batch_destroy(self._h)
-            self._h = None
-            self._staging = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self):
-        return self.B
-
-    def _chk(self, rc, where):
-        if rc != 0:
-            detail = self._L.rdet3d_batch_last_hip_error(self._h).decode() if rc == -2 else ""
-            raise RdetError(rc, where + (": " + detail if detail else ""))
 
     @staticmethod
     def max_bright() -> int:
         """Survivors of the intensity gate a cloud may have (more: status -4, and the cloud goes through a PointCloudReflectorDetect)."""
         return int(_batch3_lib().rdet3d_batch_max_bright())
-
-    # -- per member ---------------------------------------------------------
-    def SetSensorToBaseLinkTransform(self, member: int, xyyaw):
-        """Takes the transform already projected with ``detect.project2d`` (x, y, yaw)."""
-        v = np.ascontiguousarray(xyyaw, dtype=np.float64).reshape(3)
-        self._chk(self._L.rdet3d_batch_set_sensor_to_base_link(self._h, int(member), v.ctypes.data), "SetSensorToBaseLinkTransform")
-        self.sensor_to_base_link[int(member)] = v
 
     def staging(self, member: int):
         """A (max_points, 4) float32 numpy view of the member's slice of the staging area.  A cloud that is a leading slice of this
@@ -335,7 +278,6 @@ class PointCloudReflectorDetectFleet:
             self._staging[member] = np.ctypeslib.as_array(tp.from_address(p.value)).reshape(self.max_points, 4)
         return self._staging[member]
 
-    # -- the fleet interface --------------------------------------------------
     @staticmethod
     def pack(clouds):
         """clouds: iterable of (member, stamp, xyzi) or (member, PointCloud).  -> (ctypes array of rdet3d_cloud, count, the float32
@@ -354,39 +296,27 @@ class PointCloudReflectorDetectFleet:
             c.xyzi = pts.ctypes.data if c.N else None
         return arr, len(clouds), keep
 
+    # (the 2D names with ``clouds`` for ``scans``: the keyword is this class's)
     def submit_code(self, clouds) -> int:
-        arr, count, keep = self.pack(clouds)
-        rc = self._L.rdet3d_batch_submit(self._h, C.cast(arr, C.c_void_p), count)
-        if rc == 0:
-            self._pending = (arr, keep, count)
-        return rc
+        return super().submit_code(clouds)
 
     def submit(self, clouds):
         """One cloud of any subset of members, at most one per member: ONE kernel launch; returns without waiting for it."""
-        self._chk(self.submit_code(clouds), "rdet3d_batch_submit")
+        super().submit(clouds)
+
+    def detect(self, clouds, max_centers: int = MAX_CENTERS):
+        return super().detect(clouds, max_centers)
 
     def collect_code(self, max_centers: int = MAX_CENTERS):
         """-> (rc, [(status, Observation)]) of the submit that has not been collected."""
-        count = self._pending[2] if self._pending else 0
-        n = max(count, 1)
-        mc = max(0, min(int(max_centers), MAX_CENTERS))
-        status, K, t, nb = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32)
-        cen = np.zeros((n, max(mc, 1), 2), np.float32)
-        rc = self._L.rdet3d_batch_collect(self._h, status.ctypes.data, K.ctypes.data, cen.ctypes.data, mc, t.ctypes.data, nb.ctypes.data)
-        if rc != 0:
-            return rc, []
-        self._pending = None
-        self.last_n_bright = [int(v) for v in nb[:count]]
-        return 0, [(int(status[i]), Observation(float(t[i]), cen[i, : int(K[i])].copy())) for i in range(count)]
+        nb = np.zeros(max(self._pending[2] if self._pending else 0, 1), np.int32)
+        rc, out = self._collect(max_centers, nb.ctypes.data)
+        if rc == 0:
+            self.last_n_bright = [int(v) for v in nb[:len(out)]]
+        return rc, out
 
     def collect(self, max_centers: int = MAX_CENTERS):
         """Waits for the launch: [(status, Observation)] in the order of the submitted clouds.  status 0, or the cloud's own error
         (-4: more than ``max_bright()`` survivors of the intensity gate -- ``last_n_bright`` holds the count -- or more than 256
         reflectors; -5: more centres than ``max_centers``)."""
-        rc, out = self.collect_code(max_centers)
-        self._chk(rc, "rdet3d_batch_collect")
-        return out
-
-    def detect(self, clouds, max_centers: int = MAX_CENTERS):
-        self.submit(clouds)
-        return self.collect(max_centers)
+        return super().collect(max_centers)

@@ -132,26 +132,9 @@ class FleetScanMatchResult:
         return self.coarse.status
 
 
-_ready = None
-_refine_ready = None
-_insert_ready = None
-_filter_ready = None
-_texture_ready = None
-
-
-def _batch_lib():
+def _declare_batch(L):
     """librgrid.so with the rgrid_batch_* argtypes set.  Raises LibraryMissing when it was not built, or was built without them."""
-    global _ready
-    if _ready is not None:
-        return _ready
-    L = _lib_rgrid()
-    if not hasattr(L, "rgrid_batch_create"):
-        raise _lib.LibraryMissing("librgrid.so has no rgrid_batch_*: rebuild it (python __graft_entry__.py); there is no CPU fallback")
     vp = C.c_void_p
-    L.rgrid_batch_sizeof_scan.restype = C.c_int
-    if L.rgrid_batch_sizeof_scan() != C.sizeof(RgridBatchScan):
-        raise _lib.LibraryMissing(f"librgrid.so: struct rgrid_batch_scan has {L.rgrid_batch_sizeof_scan()} bytes, this package packs "
-                                  f"{C.sizeof(RgridBatchScan)}: rebuild it (python __graft_entry__.py)")
     L.rgrid_batch_last_hip_error.restype = C.c_char_p
     L.rgrid_batch_last_hip_error.argtypes = [vp]
     L.rgrid_batch_last_prepare_seconds.restype = C.c_double
@@ -163,100 +146,64 @@ def _batch_lib():
     L.rgrid_batch_set_reduction.argtypes = [vp, C.c_int]
     L.rgrid_batch_match_submit.argtypes = [vp, C.POINTER(_MatchOptions), vp, C.c_int]
     L.rgrid_batch_match_collect.argtypes = [vp, vp, vp, vp, vp, vp]
-    _ready = L
-    return L
 
 
-def _refine_lib():
+_batch_lib = _lib.Feature(_lib_rgrid, "librgrid.so", ("rgrid_batch_create",), [("rgrid_batch_sizeof_scan", RgridBatchScan)], _declare_batch)
+
+
+def _declare_refine(L):
     """``_batch_lib()`` with the argtypes of the refine and match-plus-refine calls set.  Raises LibraryMissing when the built library
     has no such calls (the ABI version does not tell: they are looked up by name); the match calls keep working then."""
-    global _refine_ready
-    if _refine_ready is not None:
-        return _refine_ready
-    L = _batch_lib()
-    names = ("rgrid_batch_refine_submit", "rgrid_batch_refine_collect", "rgrid_batch_scan_match_submit",
-             "rgrid_batch_scan_match_collect", "rgrid_batch_sizeof_refine_scan")
-    missing = [n for n in names if not hasattr(L, n)]
-    if missing:
-        raise _lib.LibraryMissing(f"librgrid.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
-    L.rgrid_batch_sizeof_refine_scan.restype = C.c_int
-    if L.rgrid_batch_sizeof_refine_scan() != C.sizeof(RgridBatchRefineScan):
-        raise _lib.LibraryMissing(f"librgrid.so: struct rgrid_batch_refine_scan has {L.rgrid_batch_sizeof_refine_scan()} bytes, this package "
-                                  f"packs {C.sizeof(RgridBatchRefineScan)}: rebuild it (python __graft_entry__.py)")
     vp = C.c_void_p
     L.rgrid_batch_refine_submit.argtypes = [vp, C.POINTER(_RefineOptions), vp, C.c_int]
     L.rgrid_batch_refine_collect.argtypes = [vp, vp, vp, vp]
     L.rgrid_batch_scan_match_submit.argtypes = [vp, C.POINTER(_MatchOptions), C.POINTER(_RefineOptions), vp, C.c_int]
     L.rgrid_batch_scan_match_collect.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    _refine_ready = L
-    return L
 
 
-def _insert_lib():
+_refine_lib = _lib.Feature(_batch_lib, "librgrid.so",
+                           ("rgrid_batch_refine_submit", "rgrid_batch_refine_collect", "rgrid_batch_scan_match_submit", "rgrid_batch_scan_match_collect"),
+                           [("rgrid_batch_sizeof_refine_scan", RgridBatchRefineScan)], _declare_refine)
+
+
+def _declare_insert(L):
     """``_batch_lib()`` with the argtypes of the insert calls and the slot read-backs set.  Raises LibraryMissing when the built
     library has no such calls or packs another structure (they are looked up by name); every other call keeps working then."""
-    global _insert_ready
-    if _insert_ready is not None:
-        return _insert_ready
-    L = _batch_lib()
-    names = ("rgrid_batch_insert_submit", "rgrid_batch_insert_collect", "rgrid_batch_get_limits", "rgrid_batch_get_grid",
-             "rgrid_batch_sizeof_insert_scan")
-    missing = [n for n in names if not hasattr(L, n)]
-    if missing:
-        raise _lib.LibraryMissing(f"librgrid.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
-    L.rgrid_batch_sizeof_insert_scan.restype = C.c_int
-    if L.rgrid_batch_sizeof_insert_scan() != C.sizeof(RgridBatchInsertScan):
-        raise _lib.LibraryMissing(f"librgrid.so: struct rgrid_batch_insert_scan has {L.rgrid_batch_sizeof_insert_scan()} bytes, this package "
-                                  f"packs {C.sizeof(RgridBatchInsertScan)}: rebuild it (python __graft_entry__.py)")
     vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
     L.rgrid_batch_insert_submit.argtypes = [vp, C.POINTER(_InsertOptions), vp, C.c_int]
     L.rgrid_batch_insert_collect.argtypes = [vp, vp]
     L.rgrid_batch_get_limits.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp]
     L.rgrid_batch_get_grid.argtypes = [vp, C.c_int, vp, C.c_long]
-    _insert_ready = L
-    return L
 
 
-def _filter_lib():
+_insert_lib = _lib.Feature(_batch_lib, "librgrid.so",
+                           ("rgrid_batch_insert_submit", "rgrid_batch_insert_collect", "rgrid_batch_get_limits", "rgrid_batch_get_grid"),
+                           [("rgrid_batch_sizeof_insert_scan", RgridBatchInsertScan)], _declare_insert)
+
+
+def _declare_filter(L):
     """``_batch_lib()`` with the argtypes of the filter calls set.  Raises LibraryMissing when the built library has no such calls or
     packs another structure (they are looked up by name); every other call keeps working then."""
-    global _filter_ready
-    if _filter_ready is not None:
-        return _filter_ready
-    L = _batch_lib()
-    names = ("rgrid_batch_filter_submit", "rgrid_batch_filter_collect", "rgrid_batch_filter_max_points", "rgrid_batch_sizeof_filter_scan")
-    missing = [n for n in names if not hasattr(L, n)]
-    if missing:
-        raise _lib.LibraryMissing(f"librgrid.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
-    L.rgrid_batch_sizeof_filter_scan.restype = C.c_int
-    if L.rgrid_batch_sizeof_filter_scan() != C.sizeof(RgridBatchFilterScan):
-        raise _lib.LibraryMissing(f"librgrid.so: struct rgrid_batch_filter_scan has {L.rgrid_batch_sizeof_filter_scan()} bytes, this package "
-                                  f"packs {C.sizeof(RgridBatchFilterScan)}: rebuild it (python __graft_entry__.py)")
     vp = C.c_void_p
     L.rgrid_batch_filter_max_points.restype = C.c_int
     L.rgrid_batch_filter_max_points.argtypes = []
     L.rgrid_batch_filter_submit.argtypes = [vp, C.POINTER(_FilterOptions), vp, C.c_int]
     L.rgrid_batch_filter_collect.argtypes = [vp, vp, vp, vp, C.c_long]
-    _filter_ready = L
-    return L
 
 
-def _texture_lib():
+_filter_lib = _lib.Feature(_batch_lib, "librgrid.so", ("rgrid_batch_filter_submit", "rgrid_batch_filter_collect", "rgrid_batch_filter_max_points"),
+                           [("rgrid_batch_sizeof_filter_scan", RgridBatchFilterScan)], _declare_filter)
+
+
+def _declare_texture(L):
     """``_batch_lib()`` with the argtypes of the texture calls set.  Raises LibraryMissing when the built library has no such calls
     (they are looked up by name); every other call keeps working then."""
-    global _texture_ready
-    if _texture_ready is not None:
-        return _texture_ready
-    L = _batch_lib()
-    names = ("rgrid_batch_texture_submit", "rgrid_batch_texture_collect")
-    missing = [n for n in names if not hasattr(L, n)]
-    if missing:
-        raise _lib.LibraryMissing(f"librgrid.so has no {', '.join(missing)}: rebuild it (python __graft_entry__.py); there is no CPU fallback")
     vp = C.c_void_p
     L.rgrid_batch_texture_submit.argtypes = [vp, vp, C.c_int]
     L.rgrid_batch_texture_collect.argtypes = [vp, vp, vp, vp, vp, C.c_long]
-    _texture_ready = L
-    return L
+
+
+_texture_lib = _lib.Feature(_batch_lib, "librgrid.so", ("rgrid_batch_texture_submit", "rgrid_batch_texture_collect"), (), _declare_texture)
 
 
 def filter_max_points() -> int:
@@ -310,8 +257,9 @@ def pose_fixes(results):
     return [tuple(float(v) for v in r.pose_estimate) if r.status == RGRID_OK else None for r in results]
 
 
-class ScanMatchFleet:
+class ScanMatchFleet(_lib.Handle):
     """One batch handle of include/rgrid.h: the real-time correlative scan matcher for up to ``max_scans`` scans per launch."""
+    _destroy = "rgrid_batch_destroy"
 
     def __init__(self, max_scans: int, max_points: int = 8192, num_grids: int = 1, max_cells: int = 1024 * 1024,
                  max_rotations: int = 256, device: int = 0):
@@ -327,22 +275,9 @@ class ScanMatchFleet:
         self._pending = None          # the submit that has not been collected: its scan count
         self._set_slots = set()       # the slots SetGrid has filled: what draw_textures draws by default
 
-    # -- lifetime -----------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.rgrid_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, where):
-        if rc != 0:
-            raise RgridError(rc, where, self._L.rgrid_batch_last_hip_error(self._h).decode() if rc == -2 else
-                             self._L.rgrid_strerror(rc).decode())
+    def _error(self, rc, where):
+        return RgridError(rc, where, self._L.rgrid_batch_last_hip_error(self._h).decode() if rc == -2 else
+                          self._L.rgrid_strerror(rc).decode())
 
     # -- grids ----------------------------------------------------------------
     def SetGrid_code(self, slot: int, cells, resolution: float, max_xy) -> int:
@@ -382,13 +317,8 @@ class ScanMatchFleet:
 
     def submit_packed_code(self, packed, options: RealTimeCorrelativeScanMatcherOptions | None = None) -> int:
         """``submit_code`` for what ``pack`` returned (reusable: the points are copied by the call)."""
-        o = options or RealTimeCorrelativeScanMatcherOptions()
-        co = _MatchOptions(o.linear_search_window, o.angular_search_window, o.translation_delta_cost_weight,
-                           o.rotation_delta_cost_weight)
-        rc = self._L.rgrid_batch_match_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1])
-        if rc == 0:
-            self._pending = packed[1]
-        return rc
+        co = _match_options(options)
+        return self._submitted(self._L.rgrid_batch_match_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1]), packed[1])
 
     def submit_code(self, scans, options: RealTimeCorrelativeScanMatcherOptions | None = None) -> int:
         return self.submit_packed_code(self.pack(scans), options)
@@ -403,11 +333,10 @@ class ScanMatchFleet:
         n = max(count, 1)
         status, pose, score = np.zeros(n, np.int32), np.zeros((n, 3)), np.zeros(n)
         best, info = np.zeros((n, 3), np.int32), np.zeros((n, 3), np.int32)
-        rc = self._L.rgrid_batch_match_collect(self._h, status.ctypes.data, pose.ctypes.data, score.ctypes.data, best.ctypes.data,
-                                               info.ctypes.data)
+        rc = self._collected(self._L.rgrid_batch_match_collect(self._h, status.ctypes.data, pose.ctypes.data, score.ctypes.data,
+                                                               best.ctypes.data, info.ctypes.data))
         if rc != 0:
             return rc, []
-        self._pending = None
         return 0, [FleetMatchResult(float(score[i]), pose[i].copy(), tuple(int(v) for v in best[i]), tuple(int(v) for v in info[i]),
                                     int(status[i])) for i in range(count)]
 
@@ -441,10 +370,7 @@ class ScanMatchFleet:
 
     def submit_refine_packed_code(self, packed, options: CeresScanMatcherOptions2D | None = None) -> int:
         co = _refine_options(options)
-        rc = _refine_lib().rgrid_batch_refine_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1])
-        if rc == 0:
-            self._pending = packed[1]
-        return rc
+        return self._submitted(_refine_lib().rgrid_batch_refine_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1]), packed[1])
 
     def submit_refine_code(self, scans, options: CeresScanMatcherOptions2D | None = None) -> int:
         return self.submit_refine_packed_code(self.pack_refine(scans), options)
@@ -458,10 +384,9 @@ class ScanMatchFleet:
         count = self._pending or 0
         n = max(count, 1)
         status, pose, summ = np.zeros(n, np.int32), np.zeros((n, 3)), (_RefineSummary * n)()
-        rc = _refine_lib().rgrid_batch_refine_collect(self._h, status.ctypes.data, pose.ctypes.data, C.cast(summ, C.c_void_p))
+        rc = self._collected(_refine_lib().rgrid_batch_refine_collect(self._h, status.ctypes.data, pose.ctypes.data, C.cast(summ, C.c_void_p)))
         if rc != 0:
             return rc, []
-        self._pending = None
         return 0, _refine_results(count, status, pose, summ)
 
     def collect_refine(self):
@@ -478,10 +403,8 @@ class ScanMatchFleet:
                                       refine_options: CeresScanMatcherOptions2D | None = None) -> int:
         """``submit_scan_match_code`` for what ``pack`` returned."""
         cm, cr = _match_options(match_options), _refine_options(refine_options)
-        rc = _refine_lib().rgrid_batch_scan_match_submit(self._h, C.byref(cm), C.byref(cr), C.cast(packed[0], C.c_void_p), packed[1])
-        if rc == 0:
-            self._pending = packed[1]
-        return rc
+        return self._submitted(_refine_lib().rgrid_batch_scan_match_submit(self._h, C.byref(cm), C.byref(cr), C.cast(packed[0], C.c_void_p), packed[1]),
+                               packed[1])
 
     def submit_scan_match_code(self, scans, match_options=None, refine_options=None) -> int:
         return self.submit_scan_match_packed_code(self.pack(scans), match_options, refine_options)
@@ -499,11 +422,11 @@ class ScanMatchFleet:
         status, coarse, score = np.zeros(n, np.int32), np.zeros((n, 3)), np.zeros(n)
         best, info = np.zeros((n, 3), np.int32), np.zeros((n, 3), np.int32)
         pose, summ = np.zeros((n, 3)), (_RefineSummary * n)()
-        rc = _refine_lib().rgrid_batch_scan_match_collect(self._h, status.ctypes.data, coarse.ctypes.data, score.ctypes.data,
-                                                          best.ctypes.data, info.ctypes.data, pose.ctypes.data, C.cast(summ, C.c_void_p))
+        rc = self._collected(_refine_lib().rgrid_batch_scan_match_collect(
+            self._h, status.ctypes.data, coarse.ctypes.data, score.ctypes.data, best.ctypes.data, info.ctypes.data, pose.ctypes.data,
+            C.cast(summ, C.c_void_p)))
         if rc != 0:
             return rc, []
-        self._pending = None
         fine = _refine_results(count, status, pose, summ)
         return 0, [FleetScanMatchResult(FleetMatchResult(float(score[i]), coarse[i].copy(), tuple(int(v) for v in best[i]),
                                                          tuple(int(v) for v in info[i]), int(status[i])), fine[i]) for i in range(count)]
@@ -540,10 +463,7 @@ class ScanMatchFleet:
     def submit_insert_packed_code(self, packed, options: RangeDataInserterOptions | None = None) -> int:
         """``submit_insert_code`` for what ``pack_insert`` returned (reusable: the points are copied by the call)."""
         co = _insert_options(options)
-        rc = _insert_lib().rgrid_batch_insert_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1])
-        if rc == 0:
-            self._pending = packed[1]
-        return rc
+        return self._submitted(_insert_lib().rgrid_batch_insert_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1]), packed[1])
 
     def submit_insert_code(self, scans, options: RangeDataInserterOptions | None = None) -> int:
         return self.submit_insert_packed_code(self.pack_insert(scans), options)
@@ -556,10 +476,9 @@ class ScanMatchFleet:
         """-> (rc, [status]) of the insert submit that has not been collected."""
         count = self._pending or 0
         status = np.zeros(max(count, 1), np.int32)
-        rc = _insert_lib().rgrid_batch_insert_collect(self._h, status.ctypes.data)
+        rc = self._collected(_insert_lib().rgrid_batch_insert_collect(self._h, status.ctypes.data))
         if rc != 0:
             return rc, []
-        self._pending = None
         return 0, [int(v) for v in status[:count]]
 
     def collect_insert(self):
@@ -595,9 +514,8 @@ class ScanMatchFleet:
     def submit_filter_packed_code(self, packed, voxel_filter_size: float = 0.025, options: AdaptiveVoxelFilterOptions | None = None) -> int:
         """``submit_filter_code`` for what ``pack_filter`` returned (reusable: the points are copied by the call)."""
         co = _filter_options(voxel_filter_size, options)
-        rc = _filter_lib().rgrid_batch_filter_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1])
+        rc = self._submitted(_filter_lib().rgrid_batch_filter_submit(self._h, C.byref(co), C.cast(packed[0], C.c_void_p), packed[1]), packed[1])
         if rc == 0:
-            self._pending = packed[1]
             self._filter_room = sum(2 * packed[0][i].n_returns + packed[0][i].n_misses for i in range(packed[1]))
         return rc
 
@@ -616,12 +534,11 @@ class ScanMatchFleet:
         n = max(count, 1)
         room = int(getattr(self, "_filter_room", 0) if out_cap_points is None else out_cap_points)
         status, counts, out = np.zeros(n, np.int32), np.zeros((n, 3), np.int32), np.zeros((max(room, 1), 2), np.float32)
-        rc = _filter_lib().rgrid_batch_filter_collect(self._h, status.ctypes.data, counts.ctypes.data, out.ctypes.data, room)
+        rc = self._collected(_filter_lib().rgrid_batch_filter_collect(self._h, status.ctypes.data, counts.ctypes.data, out.ctypes.data, room))
         if rc == RGRID_ERR_BUFFER:
             return rc, [tuple(int(v) for v in counts[i]) for i in range(count)]
         if rc != 0:
             return rc, []
-        self._pending = None
         results, at = [], 0
         for i in range(count):
             clouds = []
@@ -654,9 +571,8 @@ class ScanMatchFleet:
         for k in ids:
             rc, lim = self.GetLimits_code(int(k)) if 0 <= k < self.num_grids else (RGRID_ERR_INVALID, None)
             room += 2 * lim[0] * lim[1] if rc == 0 else 0
-        rc = L.rgrid_batch_texture_submit(self._h, ids.ctypes.data if ids.size else None, int(ids.size))
+        rc = self._submitted(L.rgrid_batch_texture_submit(self._h, ids.ctypes.data if ids.size else None, int(ids.size)), int(ids.size))
         if rc == 0:
-            self._pending = int(ids.size)
             self._texture_room = room
         return rc
 
@@ -674,12 +590,11 @@ class ScanMatchFleet:
         room = int(getattr(self, "_texture_room", 0) if cap is None else cap)
         boxes, sm, offs = np.zeros((n, 4), np.int32), np.zeros((n, 2)), np.zeros(n, dtype=C.c_long)
         out = np.empty(max(room, 1), np.uint8)
-        rc = L.rgrid_batch_texture_collect(self._h, boxes.ctypes.data, sm.ctypes.data, offs.ctypes.data, out.ctypes.data, room)
+        rc = self._collected(L.rgrid_batch_texture_collect(self._h, boxes.ctypes.data, sm.ctypes.data, offs.ctypes.data, out.ctypes.data, room))
         if rc == RGRID_ERR_BUFFER:
             return rc, [(tuple(int(v) for v in boxes[i]), (float(sm[i, 0]), float(sm[i, 1])), int(offs[i])) for i in range(count)]
         if rc != 0:
             return rc, []
-        self._pending = None
         results = []
         for i in range(count):
             w, h, at = int(boxes[i, 2]), int(boxes[i, 3]), int(offs[i])

@@ -5,7 +5,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -24,24 +23,12 @@ class _MatchOptions(C.Structure):
                 ("translation_delta_cost_weight", C.c_double), ("rotation_delta_cost_weight", C.c_double)]
 
 
-_rgrid = None
 RGRID_ABI_VERSION = 4            # include/rgrid.h
 
 
-def _lib_rgrid():
-    global _rgrid
-    if _rgrid is not None:
-        return _rgrid
-    path = _lib.lib_path("librgrid.so")
-    if not os.path.exists(path):
-        raise _lib.LibraryMissing(f"{path} not found: the HIP extension is not built "
-                                  "(run `python __graft_entry__.py`); there is no CPU fallback")
-    L = C.CDLL(path)
+def _declare_rgrid(L):
+    """librgrid.so with argtypes set.  Raises LibraryMissing when it was not built or speaks another ABI version."""
     vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
-    L.rgrid_abi_version.restype = C.c_int
-    if L.rgrid_abi_version() != RGRID_ABI_VERSION:
-        raise _lib.LibraryMissing(f"{path} has ABI version {L.rgrid_abi_version()}, this package expects {RGRID_ABI_VERSION}: "
-                                  "rebuild it (`python __graft_entry__.py`)")
     L.rgrid_strerror.restype = C.c_char_p
     L.rgrid_strerror.argtypes = [C.c_int]
     L.rgrid_last_hip_error.restype = C.c_char_p
@@ -60,8 +47,9 @@ def _lib_rgrid():
     L.rgrid_draw_texture.argtypes = [vp, vp, C.c_long, ip, dp]
     L.rgrid_add_range_data.argtypes = [vp, C.POINTER(_MapBuilderOptionsC), vp, vp, C.c_int, vp, C.c_int, dp, dp, vp, ip]
     L.rgrid_refine_match.argtypes = [vp, C.POINTER(_RefineOptions), dp, dp, vp, C.c_int, dp, C.POINTER(_RefineSummary)]
-    _rgrid = L
-    return L
+
+
+_lib_rgrid = _lib.Library("librgrid.so", ("rgrid_abi_version", RGRID_ABI_VERSION), _declare_rgrid)
 
 
 class _RefineOptions(C.Structure):
@@ -134,8 +122,9 @@ class MatchResult:
     info: tuple                      # (num_scans, num_linear_perturbations, num_candidates)
 
 
-class GridFrontEnd:
+class GridFrontEnd(_lib.Handle):
     """One handle of include/rgrid.h: voxel filters + the real-time correlative scan matcher."""
+    _destroy = "rgrid_destroy"
 
     def __init__(self, max_points: int = 8192, max_cells: int = 4096 * 4096, max_candidates: int = 1 << 20, device: int = 0):
         self._L = _lib_rgrid()
@@ -146,21 +135,9 @@ class GridFrontEnd:
         self._h = h
         self.max_points = int(max_points)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.rgrid_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, where):
-        if rc != 0:
-            raise RgridError(rc, where, self._L.rgrid_last_hip_error(self._h).decode() if rc == -2 else
-                             self._L.rgrid_strerror(rc).decode())
+    def _error(self, rc, where):
+        return RgridError(rc, where, self._L.rgrid_last_hip_error(self._h).decode() if rc == -2 else
+                          self._L.rgrid_strerror(rc).decode())
 
     # sensor::VoxelFilter(size).Filter(point_cloud)  (voxel_filter.cc:81-95)
     def VoxelFilter(self, points_xy, size: float) -> np.ndarray:

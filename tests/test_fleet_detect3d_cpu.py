@@ -49,19 +49,19 @@ def test_module_imports_without_a_gpu_and_reports_a_missing_library_on_first_use
     from reflector_ekf_slam_amd import _lib, detect, fleet_detect
     assert reflector_ekf_slam_amd.PointCloudReflectorDetectFleet is fleet_detect.PointCloudReflectorDetectFleet
     assert reflector_ekf_slam_amd.cloud_events is fleet_detect.cloud_events
-    monkeypatch.setattr(fleet_detect, "_ready3", None)
-    monkeypatch.setattr(detect, "_lib_rdet", None)
+    monkeypatch.setattr(fleet_detect._batch3_lib, "ready", None)
+    monkeypatch.setattr(detect._rdet, "ready", None)
     monkeypatch.setattr(_lib, "lib_path", lambda name: os.path.join(ROOT, "no_such_dir", name))
     with pytest.raises(_lib.LibraryMissing):
         fleet_detect.PointCloudReflectorDetectFleet([detect.PointCloudOptions()])
-    monkeypatch.setattr(detect, "_lib_rdet", NS())       # a library built before the batch calls existed
+    monkeypatch.setattr(detect._rdet, "ready", NS())       # a library built before the batch calls existed
     with pytest.raises(_lib.LibraryMissing):
         fleet_detect.PointCloudReflectorDetectFleet([detect.PointCloudOptions()])
     wrong = NS(rdet3d_batch_create=None, rdet3d_batch_sizeof_cloud=lambda: 24)    # ... or with another struct rdet3d_cloud
-    monkeypatch.setattr(detect, "_lib_rdet", wrong)
+    monkeypatch.setattr(detect._rdet, "ready", wrong)
     with pytest.raises(_lib.LibraryMissing):
         fleet_detect.PointCloudReflectorDetectFleet([detect.PointCloudOptions()])
-    assert fleet_detect._ready3 is None
+    assert fleet_detect._batch3_lib.ready is None
 
 
 def test_refusals_in_front_of_any_hip_call():

@@ -42,12 +42,12 @@ def test_module_imports_without_a_gpu_and_reports_a_missing_library(monkeypatch)
     from reflector_ekf_slam_amd import _lib, detect, fleet_detect
     assert reflector_ekf_slam_amd.LaserReflectorDetectFleet is fleet_detect.LaserReflectorDetectFleet
     assert reflector_ekf_slam_amd.scan_events is fleet_detect.scan_events
-    monkeypatch.setattr(fleet_detect, "_ready", None)
-    monkeypatch.setattr(detect, "_lib_rdet", None)
+    monkeypatch.setattr(fleet_detect._batch_lib, "ready", None)
+    monkeypatch.setattr(detect._rdet, "ready", None)
     monkeypatch.setattr(_lib, "lib_path", lambda name: os.path.join(ROOT, "no_such_dir", name))
     with pytest.raises(_lib.LibraryMissing):
         fleet_detect.LaserReflectorDetectFleet([detect.ReflectorDetectOptions()])
-    monkeypatch.setattr(detect, "_lib_rdet", NS())       # a library built before the batch calls existed
+    monkeypatch.setattr(detect._rdet, "ready", NS())       # a library built before the batch calls existed
     with pytest.raises(_lib.LibraryMissing):
         fleet_detect.LaserReflectorDetectFleet([detect.ReflectorDetectOptions()])
 

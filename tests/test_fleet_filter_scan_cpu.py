@@ -88,10 +88,10 @@ def test_a_library_without_the_calls_is_reported_by_them_only(monkeypatch):
     refine, insert = M._refine_lib(), M._insert_lib()
     for hidden in (NEW, NEW[2:3]):
         old = _Without(real, hidden)
-        monkeypatch.setattr(M, "_ready", old)
-        monkeypatch.setattr(M, "_refine_ready", None)
-        monkeypatch.setattr(M, "_insert_ready", None)
-        monkeypatch.setattr(M, "_filter_ready", None)
+        monkeypatch.setattr(M._batch_lib, "ready", old)
+        monkeypatch.setattr(M._refine_lib, "ready", None)
+        monkeypatch.setattr(M._insert_lib, "ready", None)
+        monkeypatch.setattr(M._filter_lib, "ready", None)
         m = object.__new__(M.ScanMatchFleet)                       # a handle as an older library would have made it
         m._L, m._h, m._pending = old, None, None
         for call in (lambda: m.submit_filter_code([]), m.collect_filter_code, lambda: m.filter([]), M.filter_max_points):
@@ -104,15 +104,15 @@ def test_a_library_without_the_calls_is_reported_by_them_only(monkeypatch):
         assert m.submit_refine_code([]) == M.RGRID_ERR_INVALID and m.submit_insert_code([]) == M.RGRID_ERR_INVALID
         assert old.rgrid_batch_match_submit(None, C.byref(_MatchOptions(0.2, 0.26, 0.1, 0.1)), None, 0) == M.RGRID_ERR_INVALID
     # a library whose structure has another size
-    monkeypatch.setattr(M, "_ready", _Without(real, (), {"rgrid_batch_sizeof_filter_scan": lambda: 16}))
-    monkeypatch.setattr(M, "_filter_ready", None)
+    monkeypatch.setattr(M._batch_lib, "ready", _Without(real, (), {"rgrid_batch_sizeof_filter_scan": lambda: 16}))
+    monkeypatch.setattr(M._filter_lib, "ready", None)
     with pytest.raises(_lib.LibraryMissing) as e:
         M._filter_lib()
     assert "16" in str(e.value) and "24" in str(e.value)
-    monkeypatch.setattr(M, "_ready", real)
-    monkeypatch.setattr(M, "_refine_ready", refine)
-    monkeypatch.setattr(M, "_insert_ready", insert)
-    monkeypatch.setattr(M, "_filter_ready", None)
+    monkeypatch.setattr(M._batch_lib, "ready", real)
+    monkeypatch.setattr(M._refine_lib, "ready", refine)
+    monkeypatch.setattr(M._insert_lib, "ready", insert)
+    monkeypatch.setattr(M._filter_lib, "ready", None)
     assert M._filter_lib() is real
 
 

@@ -233,12 +233,12 @@ def test_the_binding_looks_the_map_calls_up_lazily(monkeypatch):
                 raise AttributeError(name)
             return getattr(real, name)
 
-    monkeypatch.setattr(fleet, "_map_ready", None)
-    monkeypatch.setattr(fleet, "rfleet", lambda: Old())
+    monkeypatch.setattr(fleet._map_lib, "ready", None)
+    monkeypatch.setattr(fleet.rfleet, "ready", Old())
     with pytest.raises(base.LibraryMissing):
         fleet._map_lib()
-    monkeypatch.setattr(fleet, "rfleet", lambda: real)
+    monkeypatch.setattr(fleet.rfleet, "ready", real)
     got = fleet._map_lib()
-    assert got is real and fleet._map_ready is real and got.rfleet_set_map.argtypes is not None
+    assert got is real and fleet._map_lib.ready is real and got.rfleet_set_map.argtypes is not None
     assert callable(fleet.ReflectorEKFSLAMFleet.set_map) and callable(fleet.ReflectorEKFSLAMFleet.map_size)
     assert not hasattr(fleet.FleetMember, "set_map")

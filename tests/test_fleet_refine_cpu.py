@@ -82,8 +82,8 @@ def test_a_library_without_the_calls_is_reported_by_them_only(monkeypatch):
     real = M._batch_lib()
     for hidden in (NEW, NEW[2:3]):
         old = _Without(real, hidden)
-        monkeypatch.setattr(M, "_ready", old)
-        monkeypatch.setattr(M, "_refine_ready", None)
+        monkeypatch.setattr(M._batch_lib, "ready", old)
+        monkeypatch.setattr(M._refine_lib, "ready", None)
         m = object.__new__(M.ScanMatchFleet)                       # a handle as an older library would have made it
         m._L, m._h, m._pending = old, None, None
         for call in (lambda: m.submit_refine_code([]), m.collect_refine_code, lambda: m.submit_scan_match_code([]), m.collect_scan_match_code,
@@ -98,13 +98,13 @@ def test_a_library_without_the_calls_is_reported_by_them_only(monkeypatch):
     # a library whose structure has another size
     def wrong_size():
         return 48
-    monkeypatch.setattr(M, "_ready", _Without(real, (), {"rgrid_batch_sizeof_refine_scan": wrong_size}))
-    monkeypatch.setattr(M, "_refine_ready", None)
+    monkeypatch.setattr(M._batch_lib, "ready", _Without(real, (), {"rgrid_batch_sizeof_refine_scan": wrong_size}))
+    monkeypatch.setattr(M._refine_lib, "ready", None)
     with pytest.raises(_lib.LibraryMissing) as e:
         M._refine_lib()
     assert "48" in str(e.value) and "56" in str(e.value)
-    monkeypatch.setattr(M, "_ready", real)
-    monkeypatch.setattr(M, "_refine_ready", None)
+    monkeypatch.setattr(M._batch_lib, "ready", real)
+    monkeypatch.setattr(M._refine_lib, "ready", None)
     assert M._refine_lib() is real
 
 

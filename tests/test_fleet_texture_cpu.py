@@ -73,9 +73,9 @@ def test_a_library_without_the_calls_is_reported_by_them_only(monkeypatch):
     insert = M._insert_lib()
     for hidden in (NEW, NEW[1:]):
         old = _Without(real, hidden)
-        monkeypatch.setattr(M, "_ready", old)
-        monkeypatch.setattr(M, "_insert_ready", None)
-        monkeypatch.setattr(M, "_texture_ready", None)
+        monkeypatch.setattr(M._batch_lib, "ready", old)
+        monkeypatch.setattr(M._insert_lib, "ready", None)
+        monkeypatch.setattr(M._texture_lib, "ready", None)
         m = object.__new__(M.ScanMatchFleet)                       # a handle as an older library would have made it
         m._L, m._h, m._pending, m.num_grids = old, None, None, 1
         for call in (lambda: m.submit_texture_code([]), m.collect_texture_code, lambda: m.submit_texture([0]), m.collect_texture,
@@ -88,9 +88,9 @@ def test_a_library_without_the_calls_is_reported_by_them_only(monkeypatch):
         assert m.submit_packed_code(M.ScanMatchFleet.pack([])) == M.RGRID_ERR_INVALID      # (a null handle: refused by the library itself)
         assert m.submit_insert_code([]) == M.RGRID_ERR_INVALID
         assert m.GetLimits_code(0)[0] == M.RGRID_ERR_INVALID
-    monkeypatch.setattr(M, "_ready", real)
-    monkeypatch.setattr(M, "_insert_ready", insert)
-    monkeypatch.setattr(M, "_texture_ready", None)
+    monkeypatch.setattr(M._batch_lib, "ready", real)
+    monkeypatch.setattr(M._insert_lib, "ready", insert)
+    monkeypatch.setattr(M._texture_lib, "ready", None)
     assert M._texture_lib() is real
 
 
