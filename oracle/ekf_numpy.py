@@ -108,8 +108,10 @@ class NumpyEKF:
             g = self._to_global(obs[i])
             if M_ > 0:
                 delta = (self.map_xy - g).astype(np.float32).astype(np.float64)  # float32 subtract
-                d = np.sqrt(np.einsum("ji,jik,jk->j", delta, self.map_cov, delta))
-                j = int(np.argmin(d))  # first minimum
+                with np.errstate(invalid="ignore"):
+                    d = np.sqrt(np.einsum("ji,jik,jk->j", delta, self.map_cov, delta))
+                # first minimum; a NaN distance (an indefinite weight) never wins, and if all are NaN there is no map pair
+                j = int(np.argmin(np.where(np.isnan(d), np.inf, d)))
                 if d[j] < 0.05:
                     map_pairs.append((i, j))
                     continue

@@ -274,11 +274,12 @@ static void reflector_match(oekf_t *e, const float *obs, int K)
                 const double t0 = dx * S[0] + dy * S[2];
                 const double t1 = dx * S[1] + dy * S[3];
                 const double dist = sqrt(t0 * dx + t1 * dy);
-                /* :414-419 sort with '<=' then front(): first minimum (ties are UB
-                 * in the reference; NaN never wins here). */
-                if (bj < 0 || dist < best) { best = dist; bj = j; }
+                /* :414-419 sort with '<=' then front(): first minimum in index order.  Ties and a NaN distance
+                 * (an indefinite S) are UB in the reference's sort; the rule here: a NaN never wins, wherever it
+                 * stands, and when every distance is NaN there is no map pair. */
+                if (dist == dist && (bj < 0 || dist < best)) { best = dist; bj = j; }
             }
-            if (best < 0.05) {                                       /* :420 */
+            if (bj >= 0 && best < 0.05) {                            /* :420 */
                 e->map_pairs[2 * e->n_map] = i;
                 e->map_pairs[2 * e->n_map + 1] = bj;
                 e->n_map++;
@@ -329,9 +330,9 @@ static void reflector_match_team(oekf_t *e, const float *obs, int K, int T)
                 const double t0 = dx * S[0] + dy * S[2];
                 const double t1 = dx * S[1] + dy * S[3];
                 const double dist = sqrt(t0 * dx + t1 * dy);
-                if (bj < 0 || dist < best) { best = dist; bj = j; }
+                if (dist == dist && (bj < 0 || dist < best)) { best = dist; bj = j; }    /* (a NaN never wins) */
             }
-            if (best < 0.05) { kind[i] = 0; idx[i] = bj; continue; } /* :420 */
+            if (bj >= 0 && best < 0.05) { kind[i] = 0; idx[i] = bj; continue; } /* :420 */
         }
         if (M > 0) {                                                 /* :426-451 */
             double best = 0; int bj = -1;

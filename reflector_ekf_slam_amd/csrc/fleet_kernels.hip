@@ -303,7 +303,8 @@ __global__ __launch_bounds__(RFLEET_THREADS) void FLEET_STEP_KERNEL(FleetDev d, 
                             const double t0 = dx * S[0] + dy * S[2];                          // cc:411: (delta sigma) delta^T
                             const double t1 = dx * S[1] + dy * S[3];
                             const double dist = sqrt(t0 * dx + t1 * dy);
-                            if (bj < 0 || dist < best) { best = dist; bj = j; }
+                            // a NaN distance (an indefinite S) never wins, wherever it stands: a lane that saw nothing else keeps bj < 0
+                            if (dist == dist && (bj < 0 || dist < best)) { best = dist; bj = j; }
                         }
                         for (int off = 32; off > 0; off >>= 1) {
                             const double ob = __shfl_xor(best, off, 64);

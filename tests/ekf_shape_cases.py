@@ -39,9 +39,12 @@ Kinds:
                K = 14 | 15 on L = 31 (31 | 33 rows: the NBR switch), K = 30 on L = 64 (63 rows in one pass), K = 31 on L = 64
                (65 rows: block steps with stride 30).  The witness is tests/witness/fleet_pose_witness.py, joint form.
 
-Out of scope: pre-loaded maps (set_map) -- the witness has no map branch; the golden map_L24_obs8 and the 512-reflector
-localisation test stay the cover -- and exclusive handles (k_mid<*, 2>): no counter proves that path ran, and it is the one
-form in which a workgroup waits for another.
+Pre-loaded maps (set_map) are the subject of tests/ekf_map_cases.py, which builds its cases with this module's Builder: a scan
+may carry observations of map points (``map_ids``), and a case with a map claims three lists per scan, ``expect[k] =
+(state_pairs, map_pairs, new_ids)``, as tests/fleet_map_cases.py does (claim3 reads either form).
+
+Out of scope: exclusive handles (k_mid<*, 2>): no counter proves that path ran, and it is the one form in which a workgroup
+waits for another.
 """
 from __future__ import annotations
 
@@ -51,6 +54,7 @@ import numpy as np
 
 from tests import fleet_cases as FC
 from tests.fleet_cases import DIFF, EV_SCAN, MARGIN_MIN, OMNI, _case, dense_spd, feed, margins, reference_events, to_local
+from tests.fleet_map_cases import map_margins
 
 GRID, PITCH, JITTER = 16, 2.0, 0.2           # 256 lattice cells, reflectors at least 1.6 m apart
 T0, DT = 100.0, 0.1
@@ -79,6 +83,12 @@ SUITE = NS(name="single", floor_sigma=FP64_FLOOR_SIGMA, floor_mu=FP64_FLOOR_MU, 
 
 
 # ---- where the matched reflectors sit ------------------------------------------------------------------------------------------
+def claim3(case, k):
+    """-> (state pairs, map pairs, new ids) as scan k of `case` claims them; a case without a map claims no map pair."""
+    e = case.expect[k]
+    return (e[0], e[1], e[2]) if len(e) == 3 else (e[0], [], e[1])
+
+
 def straddler16(L):
     """The first reflector whose rows 3 + 2 j, 4 + 2 j lie on either side of a 16-row edge; None below L = 7."""
     return 6 if L > 6 else None
@@ -128,7 +138,9 @@ class Builder:
     """Lays the scans of a case down one after the other on a run of oracle/ekf_numpy.py (the predicted pose and the current
     means of the reflectors are where the observations are placed)."""
 
-    def __init__(self, L, model, seed, cap, auto_grow=False):
+    def __init__(self, L, model, seed, cap, auto_grow=False, n_map=0, map_cov=None):
+        """n_map > 0: a pre-loaded map of that many points, free lattice cells (so at least 1.6 m from every reflector and every
+        new point); map_cov: its weights (n_map x 4, row-major 2 x 2), identity when None."""
         rng = self.rng = np.random.default_rng(seed)
         self.L0, self.model, self.cap, self.auto_grow = L, model, cap, auto_grow
         n = 3 + 2 * L
@@ -136,8 +148,17 @@ class Builder:
         pts = np.stack([cells % GRID, cells // GRID], -1) * PITCH + rng.uniform(-JITTER, JITTER, size=(GRID * GRID, 2))
         pts = pts.astype(np.float32).astype(np.float64)
         lm, free = pts[:L], pts[L:]
-        d = np.sort(np.hypot(lm[None, :, 0] - free[:, None, 0], lm[None, :, 1] - free[:, None, 1]), axis=1)
-        self.free = list(free[d[:, 1] - d[:, 0] >= 0.05])     # new points: the two nearest reflectors are not nearly equidistant
+        if L >= 2:
+            d = np.sort(np.hypot(lm[None, :, 0] - free[:, None, 0], lm[None, :, 1] - free[:, None, 1]), axis=1)
+            free = free[d[:, 1] - d[:, 0] >= 0.05]            # new points: the two nearest reflectors are not nearly equidistant
+        self.free = list(free)
+        self.map_xy = self.map_cov = None
+        if n_map:
+            # the map takes the front of the free cells (new points come off the back); nothing is drawn for it
+            self.map_xy = np.asarray(self.free[:n_map], np.float32).reshape(n_map, 2)
+            self.free = self.free[n_map:]
+            assert np.array_equal(self.map_xy.astype(np.float64), np.asarray(free[:n_map]))
+            self.map_cov = np.tile(np.asarray((1.0, 0.0, 0.0, 1.0)), (n_map, 1)) if map_cov is None else np.asarray(map_cov, np.float64).reshape(n_map, 4)
         mu = np.zeros(n)
         mu[0:2] = 0.5 * GRID * PITCH + rng.uniform(-1.5, 1.5, size=2)
         mu[2] = rng.uniform(-3.0, 3.0)
@@ -146,7 +167,9 @@ class Builder:
         vt = (rng.uniform(0.2, 1.0), rng.uniform(-0.3, 0.3) if model == OMNI else 0.0, rng.uniform(-0.4, 0.4))
         self.mu, self.P, self.vt = mu, P, vt
         self.ek = FC.numpy_of(NS(model=model, t=T0, mu=mu, P=P, vt=vt))
-        self.events, self.expect, self.kept, self.marg = [], {}, {}, {}
+        if n_map:
+            self.ek.set_map(self.map_xy, self.map_cov)
+        self.events, self.expect, self.kept, self.marg, self.map_marg = [], {}, {}, {}, {}
         self.fix_rng = None
 
     def with_fixes(self, seed):
@@ -156,31 +179,39 @@ class Builder:
     def L(self):
         return (self.ek.mu.shape[0] - 3) // 2
 
-    def scan(self, ids, far=0, avoid=None):
-        """One scan: an observation of each reflector of `ids` (in that order, repeats allowed) and `far` free cells, interleaved
-        at random (not in the order `avoid` of reflectors).  On a full filter the far ones are dropped, on any other they become
-        reflectors."""
+    def scan(self, ids, far=0, avoid=None, map_ids=(), avoid_map=None):
+        """One scan: an observation of each reflector of `ids` (in that order, repeats allowed), one of each map point of `map_ids`
+        (the same) and `far` free cells, interleaved at random (not in the order `avoid` of reflectors, nor `avoid_map` of map
+        points).  On a full filter the far ones are dropped, on any other they become reflectors."""
         rng, ek, k = self.rng, self.ek, len(self.events)
         t = T0 + DT * (k + 1)
         mu_p = ek.predict_state(t)[0]
         pose = tuple(float(v) for v in mu_p[:3])
-        K = len(ids) + far
+        n_s, n_m = len(ids), len(map_ids)
+        assert n_m == 0 or self.map_xy is not None
+        K = n_s + n_m + far
         while True:
             slots = rng.permutation(K)
+            if avoid_map is not None and n_m >= 2 and [int(map_ids[s - n_s]) for s in slots if n_s <= s < n_s + n_m] == avoid_map:
+                continue
             if avoid is None or len(ids) < 2 or [int(ids[s]) for s in slots if s < len(ids)] != avoid:
                 break
         full = not self.auto_grow and self.L() == self.cap
         # (what a full filter drops never enters the state: the same free cells serve every scan)
         cells = [self.free[i] for i in range(far)] if full else [self.free.pop() for _ in range(far)]
         cloud = np.zeros((K, 2), np.float32)
-        pairs, new = [], []
+        pairs, mpairs, new = [], [], []
         for q in range(K):
-            if slots[q] < len(ids):
+            if slots[q] < n_s:
                 j = int(ids[slots[q]])
                 g = ek.mu[3 + 2 * j: 5 + 2 * j] + rng.uniform(-2e-3, 2e-3, size=2)
                 pairs.append((q, j))
+            elif slots[q] < n_s + n_m:
+                j = int(map_ids[slots[q] - n_s])
+                g = self.map_xy[j].astype(np.float64) + rng.uniform(-2e-3, 2e-3, size=2)
+                mpairs.append((q, j))
             else:
-                g = cells[slots[q] - len(ids)]
+                g = cells[slots[q] - n_s - n_m]
                 new.append(q)
             cloud[q] = to_local(pose, g)
         fix = None
@@ -189,43 +220,70 @@ class Builder:
             fix = (float(f[0]), float(f[1]), float(np.arctan2(np.sin(f[2]), np.cos(f[2]))))
         dropped = full and far > 0
         assert full or self.auto_grow or self.L() + far <= self.cap
-        keep = [q for q, _ in pairs] if dropped else None
+        keep = sorted(q for q, _ in pairs + mpairs) if dropped else None
         if dropped:
             self.kept[k] = keep
-        self.expect[k] = (pairs, [] if dropped else new)
+        has_map = self.map_xy is not None
+        self.expect[k] = (pairs, mpairs, [] if dropped else new) if has_map else (pairs, [] if dropped else new)
         kc = cloud if keep is None else np.ascontiguousarray(cloud[keep])
         self.marg[k] = margins(mu_p, kc)
         for a, b in self.marg[k]:
             assert a >= MARGIN_MIN and b >= MARGIN_MIN, (k, a, b)      # no case is excused
+        if has_map:
+            # the map branch's margins (fleet_map_cases.map_margins: over the weight's scale), of every observation of the scan
+            self.map_marg[k] = map_margins(self, mu_p, kc)
+            kept_q = range(K) if keep is None else keep
+            for q, (a, b, inside) in zip(kept_q, self.map_marg[k]):
+                assert a >= MARGIN_MIN and b >= MARGIN_MIN and inside == (q in {o for o, _ in mpairs}), (k, q, a, b, inside)
         self.events.append((EV_SCAN, t, (0.0, 0.0, 0.0), cloud) + ((fix,) if self.fix_rng is not None else ()))
         ek.handle_observation(t, kc, *(() if fix is None else (np.asarray(fix),)))
         got = ([tuple(int(v) for v in p) for p in ek.last_match[1]], [int(v) for v in ek.last_match[2]])
         want = FC.map_back(NS(kept=self.kept), k, *got)
-        assert [tuple(p) for p in want[0].tolist()] == pairs and want[1].tolist() == self.expect[k][1], (k, got, pairs, new)
+        assert [tuple(p) for p in want[0].tolist()] == pairs and want[1].tolist() == self.expect[k][-1], (k, got, pairs, new)
+        got_m = FC.map_back(NS(kept=self.kept), k, ek.last_match[0], [])[0]
+        assert [tuple(p) for p in got_m.tolist()] == mpairs, (k, got_m.tolist(), mpairs)
 
-    def four_scans(self, MM, far=(0, 0, 0, 0), first_new=0):
+    def four_scans(self, MM, far=(0, 0, 0, 0), first_new=0, Mm=0):
         """The sequence of the module docstring.  far[k]: far observations of scan k (a full filter drops them);
-        first_new: new reflectors of scan 1 (a growing filter)."""
+        first_new: new reflectors of scan 1 (a growing filter).  Mm: map points per scan (tests/ekf_map_cases.py): scans 1 and 2
+        see map points 0 .. Mm - 1, scan 3 sees Mm .. 2 Mm - 1, scan 4 part of those with map point Mm three times (duplicate
+        map rows); MM may then be 0 (map rows only)."""
         L = self.L0
-        first, third = matched_sets(L, MM, self.rng)
-        self.scan(first, far[0] + first_new)
+        first, third = matched_sets(L, MM, self.rng) if MM else ([], [])
+        m1, m3 = list(range(Mm)), list(range(Mm, 2 * Mm))
+        self.scan(first, far[0] + first_new, map_ids=m1)
         Lg, pos = self.L(), MM - 1
         for j in ([Lg - 1, L] if Lg > L + 1 else [Lg - 1] if Lg > L else []):
             # the grown state: scan 3 matches the last reflector scan 1 appended and the first one (its rows straddle the edge)
             if pos >= 1 and j not in third:
                 third[pos] = j
                 pos -= 1
-        self.scan(first, far[1], avoid=[g for _, g in self.expect[0][0]])
-        self.scan(third, far[2])
-        tri = third[0]
-        K4 = max(3, MM)
-        others = [j for j in third if j != tri][:K4 - 3]
-        self.scan([tri] + others[:len(others) // 2] + [tri] + others[len(others) // 2:] + [tri], far[3])
+        self.scan(first, far[1], avoid=[g for _, g in self.expect[0][0]], map_ids=m1,
+                  avoid_map=[g for _, g in self.expect[0][1]] if Mm else None)
+        self.scan(third, far[2], map_ids=m3)
+        # scan 4: max(3, MM) state observations and max(3, Mm) map observations, but no more pairs than the case's MM + Mm where
+        # that leaves three of each kind (so that the scan stays on the launch form of the others)
+        K4, K4m = (max(3, MM) if MM else 0), (max(3, Mm) if Mm else 0)
+        over = max(0, K4 + K4m - (MM + Mm)) if Mm else 0
+        if K4 >= K4m:
+            K4 = max(3, K4 - over) if MM else 0
+        else:
+            K4m = max(3, K4m - over)
+        ids4 = []
+        if MM:
+            tri = third[0]
+            others = [j for j in third if j != tri][:K4 - 3]
+            ids4 = [tri] + others[:len(others) // 2] + [tri] + others[len(others) // 2:] + [tri]
+        else:
+            tri = None
+        self.scan(ids4, far[3], map_ids=([Mm] + m3[1:K4m - 2] + [Mm, Mm]) if Mm else ())
         self.sets = (first, third, tri)
 
     def case(self, name, kind, **tags):
         c = _case(name, kind, self.model, self.mu, self.P, self.vt, T0, self.events, self.expect,
                   max_landmarks=max(self.cap, self.L()), kept=self.kept, L=self.L0, n=3 + 2 * self.L0, cap=self.cap, **tags)
+        if self.map_xy is not None:
+            c.map_xy, c.map_cov, c.use, c.map_margins = self.map_xy, self.map_cov, True, self.map_marg
         c.margins = self.marg
         c.cond_S = cond_S_of(c)
         c.flags = FC.FLAG_CAPACITY if self.kept else 0
@@ -238,6 +296,8 @@ def cond_S_of(case):
     """cond(S) of every scan (reflector rows; read off when a case is far out) from a run of oracle/ekf_numpy.py."""
     out = {}
     ek = FC.numpy_of(case)
+    if hasattr(case, "map_xy"):
+        ek.set_map(case.map_xy, case.map_cov)
     for k, ev in enumerate(reference_events(case)):
         mu_p, P_p = ek.predict_state(ev[1])
         pairs = [(l, g) for l, g in np.asarray(case.expect[k][0]).reshape(-1, 2)]

@@ -10,6 +10,9 @@ coordinate is a float32-exact dyadic number.  Three lattices that cannot be conf
 A scan is written as tokens, which are the claim: ("m", j) an observation 0.014 m or less from map point j, ("s", j) the same
 from reflector j of the state, ("n", point); a token may carry its own point.
 
+nan_cases: a weighted distance that is NaN (an indefinite weight) never wins, wherever it stands -- the one rule of the three
+references, the fleet kernel and (where tests/test_ekf_map_gpu.py does not list a divergence) the single filter.
+
 A fleet has ONE map, so the lockstep run (run_lockstep) makes all cases members of one fleet per capacity and walks them group by
 group, replacing the map in between; a case with ``use = False`` sits in the fleet while the map is set and must not see it.
 """
@@ -133,7 +136,8 @@ def build(name, lms, map_pts, scans, seed, map_cov=None, use=True, max_landmarks
 
 def map_margins(case, mu_pred, cloud):
     """Per observation (|d1 - 0.05|, d2 - d1) of ReflectorMatch's map branch at the predicted mean, each divided by the weight's
-    scale (a distance in metres), and whether the best point is inside the gate."""
+    scale (a distance in metres), and whether the best point is inside the gate.  d1 and d2 are taken over the points whose
+    distance is a number: a NaN never wins (nan_cases); (inf, inf, False) where every distance is NaN."""
     from tests.witness.fleet_map_witness import weighted_distances
     out = []
     c, s = math.cos(mu_pred[2]), math.sin(mu_pred[2])
@@ -142,11 +146,15 @@ def map_margins(case, mu_pred, cloud):
         gx = np.float32(float(p[0]) * c - float(p[1]) * s + mu_pred[0])
         gy = np.float32(float(p[0]) * s + float(p[1]) * c + mu_pred[1])
         dw, _ = weighted_distances(case.map_xy, case.map_cov, gx, gy)
-        order = np.argsort(dw, kind="stable")
+        valid = np.nonzero(~np.isnan(dw))[0]                  # a NaN distance (an indefinite weight) never wins: such a point is
+        if valid.shape[0] == 0:                               # skipped, and where every point is one the map decides nothing
+            out.append((np.inf, np.inf, False))
+            continue
+        order = valid[np.argsort(dw[valid], kind="stable")]
         j1 = int(order[0])
         a = abs(dw[j1] - MAP_GATE) / scales[j1]
         b = np.inf
-        if dw.shape[0] > 1:
+        if order.shape[0] > 1:
             j2 = int(order[1])
             b = (dw[j2] - dw[j1]) / max(scales[j1], scales[j2])
         out.append((float(a), float(b), bool(dw[j1] < MAP_GATE)))
@@ -286,13 +294,63 @@ def two_scan_case():
     return build("two_scans", [], pts, [s0, s1], seed=280)
 
 
+INDEFINITE = (-1.0, 0.0, 0.0, -1.0)
+NAN_PQ = ((0, 1), (5, 69), (5, 37), (70, 3), (64, 0))
+
+
+def nan_cases():
+    """A weighted distance that is NaN: sqrt(e S e^T) with e S e^T < 0 for an indefinite weight S.  The reference's std::sort with
+    `<=` is undefined there (cc:414-419); the rule of this project (DESIGN.md, quirk register): a NaN distance never wins, wherever
+    it stands; the map pair is the first minimum in index order over the distances that are numbers, if that is < 0.05; if every
+    distance is NaN the observation goes on to the state branch.  129 points, identity weights, point p with the weight -I, one
+    observation 1/64 m from point q: p in lane p of the wave sweep, q in the same lane a stride later (5, 69), in a lane whose
+    result reaches lane 0 through lane p (5, 37), in front of p (70, 3; 64, 0) and right behind index 0 (0, 1).  n = 3 unless stated.
+    Every claim is checked against MapWitnessEKF.match3 here."""
+    out = []
+    e = 1 / 64
+
+    def cov_with(M_, bad):
+        cov = [list(IDENTITY) for _ in range(M_)]
+        for j, S in bad.items():
+            cov[j] = list(S)
+        return cov
+
+    for p, q in NAN_PQ:
+        pts = map_lattice(129)
+        out.append(build(f"nan_p{p}_q{q}", [], pts, [[("m", q, (pts[q][0] + e, pts[q][1]))]], seed=290 + len(out),
+                         map_cov=cov_with(129, {p: INDEFINITE}), nan_at=[p]))
+    # the nearest point itself is the NaN: the runner-up, 3/64 m away and a stride later in the same lane, is the match
+    pts = map_lattice(129)
+    g = (0.25, 0.0)
+    pts[5], pts[69] = (g[0] + e, g[1]), (g[0] - 3 * e, g[1])
+    out.append(build("nan_nearest_5_runner_up_69", [], pts, [[("m", 69, g)]], seed=295, map_cov=cov_with(129, {5: INDEFINITE}), nan_at=[5]))
+    # every distance NaN: the state branch decides (a state pair, a new reflector), also for the observation right at a map point
+    pts = map_lattice(129)
+    lms = FC.far_lattice(2)
+    toks = [("s", 0, (lms[0][0] + 1 / 512, lms[0][1])), ("n", (pts[7][0] + e, pts[7][1]))]
+    out.append(build("nan_everywhere", lms, pts, [toks], seed=296, map_cov=[list(INDEFINITE)] * 129, nan_at=list(range(129))))
+    pts = map_lattice(1)
+    out.append(build("nan_M1", [], pts, [[("n", (pts[0][0] + e, pts[0][1]))]], seed=297, map_cov=[list(INDEFINITE)], nan_at=[0]))
+    # semi-indefinite: e S e^T = ex^2 - ey^2 / 1024 -- a number (1/64, inside the gate) along x, NaN along y (no pair: new)
+    pts = map_lattice(129)
+    toks = [("m", 66, (pts[66][0] + e, pts[66][1])), ("n", (pts[66][0], pts[66][1] + e))]
+    out.append(build("nan_semi_definite_66", [], pts, [toks], seed=298, map_cov=cov_with(129, {66: (1.0, 0.0, 0.0, -1 / 1024)}), nan_at=[66]))
+    for c in out:
+        w = map_witness_of(c)
+        w.predict(c.events[0][1] - w.time)
+        got = w.match3(np.asarray(c.events[0][3], np.float32))
+        assert got == tuple(c.expect[0]), (c.name, got, c.expect[0])
+    return out
+
+
 _cases = None
 
 
 def all_cases():
     global _cases
     if _cases is None:
-        _cases = size_cases() + tie_cases() + mix_cases() + branch_cases() + weight_cases() + fix_cases() + [unused_case(), two_scan_case()]
+        _cases = (size_cases() + tie_cases() + mix_cases() + branch_cases() + weight_cases() + fix_cases() + [unused_case(), two_scan_case()] +
+                  nan_cases())
     return _cases
 
 

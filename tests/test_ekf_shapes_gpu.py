@@ -20,7 +20,10 @@ run and must show that the path the pattern is about ran (`_check_counters` says
 The cases of the fleet's sweep and its crafted cases (tests/fleet_cases.py; about 100 further shapes, gates to the last float32
 ulp, exact ties, duplicates, the heading wrap) run through a single-filter handle in the reader pattern, with their own floors.
 
-Out of scope, as in tests/ekf_shape_cases.py: pre-loaded maps and exclusive handles."""
+run_pattern serves tests/test_ekf_map_gpu.py as well: a case with a map (``map_xy`` / ``map_cov``) has it set on the handle, and all
+three lists of last_match() are compared with the case's claim (no map pair for a case without a map).
+
+Out of scope, as in tests/ekf_shape_cases.py: exclusive handles."""
 from __future__ import annotations
 
 import ctypes as C
@@ -46,19 +49,24 @@ _witness = {}
 
 def witness_run(case, suite):
     """-> per scan event k the witness's (mu, P) after it: computed once per case, shared by its patterns, never changed."""
-    if case.name not in _witness:
+    key = (suite.name, case.name)                               # (two case modules may use one name: fleet_cases' and fleet_map_cases' ties)
+    if key not in _witness:
         w = next(iter(suite.witnesses.values()))(case)
         out = {}
         k_of = [k for k, ev in enumerate(case.events) if not (ev[0] == FC.EV_ODOM and case.use_imu)]
         for k, ev in zip(k_of, FC.reference_events(case)):
             FC.feed(w, ev)
             if ev[0] == FC.EV_SCAN:
-                pairs, new = FC.map_back(case, k, *w.last_match)
-                assert np.array_equal(pairs, np.asarray(case.expect[k][0], np.int32).reshape(-1, 2)), (case.name, k)
-                assert np.array_equal(new, np.asarray(case.expect[k][1], np.int32).reshape(-1)), (case.name, k)
+                got = w.last_match if len(w.last_match) == 3 else (w.last_match[0], [], w.last_match[1])
+                pairs, new = FC.map_back(case, k, got[0], got[2])
+                mapped, _ = FC.map_back(case, k, got[1], [])
+                want_p, want_m, want_n = EC.claim3(case, k)
+                assert np.array_equal(pairs, np.asarray(want_p, np.int32).reshape(-1, 2)), (case.name, k)
+                assert np.array_equal(mapped, np.asarray(want_m, np.int32).reshape(-1, 2)), (case.name, k)
+                assert np.array_equal(new, np.asarray(want_n, np.int32).reshape(-1)), (case.name, k)
                 out[k] = w.state()
-        _witness[case.name] = out
-    return _witness[case.name]
+        _witness[key] = out
+    return _witness[key]
 
 
 def _counters(g):
@@ -69,8 +77,8 @@ def _counters(g):
 
 def _check_match(g, case, k, what):
     sp, mp, nw = norm_match(g.last_match())
-    want_p, want_n = case.expect[k]
-    assert mp.shape[0] == 0
+    want_p, want_m, want_n = EC.claim3(case, k)
+    assert np.array_equal(mp, np.asarray(want_m, np.int32).reshape(-1, 2)), (what, k, mp.tolist(), want_m)
     assert np.array_equal(sp, np.asarray(want_p, np.int32).reshape(-1, 2)), (what, k, sp.tolist(), want_p)
     assert np.array_equal(nw, np.asarray(want_n, np.int32).reshape(-1)), (what, k, nw.tolist(), want_n)
 
@@ -83,8 +91,6 @@ def _check_state(st, ref, suite, what):
     es, em = rel_err(st.mu, st.sigma, mu_ref, P_ref)
     bs, bm = bounds_within_tolerances(mu_ref, P_ref, suite)
     fs, fm = es / suite.floor_sigma, em / suite.floor_mu
-    ws, wm = WORST.get(suite.name, ((0.0, ""), (0.0, "")))
-    WORST[suite.name] = (max(ws, (fs, what)), max(wm, (fm, what)))
     if es > bs or em > bm:
         d = np.abs(np.asarray(st.sigma, np.longdouble) - P_ref)
         r, c = np.unravel_index(int(np.argmax(d)), d.shape)
@@ -93,6 +99,8 @@ def _check_state(st, ref, suite, what):
               f"{np.nonzero(d.max(axis=1) > bs * float(np.abs(P_ref).max()))[0].tolist()[:40]}; worst mu row {dm}")
     assert es <= bs, f"{what}: sigma off by {es:.3e} = {fs:.1f} x the FP64 floor (bound {bs:.3e})"
     assert em <= bm, f"{what}: mu off by {em:.3e} = {fm:.1f} x the FP64 floor (bound {bm:.3e})"
+    ws, wm = WORST.get(suite.name, ((0.0, ""), (0.0, "")))          # (of the states that hold the bound: a miss is its own test's failure)
+    WORST[suite.name] = (max(ws, (fs, what)), max(wm, (fm, what)))
     return fs, fm
 
 
@@ -107,6 +115,8 @@ def run_pattern(case, pattern, monkeypatch, suite):
     cap = getattr(case, "cap", case.max_landmarks)
     g = ReflectorEKFSLAM(FC.options_of(case), max_landmarks=cap, auto_grow=bool(getattr(case, "auto_grow", False)))
     try:
+        if getattr(case, "map_xy", None) is not None and getattr(case, "use", True):
+            g.set_map(case.map_xy, case.map_cov)
         g.set_state(case.t, case.mu, case.P, case.vt)
         if kw.get("grid", True) is False:
             g.debug_set_grid(False)

@@ -78,15 +78,61 @@ def test_cases_are_what_they_claim(all_cases, reference_runs):
     assert c.mu.shape[0] == 3 and len(c.expect[0][2]) == 3 and [j for _, j in c.expect[1][0]] == [0, 1, 2] and len(c.expect[1][1]) == 2
 
 
+@needs_ld
+def test_nan_cases_are_what_they_claim(all_cases, reference_runs):
+    """The NaN rule (a NaN weighted distance never wins; all NaN: on to the state branch).  The three references give the claimed
+    lists on every nan case (reference_runs asserts that for every case; said here by name), the distances that are NaN are
+    exactly those of the points the case names, and the (p, q) pairs are the ones the wave sweep of 64 lanes can get wrong."""
+    nan = MC.nan_cases()
+    by = {c.name: c for c in all_cases}
+    assert len(nan) == 9 and all(c.name in by and c.name in reference_runs for c in nan)
+    assert [(c.nan_at[0], c.expect[0][1][0][1]) for c in nan[:5]] == [(0, 1), (5, 69), (5, 37), (70, 3), (64, 0)] == list(MC.NAN_PQ)
+    for c in nan:
+        assert sorted(reference_runs[c.name]) == [0] and len(c.events) == 1
+        for q, p in enumerate(c.events[0][3]):
+            dw, _ = MW.weighted_distances(c.map_xy, c.map_cov, np.float32(p[0]), np.float32(p[1]))
+            bad = np.nonzero(np.isnan(dw))[0].tolist()
+            assert bad in ([], c.nan_at), (c.name, q, bad)
+            pair = [j for i, j in c.expect[0][1] if i == q]
+            if pair:                                           # the first minimum over the numbers, inside the gate
+                assert pair[0] not in bad and dw[pair[0]] == np.nanmin(dw) < MC.MAP_GATE and int(np.nanargmin(dw)) == pair[0]
+            else:
+                assert len(bad) == dw.shape[0] or np.nanmin(dw) >= MC.MAP_GATE + MC.MARGIN_MIN
+        assert any(np.isnan(MW.weighted_distances(c.map_xy, c.map_cov, np.float32(p[0]), np.float32(p[1]))[0]).any() for p in c.events[0][3])
+    # same lane a stride later; a lane whose result reaches lane 0 through lane 5 in the xor butterfly (32, 16, 8, 4, 2, 1)
+    assert 69 % 64 == 5 and 37 ^ 32 == 5 and 64 % 64 == 0 and 70 % 64 != 3
+    c = by["nan_nearest_5_runner_up_69"]
+    p = c.events[0][3][0]
+    _, de = MW.weighted_distances(c.map_xy, c.map_cov, np.float32(p[0]), np.float32(p[1]))
+    assert int(np.argmin(de)) == 5 and c.expect[0] == ([], [(0, 69)], []) and float(de[69]) == 3 / 64
+    c = by["nan_everywhere"]
+    assert c.mu.shape[0] == 7 and c.expect[0] == ([(0, 0)], [], [1]) and (c.map_cov == np.asarray(MC.INDEFINITE)).all()
+    assert float(np.hypot(*(c.events[0][3][0] - c.mu[3:5]))) <= 2e-3
+    assert by["nan_M1"].map_xy.shape[0] == 1 and by["nan_M1"].expect[0] == ([], [], [0])
+    c = by["nan_semi_definite_66"]
+    assert c.map_cov[66].tolist() == [1.0, 0.0, 0.0, -1 / 1024] and c.expect[0] == ([], [(0, 66)], [1])
+    d0, d1 = c.events[0][3][0] - c.map_xy[66], c.events[0][3][1] - c.map_xy[66]
+    assert d0.tolist() == [1 / 64, 0.0] and d1.tolist() == [0.0, 1 / 64]
+
+
 def test_margins(all_cases):
     """Every claimed association is clear of its thresholds: the best weighted distance at least MARGIN_MIN metres (scaled by the
     weight) from 0.05, inside the gate the second best that far behind (ties excepted: they are the point of their cases;
-    outside the gate the index of the best point decides nothing), and for an observation that reaches the state branch |d1 - 0.6| at least MARGIN_MIN and, inside that gate, d2 - d1 too."""
+    outside the gate the index of the best point decides nothing), and for an observation that reaches the state branch |d1 - 0.6| at least MARGIN_MIN and, inside that gate, d2 - d1 too.
+    A map point whose weighted distance is NaN is skipped (fleet_map_cases.map_margins leaves it out by name: it can never be the
+    pair); the best and the second best are those of the remaining points, and no case is excused.  Where every point is skipped
+    the map margins are infinite and the state margins decide."""
     worst = np.inf
+    skipped = 0
     for c in all_cases:
         for k in c.map_margins:
             mapped, in_state = {i for i, _ in c.expect[k][1]}, {i for i, _ in c.expect[k][0]}
             keep = c.kept.get(k)
+            for p in FC.kept_cloud(c, k):
+                dw, _ = MW.weighted_distances(c.map_xy, c.map_cov, np.float32(p[0]), np.float32(p[1]))
+                n_nan = int(np.isnan(dw).sum())
+                assert n_nan == 0 or hasattr(c, "nan_at"), (c.name, k)
+                skipped += n_nan
             for q, (a, b, inside) in enumerate(c.map_margins[k]):
                 i = q if keep is None else keep[q]
                 assert inside == (i in mapped), (c.name, k, i)
@@ -97,7 +143,8 @@ def test_margins(all_cases):
                 if not inside:
                     sa, sb = c.margins[k][q]
                     assert sa >= MC.MARGIN_MIN and (sb >= MC.MARGIN_MIN or i not in in_state), (c.name, k, i, sa, sb)
-    print(f"\nsmallest distance of a best weighted distance from the map gate, in metres: {worst:.3e}")
+    print(f"\nsmallest distance of a best weighted distance from the map gate, in metres: {worst:.3e}; NaN distances skipped: {skipped}")
+    assert skipped == 5 + 1 + 2 * 129 + 1 + 1
 
 
 @needs_ld
@@ -164,7 +211,10 @@ def test_transposed_weight_is_the_same_distance(all_cases):
         for p in c.events[0][3]:
             a, _ = MW.weighted_distances(c.map_xy, c.map_cov, np.float32(p[0]), np.float32(p[1]))
             b, _ = MW.weighted_distances(c.map_xy, c.map_cov, np.float32(p[0]), np.float32(p[1]), column_major=True)
-            worst = max(worst, float(np.abs(a - b).max() / a.max()))
+            ok = ~(np.isnan(a) | np.isnan(b))                    # (a NaN distance is NaN either way: nan_cases)
+            assert np.array_equal(np.isnan(a), np.isnan(b))
+            if ok.any():
+                worst = max(worst, float(np.abs(a[ok] - b[ok]).max() / a[ok].max()))
     print(f"\nrow-major against column-major weights: largest relative difference of a distance {worst:.2e}")
     assert worst < 1e-15
     assert "cov_column_major" in MW.UNOBSERVABLE_MUTATIONS and "cov_column_major" not in MW.MAP_MUTATIONS

@@ -33,7 +33,10 @@ def test_all_cases_in_lockstep():
 
     Measured on the MI355X: worst 0.75 x the floor in sigma (mix_5_5_5_L5), 0.82 x in mu (fix_16_16).  fix_0_31 (n = 3, 31 map
     pairs and a pose fix) was 242 x in mu while the fix followed the reflector rows; with the fix in front of them (what
-    k_fleet_step_map does for a member on the map) it is 0.56 x."""
+    k_fleet_step_map does for a member on the map) it is 0.56 x.  The nine nan cases (a NaN weighted distance
+    never wins: the `dist == dist` in the lane loop of the map sweep) are among the cases; the single filter's sweep has no such
+    compare yet, and nan_p0_q1, nan_p5_q69, nan_p5_q37 and nan_nearest_5_runner_up_69 come out as new reflectors there
+    (tests/test_ekf_map_gpu.py, KNOWN_DIVERGENCES)."""
     worst_s, worst_m, misses = MC.run_lockstep(MC.all_cases())
     print(f"\nworst over {len(MC.all_cases())} map cases: sigma {worst_s[0]:.2f} x the FP64 floor at {worst_s[1]}, "
           f"mu {worst_m[0]:.2f} x at {worst_m[1]} (the bound is {FC.GPU_FACTOR:.0f} x); {len(misses)} misses")
