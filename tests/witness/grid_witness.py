@@ -1,4 +1,4 @@
-"""tests/witness/grid_witness.py -- TEST INFRASTRUCTURE: second, independent statements of four grid-mapper pieces whose
+"""tests/witness/grid_witness.py -- TEST INFRASTRUCTURE: second, independent statements of five grid-mapper pieces whose
 only other restatement is oracle/grid_oracle.c (reference: src/mapping/probability_grid_range_data_inserter_2d.cc:40-114
 with ray_to_pixel_mask.cc:17-168, probability_values.cc; src/scan_matching/real_time_correlative_scan_matcher_2d.cc:20-136).
 
@@ -14,6 +14,11 @@ with ray_to_pixel_mask.cc:17-168, probability_values.cc; src/scan_matching/real_
   * refine_cost_witness: the objective of the Ceres refinement (ceres_scan_matcher_2d.cc:26-62 with
     occupied_space_cost_function_2d.cc:25-81) at one pose, in longdouble, the bicubic interpolation as a tensor product of
     Catmull-Rom weights over all points at once; the oracle and the kernel nest two Horner splines point by point.
+  * refine_eval_witness / refine_solve_witness: the refinement's derivatives and its trust-region loop in longdouble -- the
+    stacked (n + 3) x 3 Jacobian with g = J'r and H = J'J as matrix products, the derivative weights DERIVED from the value
+    weights (numpy.polynomial), the damped 3 x 3 system by Cramer's rule, a trace of every decision and its distance from the
+    threshold; the oracle and the kernels keep ten running sums, type the Hermite derivative in and factor by Cholesky.
+    SOLVER_MUTANTS: eight deliberately wrong pieces of it, for the test that shows tests/refine_solver_cases.py sees each.
 All of them take `mutant`: the grid convention transposed in one place (MUTANTS), for the tests that show which fixtures can
 tell the convention from its transpose (tests/grid_geometry_cases.py for the matchers, tests/grid_write_cases.py for
 insert_witness and grow_witness).
@@ -270,12 +275,31 @@ def match_witness(initial_pose, points_xy, cells, resolution, max_xy, linear_sea
 K_PADDING = 536870911          # kPadding = INT_MAX / 4 (occupied_space_cost_function_2d.cc:57)
 
 
+def _catmull_rom_terms(t):
+    """The four Catmull-Rom basis weights as a tuple; t is anything with + - * and / by a number (an array, a Polynomial)."""
+    t2 = t * t
+    t3 = t2 * t
+    return (-t3 + 2 * t2 - t) / 2, (3 * t3 - 5 * t2 + 2) / 2, (-3 * t3 + 4 * t2 + t) / 2, (t3 - t2) / 2
+
+
 def _catmull_rom_weights(t):
     """The four Catmull-Rom basis weights of the samples at -1, 0, 1, 2 for the offset t in [0, 1): ceres::CubicHermiteSpline
     written as a weighted sum of its four samples.  t: longdouble (n,) -> (4, n)."""
-    t2 = t * t
-    t3 = t2 * t
-    return np.stack([(-t3 + 2 * t2 - t) / 2, (3 * t3 - 5 * t2 + 2) / 2, (-3 * t3 + 4 * t2 + t) / 2, (t3 - t2) / 2])
+    return np.stack(_catmull_rom_terms(t))
+
+
+def _catmull_rom_derivative_weights(t):
+    """d/dt of _catmull_rom_weights, DERIVED from it: the value weights evaluated on the polynomial `t` itself
+    (numpy.polynomial.Polynomial), differentiated with .deriv(), the coefficients (halves of integers, exact) applied in
+    longdouble.  Nothing about the derivative is typed in.  t: longdouble (n,) -> (4, n)."""
+    from numpy.polynomial import Polynomial
+    out = []
+    for w in _catmull_rom_terms(Polynomial([0.0, 1.0])):
+        acc = np.zeros_like(t)
+        for c in w.deriv().coef[::-1]:
+            acc = acc * t + np.longdouble(c)
+        out.append(acc)
+    return np.stack(out)
 
 
 def refine_cost_witness(pose, target_translation, initial_angle, points_xy, cells, resolution, max_xy, w_occ, w_t, w_r, mutant=None):
@@ -312,3 +336,241 @@ def refine_cost_witness(pose, target_translation, initial_angle, points_xy, cell
     d = np.array([LD(w_t) * (LD(x) - LD(float(target_translation[0]))), LD(w_t) * (LD(y) - LD(float(target_translation[1]))),
                   LD(w_r) * (LD(th) - LD(float(initial_angle)))])
     return LD(0.5) * ((occ * occ).sum() + (d * d).sum())
+
+
+# ---- the refinement's derivatives and its solver ----------------------------------------------------------------------------
+# Deliberately wrong solver pieces (tests/test_refine_solver_cpu.py shows that the cases of tests/refine_solver_cases.py see
+# each of them; no kernel with a planted defect exists).  The first three act in refine_eval_witness, the others in
+# refine_solve_witness:
+#   angle_dwx_sign        d(world x)/d(angle) with the wrong sign in the angle column
+#   dvdq_value_rows       d(value)/d(column) interpolated from the value rows instead of the derivative rows (it IS the value then)
+#   angle_without_ninv    the angle column without its factor -1 / resolution
+#   jacobi_rescaled       the Jacobi scaling recomputed at every accepted step instead of fixed at iteration 0
+#   lm_no_floor           the LM diagonal without its floor of 1e-6
+#   rho_first_ratio       step quality from the first ratio only (no non-monotonic reference)
+#   radius_no_cap         the radius update without the cap of 1/3 on its divisor
+#   last_iterate          the answer = the last iterate, not the accepted iterate of least cost
+SOLVER_MUTANTS = ("angle_dwx_sign", "dvdq_value_rows", "angle_without_ninv", "jacobi_rescaled", "lm_no_floor", "rho_first_ratio",
+                  "radius_no_cap", "last_iterate")
+
+
+def _split_mutant(mutant):
+    """-> (geometry mutant, solver mutant): `mutant` is one of MUTANTS, one of SOLVER_MUTANTS or None."""
+    assert mutant is None or mutant in MUTANTS or mutant in SOLVER_MUTANTS, mutant
+    return (None, mutant) if mutant in SOLVER_MUTANTS else (mutant, None)
+
+
+def refine_eval_witness(pose, target_translation, initial_angle, points_xy, cells, resolution, max_xy, w_occ, w_t, w_r, mutant=None,
+                        padding=True):
+    """-> (cost, g[3], H[3, 3]) as np.longdouble: cost = 1/2 |r|^2 of refine_cost_witness, g = J'r, H = J'J with J the stacked
+    (n + 3) x 3 Jacobian of the residuals (n occupied-space rows, two translation rows, one rotation row).
+
+    Coordinates as in refine_cost_witness: the padded (row, column) in float64 with kPadding added, everything after it
+    longdouble.  Value and both partial derivatives are tensor products over the 4 x 4 taps, all points at once; the derivative
+    weights are _catmull_rom_derivative_weights (derived from the value weights, not typed in).  g and H are matrix products of
+    the stacked J -- no running sums.  `padding=False` leaves kPadding out and forms the coordinates in longdouble from a
+    longdouble pose: the objective is then smooth inside a cell, which is what the finite-difference check of
+    tests/test_refine_solver_cpu.py needs.  `mutant`: one of MUTANTS or of SOLVER_MUTANTS."""
+    LD = np.longdouble
+    geo, sol = _split_mutant(mutant)
+    pts = np.ascontiguousarray(points_xy, f32).reshape(-1, 2).astype(np.float64)
+    n = pts.shape[0]
+    flat, nx, ny, max_x, max_y, bound_x, bound_y, stride = _geometry(cells, max_xy, geo)
+    if padding:
+        x, y, th = (float(v) for v in pose)
+        c, s = math.cos(th), math.sin(th)
+        wx = c * pts[:, 0] - s * pts[:, 1] + x
+        wy = s * pts[:, 0] + c * pts[:, 1] + y
+        r = (max_x - wx) / resolution - 0.5 + float(K_PADDING)          # float64, rounding included
+        q = (max_y - wy) / resolution - 0.5 + float(K_PADDING)
+        rf, qf = np.floor(r), np.floor(q)
+        row, col = rf.astype(np.int64) - K_PADDING, qf.astype(np.int64) - K_PADDING
+        tr, tq = r.astype(LD) - rf.astype(LD), q.astype(LD) - qf.astype(LD)
+    else:
+        x, y, th = (LD(v) for v in pose)
+        c, s = np.cos(th), np.sin(th)
+        p = pts.astype(LD)
+        r = (LD(max_x) - (c * p[:, 0] - s * p[:, 1] + x)) / LD(resolution) - LD(0.5)
+        q = (LD(max_y) - (s * p[:, 0] + c * p[:, 1] + y)) / LD(resolution) - LD(0.5)
+        rf, qf = np.floor(r), np.floor(q)
+        row, col = rf.astype(np.int64), qf.astype(np.int64)
+        tr, tq = r - rf, q - qf
+    tap = np.arange(-1, 3)
+    cy = (row[None, :] + tap[:, None])[:, None, :]                      # [4, 1, n]
+    cx = (col[None, :] + tap[:, None])[None, :, :]                      # [1, 4, n]
+    inside = (cx >= 0) & (cy >= 0) & (cx < bound_x) & (cy < bound_y)
+    taps = np.where(inside, value_to_cost(_load(flat, nx, ny, stride, cx, cy)), f32(0.9)).astype(LD)     # [4, 4, n]
+    wr, wc = _catmull_rom_weights(tr), _catmull_rom_weights(tq)
+    dwr, dwc = _catmull_rom_derivative_weights(tr), _catmull_rom_derivative_weights(tq)
+    bicubic = (wr[:, None, :] * wc[None, :, :] * taps).sum(axis=(0, 1))
+    dvdr = (dwr[:, None, :] * wc[None, :, :] * taps).sum(axis=(0, 1))
+    dvdq = (wr[:, None, :] * dwc[None, :, :] * taps).sum(axis=(0, 1)) if sol != "dvdq_value_rows" else bicubic
+    px, py = pts[:, 0].astype(LD), pts[:, 1].astype(LD)
+    cl, sl = LD(c), LD(s)
+    dwx, dwy = -sl * px - cl * py, cl * px - sl * py                    # d world / d angle
+    if sol == "angle_dwx_sign":
+        dwx = -dwx
+    ninv = -LD(1) / LD(resolution)                                      # d row / d world x = d column / d world y
+    scale = LD(w_occ) / np.sqrt(LD(n))
+    J = np.zeros((n + 3, 3), LD)
+    J[:n, 0], J[:n, 1] = scale * dvdr * ninv, scale * dvdq * ninv
+    J[:n, 2] = scale * (dvdr * dwx + dvdq * dwy) * (ninv if sol != "angle_without_ninv" else LD(1))
+    J[n, 0] = J[n + 1, 1] = LD(w_t)
+    J[n + 2, 2] = LD(w_r)
+    occ = LD(w_occ) / np.sqrt(LD(n)) * bicubic
+    d = np.array([LD(w_t) * (LD(x) - LD(float(target_translation[0]))), LD(w_t) * (LD(y) - LD(float(target_translation[1]))),
+                  LD(w_r) * (LD(th) - LD(float(initial_angle)))])
+    res = np.concatenate([occ, d])
+    return LD(0.5) * ((occ * occ).sum() + (d * d).sum()), J.T @ res, J.T @ J
+
+
+def _double_range(v):
+    """`v` (longdouble) with every entry that is not finite AS A FLOAT64 replaced by that float64 (inf, nan)."""
+    v = np.asarray(v, np.longdouble)
+    f = v.astype(np.float64)
+    return np.where(np.isfinite(f), v, f.astype(np.longdouble))[()]
+
+
+def _det3(M):
+    return (M[0, 0] * (M[1, 1] * M[2, 2] - M[1, 2] * M[2, 1]) - M[0, 1] * (M[1, 0] * M[2, 2] - M[1, 2] * M[2, 0])
+            + M[0, 2] * (M[1, 0] * M[2, 1] - M[1, 1] * M[2, 0]))
+
+
+def _cramer3(A, b):
+    d = _det3(A)
+    out = []
+    for k in range(3):
+        M = A.copy()
+        M[:, k] = b
+        out.append(_det3(M) / d)
+    return np.array(out, np.longdouble)
+
+
+def refine_solve_witness(target_translation, initial_pose, points_xy, cells, resolution, max_xy, w_occ=1.0, w_t=0.1, w_r=0.4,
+                         max_num_iterations=100, use_nonmonotonic_steps=True, mutant=None):
+    """CeresScanMatcher2D::Match (ceres_scan_matcher_2d.cc:26-62) under the solver options of src/ros_node.cc:364-377, the
+    trust-region loop as oracle/grid_oracle.c documents it, in longdouble on top of refine_eval_witness.
+    -> (pose float64 (3,), summary, trace).
+
+    Differently built than the oracle and the kernels: g and H come from the stacked Jacobian, the damped 3 x 3 system is solved by
+    Cramer's rule (no Cholesky), the model cost change is -(d'g) - d'Hd / 2 in matrix products.  Two places keep the precision of
+    the real solver ON PURPOSE: the iterate is rounded to float64 after every step (the solver's parameters are doubles), and a
+    total (cost, g, H) that is not finite as a float64 counts as not finite, so that weights which overflow a double take the
+    invalid-step branch here as they do in a double solver although longdouble could carry them.
+
+    summary: initial_cost, final_cost (longdouble), iterations, termination (0 convergence, 1 no convergence, 2 failure) and
+    margin = the smallest distance of any decision from its threshold: function tolerance, parameter tolerance and rho against
+    1e-3 as |value - threshold| / threshold; cost < min_cost, ev_cur < ev_min and ev_cur > ev_cand as |difference of the two
+    costs| / (model cost change of the step that produced the newer one) -- the unit in which the solver itself judges a cost
+    change (rho is such a quotient), and the quantity a reordered float64 sum moves by about 1e-12.  Relative to the COST these
+    three could never keep a margin of 1e-3: a run that ends by function tolerance has just accepted steps that changed the
+    cost by little more than 1e-6 of it.
+    trace: one letter per decision of the loop -- a accepted with the cost down, n accepted with the cost up, r rejected,
+    I invalid step; then how it ended -- M iteration limit, G gradient tolerance, P parameter tolerance, F function tolerance,
+    Z radius below its minimum, X failure (five invalid steps in a row)."""
+    LD = np.longdouble
+    _, sol = _split_mutant(mutant)
+    tt = (float(target_translation[0]), float(target_translation[1]))
+    a0 = float(initial_pose[2])
+
+    def ev(p):
+        c_, g_, H_ = refine_eval_witness(p, tt, a0, points_xy, cells, resolution, max_xy, w_occ, w_t, w_r, mutant=mutant)
+        return _double_range(c_), _double_range(g_), _double_range(H_)
+
+    margins = []
+
+    def near(a, b):                                                     # a decision `a against the threshold b`
+        if np.isfinite(a) and np.isfinite(b) and b != 0:
+            margins.append(float(abs(a - b) / abs(b)))
+
+    def near_cost(a, b, unit):                                          # a decision between two costs, in units of the step's mcc
+        if np.isfinite(a) and np.isfinite(b) and np.isfinite(unit) and unit > 0:
+            margins.append(float(abs(a - b) / unit))
+
+    jacobi = lambda H_: LD(1) / (LD(1) + np.sqrt(np.diag(H_)))
+    norm = lambda v: np.sqrt((np.asarray(v, LD) ** 2).sum())
+    with np.errstate(all="ignore"):
+        x = np.array([float(v) for v in initial_pose], np.float64)
+        cost, g, H = ev(x)
+        s = jacobi(H)
+        radius, decrease = LD(1e4), LD(2)
+        ev_min = ev_cur = ev_ref = ev_cand = initial = cost
+        acc_ref = acc_cand = LD(0)
+        nonmono = invalid = it = 0
+        max_nonmono = 5 if use_nonmonotonic_steps else 0
+        successful, best, min_cost, trace, mcc = True, x.copy(), LD(np.inf), [], LD(0)
+        while True:
+            if successful:
+                near_cost(cost, min_cost, mcc)
+                if cost < min_cost:
+                    min_cost, best = cost, x.copy()
+            if it >= int(max_num_iterations):
+                end, termination = "M", 1
+                break
+            if successful and np.abs(g).max() <= LD(1e-10):
+                end, termination = "G", 0
+                break
+            if radius < LD(1e-32):
+                end, termination = "Z", 0
+                break
+            it += 1
+            D = np.diag(s)
+            Hs, gs = D @ H @ D, D @ g
+            A = Hs + np.diag(np.clip(np.diag(Hs), LD(0.0 if sol == "lm_no_floor" else 1e-6), LD(1e32)) / radius)
+            step = -_cramer3(A, gs)
+            mcc = -(step @ gs) - LD(0.5) * (step @ Hs @ step)
+            if not (np.isfinite(step).all() and mcc > 0):
+                trace.append("I")
+                successful = False
+                invalid += 1
+                if invalid >= 5:
+                    end, termination = "X", 2
+                    break
+                radius, decrease = radius / decrease, decrease * 2
+                continue
+            invalid = 0
+            xc = (x.astype(LD) + D @ step).astype(np.float64)               # the solver's parameters are doubles
+            c_cost, cg, cH = ev(xc)
+            moved, enough = norm(x.astype(LD) - xc.astype(LD)), LD(1e-8) * (norm(x) + LD(1e-8))
+            near(moved, enough)
+            if moved <= enough:
+                end, termination = "P", 0
+                break
+            change, enough = abs(cost - c_cost), LD(1e-6) * cost
+            near(change, enough)
+            if change <= enough:
+                end, termination = "F", 0
+                break
+            rho = (ev_cur - c_cost) / mcc
+            if sol != "rho_first_ratio":
+                rho = max(rho, (ev_ref - c_cost) / (acc_ref + mcc))
+            near(rho, LD(1e-3))
+            if rho > LD(1e-3):
+                trace.append("a" if c_cost < cost else "n")
+                x, cost, g, H = xc, c_cost, cg, cH
+                if sol == "jacobi_rescaled":
+                    s = jacobi(H)
+                successful = True
+                t = 2 * rho - 1
+                shrink = 1 - t * t * t
+                radius = min(LD(1e16), radius / (shrink if sol == "radius_no_cap" else max(LD(1) / 3, shrink)))
+                decrease = LD(2)
+                ev_cur, acc_cand, acc_ref = c_cost, acc_cand + mcc, acc_ref + mcc
+                near_cost(ev_cur, ev_min, mcc)
+                if ev_cur < ev_min:
+                    ev_min, nonmono, ev_cand, acc_cand = ev_cur, 0, ev_cur, LD(0)
+                else:
+                    nonmono += 1
+                    near_cost(ev_cur, ev_cand, mcc)
+                    if ev_cur > ev_cand:
+                        ev_cand, acc_cand = ev_cur, LD(0)
+                if nonmono == max_nonmono:
+                    ev_ref, acc_ref = ev_cand, acc_cand
+            else:
+                trace.append("r")
+                successful = False
+                radius, decrease = radius / decrease, decrease * 2
+    last = sol == "last_iterate"
+    summary = {"initial_cost": initial, "final_cost": cost if last else min_cost, "iterations": it, "termination": termination,
+               "margin": min(margins) if margins else math.inf}
+    return (x if last else best).copy(), summary, "".join(trace) + end
