@@ -4,6 +4,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cstdio>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -118,6 +119,45 @@ public:
         t.slice_max_x = sm[0]; t.slice_max_y = sm[1];
         t.cells.resize(2 * (size_t)t.width * t.height);
         return t;
+    }
+    // Node::PublishMap up to the message fields (src/ros_node.cc:845-863,897-945; mode 0: nav_msgs::OccupancyGrid::data, info.width /
+    // height, info.origin.position) or the image of Node::HandleSaveMap (mode 1: the red bytes WritePgm writes, rows top to bottom);
+    // submap_origin = the translation of the submap's local pose
+    struct Occupancy { std::vector<int8_t> data; int width, height; double resolution, origin_x, origin_y; int box[4]; };
+    Occupancy OccupancyGrid(const std::array<double, 2> &submap_origin, int mode = 0)
+    {
+        const Limits l = GetLimits();
+        Occupancy o;
+        o.data.resize(((size_t)l.num_x_cells + 11) * ((size_t)l.num_y_cells + 11));
+        int size[2] = {0, 0};
+        double origin[2] = {0., 0.};
+        chk(rgrid_occupancy_grid(h_, mode, submap_origin.data(), o.data.data(), (long)o.data.size(), size, origin, o.box), "OccupancyGrid");
+        o.width = size[0]; o.height = size[1]; o.resolution = l.resolution; o.origin_x = origin[0]; o.origin_y = origin[1];
+        o.data.resize((size_t)o.width * o.height);
+        return o;
+    }
+    // Node::HandleSaveMap's grid map (ros_node.cc:969-996): filebase.pgm and filebase.yaml with WritePgm's and WriteYaml's bytes
+    void SaveMap(const std::array<double, 2> &submap_origin, const std::string &filebase)
+    {
+        const Occupancy o = OccupancyGrid(submap_origin, 1);
+        const std::string pgm = filebase + ".pgm", yaml = filebase + ".yaml";
+        const std::string header = "P5\n# Cartographer map; " + std::to_string(o.resolution) + " m/pixel\n" + std::to_string(o.width) + " " +
+                                   std::to_string(o.height) + "\n255\n";
+        const std::string text = "image: " + pgm + "\n" + "resolution: " + std::to_string(o.resolution) + "\n" + "origin: [" +
+                                 std::to_string(o.origin_x) + ", " + std::to_string(o.origin_y) +
+                                 ", 0.0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n";
+        // both files are opened before either is written, a short write or a failed close throws, and a pair that is not complete
+        // is removed
+        std::FILE *fp = std::fopen(pgm.c_str(), "wb");
+        if (!fp) throw GridError(RGRID_ERR_INVALID, "SaveMap: cannot open the .pgm");
+        std::FILE *fy = std::fopen(yaml.c_str(), "wb");
+        if (!fy) { std::fclose(fp); std::remove(pgm.c_str()); throw GridError(RGRID_ERR_INVALID, "SaveMap: cannot open the .yaml"); }
+        bool ok = std::fwrite(header.data(), 1, header.size(), fp) == header.size();
+        ok = std::fwrite(o.data.data(), 1, o.data.size(), fp) == o.data.size() && ok;
+        ok = std::fwrite(text.data(), 1, text.size(), fy) == text.size() && ok;
+        ok = (std::fclose(fp) == 0) && ok;
+        ok = (std::fclose(fy) == 0) && ok;
+        if (!ok) { std::remove(pgm.c_str()); std::remove(yaml.c_str()); throw GridError(RGRID_ERR_INVALID, "SaveMap: short write"); }
     }
     // mapping::MapBuilder::AddRangeData  (map_builder.cc:57-108) in one call; false where the reference returns nullptr
     bool AddRangeData(const rgrid_map_builder_options &opt, const std::array<float, 2> &origin, const Cloud &returns, const Cloud &misses,

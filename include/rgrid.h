@@ -354,6 +354,50 @@ int rgrid_batch_texture_submit(rgrid_batch_t *b, const int *grids, int count);
  * RGRID_ERR_INVALID without a pending texture submit (a pending submit of another kind stays pending). */
 int rgrid_batch_texture_collect(rgrid_batch_t *b, int *boxes, double *slice_max, long *offsets, uint8_t *cells, long cap);
 
+/* ---- occupancy grid and saved map: Node::PublishMap (src/ros_node.cc:845-863: ToSubmapTexture -> io::FillSubmapSlice ->
+ * io::PaintSubmapSlices, src/io/submap_painter.cc:44-112 -> Node::CreateOccupancyGridMsg, ros_node.cc:897-945) and the image of
+ * Node::HandleSaveMap (:947-1001, WritePgm :865-881) for the resident grid, without cairo.  The reference paints the texture onto a
+ * background of red 128 through a transform that is a turn by 90 degrees and a translation; inside the domain below the painting is a
+ * closed form (pinned against libcairo by tests/test_occupancy_cpu.py): the image has size = (height + 10, width + 10)
+ * of the texture -- or 11 where the reference's float32 bounding box rounds up, the extra column or row at the far end -- texture pixel
+ * (u, v) lies at image pixel (height + 4 - v, u + 5) with red = min(255, value + mul8(255 - alpha, 128)), everything else is background.
+ * mode 0: the occupancy values in message order (nav_msgs::OccupancyGrid::data: image rows bottom-up; -1 where nothing was observed,
+ * else RoundToInt((1. - red / 255.) * 100.)); mode 1: the red bytes in image order, the body of the PGM.  Another mode is
+ * RGRID_ERR_INVALID.  size = (width, height) of the image, origin = info.origin.position = the YAML origin of the saved map
+ * (-origin.x * resolution, (-height + origin.y) * resolution), box = the known-cells box as rgrid_draw_texture gives it.
+ * submap_origin = the translation of the submap's local pose (the float origin cast to double, submap_2d.cc:18-24): the reference's
+ * slice_pose is slice_max - submap_origin, and adding it back is not always slice_max.
+ * Domain: both |translation / resolution| below 16384 pixels and both image sides at most 32767 (cairo's limit); outside it the call
+ * is RGRID_ERR_CAPACITY with box filled and nothing else written.  out needs size[0] * size[1] bytes -- (num_x_cells + 11) *
+ * (num_y_cells + 11) always suffices; RGRID_ERR_BUFFER reports size, origin and box.
+ * The ABI version stays 4: a caller that may meet an older library looks for these symbols. */
+int rgrid_occupancy_grid(rgrid_t *h, int mode, const double submap_origin[2], int8_t *out, long cap,
+                         int size[2], double origin[2], int box[4]);
+
+/* ---- fleet occupancy grid: the above for the resident slots of many robots, ONE launch and ONE synchronisation per call
+ * (kgb_occupancy, one workgroup per named slot, csrc/rgrid_batch.hip).  The specification is the single call: for every named slot,
+ * size, origin, box and the bytes are exactly what rgrid_occupancy_grid returns from an rgrid_t holding the same grid.  The kernel
+ * finds the box, looks every cell of it up in the byte table of the call's mode and writes the turned block into pinned host memory;
+ * collect puts the frame of background around it in the copy it makes anyway.  The call only reads the slots.  The two byte tables are
+ * uploaded by the handle's first occupancy submit; the output area (num_x_cells * (num_y_cells rounded up to 16) bytes per named slot)
+ * and the box records are allocated by it too and grow only when a later call needs more. */
+
+/* Enqueues the occupancy grids (mode 0) or images (mode 1) of slots grids[0 .. count), submap_origins = 2 * count doubles, and returns
+ * without waiting.  Refused as a whole with RGRID_ERR_INVALID, nothing launched and the handle still usable: what
+ * rgrid_batch_texture_submit refuses, a null submap_origins with count > 0, another mode.  The same slot may be named more than once.
+ * count == 0 is a submit with nothing launched. */
+int rgrid_batch_occupancy_submit(rgrid_batch_t *b, int mode, const int *grids, const double *submap_origins, int count);
+
+/* Waits once and hands out the pending occupancy submit's results in its order: status (count), sizes (2 * count), origins
+ * (2 * count), boxes (4 * count), offsets (count: the byte in `out` where image j starts) and the images back to back in `out`,
+ * sizes[2j] * sizes[2j + 1] bytes each.  A slot outside the domain has status RGRID_ERR_CAPACITY, size (0, 0), origin (0, 0) and no
+ * bytes; its neighbours are unaffected.  RGRID_ERR_BUFFER when cap is below the sum, or out is NULL with a sum that is not 0: all but
+ * the bytes is filled and the submit is LEFT PENDING, the caller comes again with room; cap = sum of (num_x_cells + 11) *
+ * (num_y_cells + 11) always suffices.  RGRID_ERR_INVALID without a pending occupancy submit (a pending submit of another kind stays
+ * pending). */
+int rgrid_batch_occupancy_collect(rgrid_batch_t *b, int *status, int *sizes, double *origins, int *boxes,
+                                  long *offsets, int8_t *out, long cap);
+
 int rgrid_batch_sizeof_scan(void);
 int rgrid_batch_sizeof_refine_scan(void);
 int rgrid_batch_sizeof_insert_scan(void);

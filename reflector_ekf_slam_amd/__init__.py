@@ -9,5 +9,6 @@ from .ekf_slam import (DIFF, OMNI, EKFOptions, Map, Observation, OdometryData,  
                        ReflectorEKFSLAM, ReflectorMatchResult, RekfError, State)
 from .fleet import ReflectorEKFSLAMFleet  # noqa: F401
 from .fleet_detect import LaserReflectorDetectFleet, PointCloud, PointCloudReflectorDetectFleet, cloud_events, scan_events  # noqa: F401
-from .fleet_match import (FleetFilterResult, FleetRefineResult, FleetScanMatchResult, FleetTexture, RgridBatchFilterScan,  # noqa: F401
+from .grid import OccupancyGrid  # noqa: F401
+from .fleet_match import (FleetFilterResult, FleetOccupancyGrid, FleetRefineResult, FleetScanMatchResult, FleetTexture, RgridBatchFilterScan,  # noqa: F401
                           RgridBatchInsertScan, ScanMatchFleet, gravity_aligned_scans, pose_fixes)

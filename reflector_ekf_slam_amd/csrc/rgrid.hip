@@ -461,6 +461,15 @@ __global__ __launch_bounds__(256) void kg_texture(const unsigned short *__restri
     if (x < w) out[(size_t)w * y + x] = table[cells[(size_t)nx * (y0 + y) + (x0 + x)] & 32767u];
 }
 
+// The interior block of the painted texture (Node::PublishMap / HandleSaveMap) for the box kg_known_box found: the
+// device text of kgb_occupancy's phase 2, the tiles spread over the launch's workgroups
+__global__ __launch_bounds__(256) void kg_occupancy(const unsigned short *__restrict__ cells, int nx, int x0, int y0, int w, int hh,
+                                                    const unsigned char *__restrict__ table, unsigned char *__restrict__ out)
+{
+    __shared__ __align__(16) unsigned char s_tile[OCC_T][OCC_PITCH];
+    occupancy_tiles(cells, nx, x0, y0, w, hh, table, out, s_tile, (int)blockIdx.x, (int)gridDim.x);
+}
+
 }  // namespace
 
 struct rgrid {
@@ -476,6 +485,10 @@ struct rgrid {
     unsigned short *d_cells2;                   // second grid buffer: target of a growth (then swapped with d_cells), texture staging
     unsigned short *d_tex;                      // (value, alpha) table of the texture export, built on first use
     int *d_box, *h_box;
+    unsigned char *d_occ_tables;                // the occupancy grid's two byte tables (occupancy, then red), built on first use
+    unsigned char *d_occ;                       // ... and its interior block on the device, occ_bytes long, grown when a grid needs more
+    size_t occ_bytes;
+    std::vector<unsigned char> h_occ;           // the block on the host
     float *d_mis;                               // misses of an insertion
     int2 *d_ends;
     int *d_bad;
@@ -580,6 +593,53 @@ int rgrid_draw_texture(rgrid_t *h, uint8_t *cells, long cap, int box[4], double 
     return RGRID_OK;
 }
 
+int rgrid_occupancy_grid(rgrid_t *h, int mode, const double submap_origin[2], int8_t *out, long cap, int size[2], double origin[2], int box[4])
+{
+    if (!h || !submap_origin || !out || !size || !origin || !box || !h->have_grid || (mode != OCC_MODE_OCCUPANCY && mode != OCC_MODE_IMAGE))
+        return RGRID_ERR_INVALID;
+    G_TRY(h, hipSetDevice(h->device));
+    if (!h->d_occ_tables) {
+        std::vector<unsigned char> t(2 * 32768);
+        occupancy_tables(reinterpret_cast<signed char *>(t.data()), t.data() + 32768);
+        unsigned char *d = nullptr;
+        G_TRY(h, hipMalloc(&d, 2 * 32768));
+        if (hipMemcpy(d, t.data(), 2 * 32768, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); h->hip_error = "occupancy tables: upload failed"; return RGRID_ERR_HIP; }
+        h->d_occ_tables = d;
+    }
+    const size_t need = occupancy_block_bytes(h->nx, h->ny);
+    if (need > h->occ_bytes) {
+        (void)hipFree(h->d_occ);
+        h->d_occ = nullptr; h->occ_bytes = 0;
+        G_TRY(h, hipMalloc(&h->d_occ, need));
+        h->occ_bytes = need;
+    }
+    h->h_box[0] = h->h_box[1] = INT_MAX; h->h_box[2] = h->h_box[3] = -1;
+    G_TRY(h, hipMemcpyAsync(h->d_box, h->h_box, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(kg_known_box, dim3((h->nx + 255) / 256, h->ny), dim3(256), 0, h->stream, h->d_cells, h->nx, h->ny, h->d_box);
+    G_TRY(h, hipMemcpyAsync(h->h_box, h->d_box, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    G_TRY(h, hipStreamSynchronize(h->stream));
+    int x0 = h->h_box[0], y0 = h->h_box[1], x1 = h->h_box[2], y1 = h->h_box[3];
+    if (x1 < 0) { x0 = y0 = 0; x1 = y1 = 0; }                                     // nothing known: offset 0, CellLimits(1, 1) (grid_2d.cc:39-44)
+    const int w = x1 - x0 + 1, hh = y1 - y0 + 1;
+    box[0] = x0; box[1] = y0; box[2] = w; box[3] = hh;
+    OccupancyFrame F;
+    const int rc = occupancy_frame(box, h->resolution, h->max_x, h->max_y, submap_origin, &F);
+    if (rc != RGRID_OK) return rc;                                                // outside the domain: no image
+    size[0] = F.size[0]; size[1] = F.size[1]; origin[0] = F.origin[0]; origin[1] = F.origin[1];
+    if ((long)F.size[0] * F.size[1] > cap) return RGRID_ERR_BUFFER;
+    const int stride = occupancy_stride(hh);
+    const int tiles = ((w + OCC_T - 1) / OCC_T) * ((stride + OCC_T - 1) / OCC_T);
+    hipLaunchKernelGGL(kg_occupancy, dim3((unsigned)(tiles < 65536 ? tiles : 65536)), dim3(256), 0, h->stream, h->d_cells, h->nx, x0, y0, w, hh,
+                       h->d_occ_tables + (mode == OCC_MODE_IMAGE ? 32768 : 0), h->d_occ);
+    G_TRY(h, hipGetLastError());
+    const size_t bytes = (size_t)stride * (size_t)w;
+    if (h->h_occ.size() < bytes) h->h_occ.resize(bytes);
+    G_TRY(h, hipMemcpyAsync(h->h_occ.data(), h->d_occ, bytes, hipMemcpyDeviceToHost, h->stream));
+    G_TRY(h, hipStreamSynchronize(h->stream));
+    occupancy_paint(mode, h->h_occ.data(), w, hh, F.size, reinterpret_cast<unsigned char *>(out));
+    return RGRID_OK;
+}
+
 int rgrid_refine_match(rgrid_t *h, const rgrid_refine_options *opt, const double target_translation[2], const double initial_pose[3],
                        const float *points_xy, int n, double pose_estimate[3], rgrid_refine_summary *summary)
 {
@@ -678,7 +738,7 @@ void rgrid_destroy(rgrid_t *h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void *ptrs[] = {h->d_in, h->d_a, h->d_b, h->d_cs, h->d_key, h->d_idx, h->d_keep, h->d_cells, h->d_bb, h->d_best, h->d_count,
-                    h->d_hit, h->d_miss, h->d_mis, h->d_ends, h->d_bad, h->d_cells2, h->d_refine, h->d_tex, h->d_box, h->d_key_b, h->d_keep_b, h->d_counts};
+                    h->d_hit, h->d_miss, h->d_mis, h->d_ends, h->d_bad, h->d_cells2, h->d_refine, h->d_tex, h->d_box, h->d_occ_tables, h->d_occ, h->d_key_b, h->d_keep_b, h->d_counts};
     for (void *p : ptrs) (void)hipFree(p);
     if (h->h_pts) (void)hipHostFree(h->h_pts);
     if (h->h_count) (void)hipHostFree(h->h_count);

@@ -680,10 +680,6 @@ __global__ __launch_bounds__(KGF_THREADS) void kgb_filter(FilterBufs B)
 // 16-byte boundary and behind the last one singly, the eight-cell vectors between them whole -- and never touches the stale
 // max_cells - nx * ny cells behind it.  Phase 2 gathers single cells (a row of the box starts anywhere) and stores eight pairs at
 // once: the region's start is 16-byte aligned by the host's prefix sum, the last w * h mod 8 pairs go singly.
-#define KGT_THREADS 512
-#define KGT_WAVES (KGT_THREADS / 64)
-#define KGT_PF 4                          // 16-byte vectors of cells a thread has in flight in phase 1
-
 // One named slot of a texture call; an array of these lies at the start of the call's segment.
 struct TextureRec {
     long long cells_off;                  // its grid's first cell in the grid pool
@@ -705,52 +701,10 @@ __global__ __launch_bounds__(KGT_THREADS) void kgb_texture(TextureBufs B)
     __shared__ int s_box[KGT_WAVES][4];
     const TextureRec R = reinterpret_cast<const TextureRec *>(B.seg)[blockIdx.x];
     const unsigned short *__restrict__ cells = B.cells + R.cells_off;
-    const int nx = R.nx, n = R.nx * R.ny;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // ---- phase 1: the columns [x0, x1] and the linear indices [k0, k1] the known cells span; the rows follow from k0 and k1
-    int x0 = 0x7fffffff, x1 = -1, k0 = 0x7fffffff, k1 = -1;
-    auto see = [&](int k, int x) { x0 = min(x0, x); x1 = max(x1, x); k0 = min(k0, k); k1 = max(k1, k); };
-    const int to_boundary = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(cells) & 15u)) & 15u) >> 1);
-    const int head = min(n, to_boundary), nvec = (n - head) >> 3, tail = head + 8 * nvec;
-    for (int k = tid; k < head; k += KGT_THREADS)
-        if (cells[k] != 0) see(k, k % nx);
-    for (int k = tail + tid; k < n; k += KGT_THREADS)
-        if (cells[k] != 0) see(k, k % nx);
-    const uint4 *__restrict__ vec = reinterpret_cast<const uint4 *>(cells + head);
-    for (int v0 = 0; v0 < nvec; v0 += KGT_THREADS * KGT_PF) {
-        uint4 q[KGT_PF];
-#pragma unroll
-        for (int u = 0; u < KGT_PF; ++u) {
-            const int v = v0 + u * KGT_THREADS + tid;
-            q[u] = v < nvec ? vec[v] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int u = 0; u < KGT_PF; ++u) {
-            if ((q[u].x | q[u].y | q[u].z | q[u].w) == 0u) continue;                // eight unknown cells (or none at all)
-            const unsigned w32[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-            const int k = head + 8 * (v0 + u * KGT_THREADS + tid);
-            int x = k % nx;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                if (((w32[c >> 1] >> (16 * (c & 1))) & 0xffffu) != 0u) see(k + c, x);
-                if (++x == nx) x = 0;                                              // the vector runs on into the next row
-            }
-        }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        x0 = min(x0, __shfl_xor(x0, off, 64)); x1 = max(x1, __shfl_xor(x1, off, 64));
-        k0 = min(k0, __shfl_xor(k0, off, 64)); k1 = max(k1, __shfl_xor(k1, off, 64));
-    }
-    if (lane == 0) { s_box[wave][0] = x0; s_box[wave][1] = x1; s_box[wave][2] = k0; s_box[wave][3] = k1; }
-    __syncthreads();
-    for (int w = 0; w < KGT_WAVES; ++w) {
-        x0 = min(x0, s_box[w][0]); x1 = max(x1, s_box[w][1]); k0 = min(k0, s_box[w][2]); k1 = max(k1, s_box[w][3]);
-    }
-    int y0 = 0, y1 = 0;
-    if (x1 < 0) { x0 = 0; x1 = 0; }                                                // nothing known: offset 0, CellLimits(1, 1) (grid_2d.cc:39-44)
-    else { y0 = k0 / nx; y1 = k1 / nx; }
-    x0 = __builtin_amdgcn_readfirstlane(x0); y0 = __builtin_amdgcn_readfirstlane(y0);
-    const int w = __builtin_amdgcn_readfirstlane(x1 - x0 + 1), h = __builtin_amdgcn_readfirstlane(y1 - y0 + 1);
+    const int nx = R.nx, tid = threadIdx.x;
+    // ---- phase 1: the box of the known cells (known_box_of_slot, rgrid_dev.h)
+    int x0, y0, w, h;
+    known_box_of_slot(cells, nx, R.nx * R.ny, s_box, x0, y0, w, h);
     if (tid == 0) { int *box = B.box + 4 * blockIdx.x; box[0] = x0; box[1] = y0; box[2] = w; box[3] = h; }
     // ---- phase 2: pair o of the texture is cell (x0 + o % w, y0 + o / w); eight pairs per store
     const unsigned short *__restrict__ table = B.table;
@@ -776,6 +730,40 @@ __global__ __launch_bounds__(KGT_THREADS) void kgb_texture(TextureBufs B)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Node::PublishMap / Node::HandleSaveMap for a batch (src/ros_node.cc:845-863,947-1001): the painting of every named slot's
+// texture, ONE workgroup per named slot.  Phase 1 is kgb_texture's (known_box_of_slot); phase 2 writes the interior block of the
+// image -- the box turned by 90 degrees, every cell through the byte table of the call's mode -- to the slot's region of the output
+// area (occupancy_tiles, rgrid_dev.h).  The frame around the block, the row order of the message and the image's size and origin
+// are the host's, in the copy collect makes anyway.  The launch only reads the pool: no atomics, no workgroup waits for another, a
+// slot may be named more than once.  DESIGN.md 10.8.
+struct OccupancyRec {
+    long long cells_off;                  // its grid's first cell in the grid pool
+    long long out_off;                    // its region's first byte in the output area (a multiple of 16)
+    int nx, ny;
+};
+static_assert(sizeof(OccupancyRec) <= sizeof(BatchRec), "the occupancy records lie where a match's records lie");
+
+struct OccupancyBufs {
+    const unsigned char *seg;             // the call's segment: OccupancyRec[nrec]
+    const unsigned short *cells;          // grid pool
+    const unsigned char *table;           // the byte table of the call's mode, 32768 entries
+    unsigned char *out;                   // pinned host memory: a region of nx * occupancy_stride(ny) bytes per record
+    int *box;                             // [nrec][4]: offset_x, offset_y, width, height, pinned host memory
+};
+
+__global__ __launch_bounds__(KGT_THREADS) void kgb_occupancy(OccupancyBufs B)
+{
+    __shared__ int s_box[KGT_WAVES][4];
+    __shared__ __align__(16) unsigned char s_tile[OCC_T][OCC_PITCH];
+    const OccupancyRec R = reinterpret_cast<const OccupancyRec *>(B.seg)[blockIdx.x];
+    const unsigned short *__restrict__ cells = B.cells + R.cells_off;
+    int x0, y0, w, h;
+    known_box_of_slot(cells, R.nx, R.nx * R.ny, s_box, x0, y0, w, h);
+    if (threadIdx.x == 0) { int *box = B.box + 4 * blockIdx.x; box[0] = x0; box[1] = y0; box[2] = w; box[3] = h; }
+    occupancy_tiles(cells, R.nx, x0, y0, w, h, B.table, B.out + R.out_off, s_tile, 0, 1);
+}
+
 struct GridSlot {
     bool set = false;
     int nx = 0, ny = 0;
@@ -792,13 +780,16 @@ struct Pending {
 // what a packed match launches with
 struct MatchWork { int nrec, nwg, nf2, n_max; };
 
-enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3, KIND_INSERT = 4, KIND_FILTER = 5, KIND_TEXTURE = 6 };  // the pending submit
+enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3, KIND_INSERT = 4, KIND_FILTER = 5, KIND_TEXTURE = 6, KIND_OCCUPANCY = 7 };  // the pending submit
 
 // what collect needs of a scan of a filter submit
 struct FilterPending { int status, rec, out_off, n_ret, n_mis; };
 
 // what collect needs of a named slot of a texture submit
 struct TexturePending { int grid; long long out_off; };
+
+// what collect needs of a named slot of an occupancy submit
+struct OccupancyPending { int grid; long long out_off; double submap_origin[2]; };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -869,6 +860,17 @@ struct rgrid_batch {
         batch_host::Pinned<int> box;
         std::vector<TexturePending> sub;
     } tex;
+    // the occupancy grid (occupancy_staging): the two byte tables (occupancy, then red: 2 * 32768 bytes) on the device, uploaded by
+    // the first occupancy submit; the output area and the box records, allocated by it too, the area grown only when a call needs more
+    struct {
+        unsigned char *d_tables = nullptr;
+        batch_host::Pinned<unsigned char> out;
+        size_t out_bytes = 0;
+        batch_host::Pinned<int> box;
+        std::vector<OccupancyPending> sub;
+        std::vector<OccupancyFrame> frame;   // filled by collect
+        int mode = 0;                        // of the pending submit
+    } occ;
     // the submit that has not been collected
     bool outstanding = false;
     int kind = 0;                          // its KIND_*
@@ -1173,6 +1175,32 @@ int texture_staging(rgrid_batch_t *b, size_t pairs)
     return RGRID_OK;
 }
 
+// the occupancy grid's staging for a call that writes `bytes` bytes: the tables and the box records once, the output area when it is too small
+int occupancy_staging(rgrid_batch_t *b, size_t bytes)
+{
+    if (!b->occ.d_tables) {
+        std::vector<unsigned char> t(2 * 32768);
+        occupancy_tables(reinterpret_cast<signed char *>(t.data()), t.data() + 32768);
+        unsigned char *d = nullptr;
+        G_TRY(b, hipMalloc((void **)&d, 2 * 32768));
+        if (hipMemcpy(d, t.data(), 2 * 32768, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); b->hip_error = "occupancy tables: upload failed"; return RGRID_ERR_HIP; }
+        b->occ.d_tables = d;
+    }
+    if (!b->occ.box.h) {
+        b->occ.sub.resize((size_t)b->max_scans);
+        b->occ.frame.resize((size_t)b->max_scans);
+        G_TRY(b, b->occ.box.alloc(4 * (size_t)b->max_scans));
+    }
+    if (bytes > b->occ.out_bytes) {                                                // it never shrinks
+        G_TRY(b, hipStreamSynchronize(b->stream));                                 // (nothing is pending: the area is idle)
+        b->occ.out.release();
+        b->occ.out_bytes = 0;
+        G_TRY(b, b->occ.out.alloc(bytes));
+        b->occ.out_bytes = bytes;
+    }
+    return RGRID_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1243,11 +1271,12 @@ void rgrid_batch_destroy(rgrid_batch_t *b)
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     (void)hipFree(b->d_cells); (void)hipFree(b->res.d_bb); (void)hipFree(b->res.d_arrived);
-    (void)hipFree(b->ins.d_hit); (void)hipFree(b->ins.d_miss); (void)hipFree(b->tex.d_table);
+    (void)hipFree(b->ins.d_hit); (void)hipFree(b->ins.d_miss); (void)hipFree(b->tex.d_table); (void)hipFree(b->occ.d_tables);
     for (auto &s : b->seg.buf) s.release();
     b->res.best.release(); b->res.fine.release(); b->ins.bad.release();
     b->fil.in.release(); b->fil.out.release(); b->fil.cnt.release();
     b->tex.out.release(); b->tex.box.release();
+    b->occ.out.release(); b->occ.box.release();
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -1597,6 +1626,72 @@ int rgrid_batch_texture_collect(rgrid_batch_t *b, int *boxes, double *slice_max,
     b->outstanding = false;
     for (int j = 0; j < count; ++j)
         std::memcpy(cells + offsets[j], b->tex.out.h + b->tex.sub[(size_t)j].out_off, 2 * (size_t)boxes[4 * j + 2] * (size_t)boxes[4 * j + 3]);
+    return RGRID_OK;
+}
+
+int rgrid_batch_occupancy_submit(rgrid_batch_t *b, int mode, const int *grids, const double *submap_origins, int count)
+{
+    if (!b || count < 0 || count > b->max_scans || (count > 0 && (!grids || !submap_origins)) || b->outstanding) return RGRID_ERR_INVALID;
+    if (mode != OCC_MODE_OCCUPANCY && mode != OCC_MODE_IMAGE) return RGRID_ERR_INVALID;
+    size_t bytes = 0;
+    for (int j = 0; j < count; ++j) {
+        if (!slot_ok(b, grids[j])) return RGRID_ERR_INVALID;
+        const GridSlot &g = b->grids[(size_t)grids[j]];
+        bytes += occupancy_block_bytes(g.nx, g.ny);                                // a multiple of 16: every region starts on a 16-byte boundary
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    int k = 0;
+    if (count > 0) {                                                               // (a call without a slot allocates nothing and takes no segment)
+        G_TRY(b, hipSetDevice(b->device));
+        const int rc = occupancy_staging(b, bytes);
+        if (rc != RGRID_OK) return rc;
+        k = take_segment(b);
+        OccupancyRec *recs = reinterpret_cast<OccupancyRec *>(b->seg.pack.data());
+        long long at = 0;
+        for (int j = 0; j < count; ++j) {
+            const GridSlot &g = b->grids[(size_t)grids[j]];
+            OccupancyRec &R = recs[j];
+            R.cells_off = cells_offset(b, grids[j]);
+            R.out_off = at; R.nx = g.nx; R.ny = g.ny;
+            b->occ.sub[(size_t)j] = OccupancyPending{grids[j], at, {submap_origins[2 * j], submap_origins[2 * j + 1]}};
+            at += (long long)occupancy_block_bytes(g.nx, g.ny);
+        }
+        std::memcpy(b->seg.buf[k].h, recs, sizeof(OccupancyRec) * (size_t)count);
+        b->occ.mode = mode;
+    }
+    return submit_tail(b, KIND_OCCUPANCY, count, count, t_begin, [&] {
+        OccupancyBufs Of;
+        Of.seg = b->seg.buf[k].dv; Of.cells = b->d_cells; Of.table = b->occ.d_tables + (mode == OCC_MODE_IMAGE ? 32768 : 0);
+        Of.out = b->occ.out.dv; Of.box = b->occ.box.dv;
+        hipLaunchKernelGGL(kgb_occupancy, dim3((unsigned)count), dim3(KGT_THREADS), 0, b->stream, Of);
+    });
+}
+
+int rgrid_batch_occupancy_collect(rgrid_batch_t *b, int *status, int *sizes, double *origins, int *boxes, long *offsets, int8_t *out, long cap)
+{
+    int count = 0;
+    const int rc = collect_head(b, KIND_OCCUPANCY, status && sizes && origins && boxes && offsets, false, &count);   // the one wait: the kernel wrote boxes and blocks into host memory
+    if (rc != RGRID_OK) return rc;
+    long total = 0;
+    for (int j = 0; j < count; ++j) {
+        const OccupancyPending &P = b->occ.sub[(size_t)j];
+        const GridSlot &g = b->grids[(size_t)P.grid];
+        const int *box = b->occ.box.h + 4 * j;
+        OccupancyFrame &F = b->occ.frame[(size_t)j];
+        for (int c = 0; c < 4; ++c) boxes[4 * j + c] = box[c];
+        status[j] = occupancy_frame(box, g.resolution, g.max_x, g.max_y, P.submap_origin, &F);
+        if (status[j] != RGRID_OK) F = OccupancyFrame{{0, 0}, {0., 0.}};           // outside the domain: no image
+        sizes[2 * j] = F.size[0]; sizes[2 * j + 1] = F.size[1];
+        origins[2 * j] = F.origin[0]; origins[2 * j + 1] = F.origin[1];
+        offsets[j] = total;
+        total += (long)F.size[0] * F.size[1];
+    }
+    if (total > cap || (total > 0 && !out)) return RGRID_ERR_BUFFER;               // the submit stays pending: come again with room
+    b->outstanding = false;
+    for (int j = 0; j < count; ++j)
+        if (status[j] == RGRID_OK)
+            occupancy_paint(b->occ.mode, b->occ.out.h + b->occ.sub[(size_t)j].out_off, boxes[4 * j + 2], boxes[4 * j + 3], &sizes[2 * j],
+                            reinterpret_cast<unsigned char *>(out) + offsets[j]);
     return RGRID_OK;
 }
 

@@ -14,7 +14,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstring>
 #include <string>
+#include <vector>
 
 // a failed HIP call: its text into the handle's (rgrid_t / rgrid_batch_t) hip_error, RGRID_ERR_HIP to the caller
 #define G_TRY(h, expr)                                                              \
@@ -223,6 +225,210 @@ void texture_table(unsigned short *table)
         const int delta = 128 - li;
         const unsigned alpha = (unsigned)(delta > 0 ? 0 : -delta) & 255u, value = (unsigned)(delta > 0 ? delta : 0) & 255u;
         table[v] = (unsigned short)(value | ((value || alpha) ? alpha : 1u) << 8);
+    }
+}
+
+// ---- occupancy grid and saved map: what rgrid_occupancy_grid (rgrid.hip) and rgrid_batch_occupancy_* (rgrid_batch.hip) share.
+// The reference paints the submap texture with cairo (io::PaintSubmapSlices, src/io/submap_painter.cc:44-91) and reads the
+// painting back as nav_msgs::OccupancyGrid (Node::CreateOccupancyGridMsg, src/ros_node.cc:897-945) or as a PGM (Node::WritePgm,
+// :865-881).  The painting is the texture turned by 90 degrees inside a frame of background: texture pixel (u, v)
+// of a w x h texture lands at image pixel (h + 4 - v, u + 5).  Host side, ONE text: the two byte tables, the image's size and origin
+// (cairo's matrix arithmetic and Eigen's float32 box, replayed) and the copy of the device's rows into the frame.  Device side,
+// ONE text: the interior block, w rows of h bytes, row u column h - 1 - v = table[cell (x0 + u, y0 + v)].
+
+// The two byte tables, composed from texture_table: cairo's OVER of the premultiplied pixel (alpha, value, observed, 0) onto the
+// background (255, 128, 0, 0) leaves red = min(255, value + mul8(255 - alpha, 128)) with pixman's mul8; occupancy is -1 where
+// nothing was observed, else RoundToInt((1. - red / 255.) * 100.).
+void occupancy_tables(signed char *occupancy, unsigned char *red)
+{
+#pragma clang fp contract(off)
+    std::vector<unsigned short> tex(32768);
+    texture_table(tex.data());
+    for (int v = 0; v < 32768; ++v) {
+        const unsigned value = tex[(size_t)v] & 255u, alpha = tex[(size_t)v] >> 8;
+        const unsigned t = (255u - alpha) * 128u + 128u;
+        const unsigned over = value + ((t + (t >> 8)) >> 8);
+        red[v] = (unsigned char)(over > 255u ? 255u : over);
+        occupancy[v] = (value == 0u && alpha == 0u) ? (signed char)-1 : (signed char)std::lround((1. - red[v] / 255.) * 100.);
+    }
+}
+
+// cairo_matrix_t and cairo_matrix_multiply(r, a, b) as cairo 1.16 writes them out: every cairo_scale / cairo_transform call
+// replaces the CTM by (new matrix) * CTM
+struct CairoMatrix { double xx, yx, xy, yy, x0, y0; };
+CairoMatrix cairo_multiply(const CairoMatrix &a, const CairoMatrix &b)
+{
+#pragma clang fp contract(off)
+    CairoMatrix r;
+    r.xx = a.xx * b.xx + a.yx * b.xy;
+    r.yx = a.xx * b.yx + a.yx * b.yy;
+    r.xy = a.xy * b.xx + a.yy * b.xy;
+    r.yy = a.xy * b.yx + a.yy * b.yy;
+    r.x0 = a.x0 * b.xx + a.y0 * b.xy + b.x0;
+    r.y0 = a.x0 * b.yx + a.y0 * b.yy + b.y0;
+    return r;
+}
+
+// What the host knows of one painted texture
+struct OccupancyFrame {
+    int size[2];          // the image: width, height
+    double origin[2];     // OccupancyGrid::info.origin.position = the saved map's YAML origin
+};
+
+enum { OCC_MODE_OCCUPANCY = 0, OCC_MODE_IMAGE = 1 };
+
+// PaintSubmapSlices' first pass (submap_painter.cc:48-73) and the origin of CreateOccupancyGridMsg (ros_node.cc:914-917) for the
+// texture of box (offset_x, offset_y, width, height) of a grid with the given limits, in a submap whose local pose has translation
+// submap_origin.  RGRID_ERR_CAPACITY outside the domain in which the painting is the closed form above: the translation at or beyond
+// 16384 pixels (a float32 ulp of the corner coordinates above 1/1024 pixel) or an image side above cairo's 32767.
+int occupancy_frame(const int box[4], double resolution, double max_x, double max_y, const double submap_origin[2], OccupancyFrame *out)
+{
+#pragma clang fp contract(off)
+    const double r = resolution;
+    // slice_pose = local_pose^-1 * Translation(slice_max) (probability_grid.cc:122-126), submap.pose * submap.slice_pose puts it back
+    const double slice_max[2] = {max_x - r * box[1], max_y - r * box[0]};
+    const double t[2] = {(slice_max[0] - submap_origin[0]) + submap_origin[0], (slice_max[1] - submap_origin[1]) + submap_origin[1]};
+    if (!(std::fabs(t[0] / r) < 16384.) || !(std::fabs(t[1] / r) < 16384.)) return RGRID_ERR_CAPACITY;
+    CairoMatrix ctm = {1., 0., 0., 1., 0., 0.};
+    ctm = cairo_multiply(CairoMatrix{1. / r, 0., 0., 1. / r, 0., 0.}, ctm);        // cairo_scale(1 / resolution)
+    ctm = cairo_multiply(CairoMatrix{0., 1., -1., -0., t[0], -t[1]}, ctm);         // cairo_transform(homo(1,0), homo(0,0), -homo(1,1), -homo(0,1), ...)
+    ctm = cairo_multiply(CairoMatrix{r, 0., 0., r, 0., 0.}, ctm);                  // cairo_scale(submap_resolution)
+    float lo[2] = {0.f, 0.f}, hi[2] = {0.f, 0.f};
+    for (int c = 0; c < 4; ++c) {                                                  // Eigen::AlignedBox2f::extend of the four corners
+        const double x = (c & 1) ? (double)box[2] : 0., y = (c & 2) ? (double)box[3] : 0.;
+        const double dx = ctm.xx * x + ctm.xy * y, dy = ctm.yx * x + ctm.yy * y;   // cairo_matrix_transform_distance ...
+        const float p[2] = {(float)(dx + ctm.x0), (float)(dy + ctm.y0)};           // ... + the translation, then Vector2f(x, y)
+        for (int a = 0; a < 2; ++a) {
+            if (c == 0 || p[a] < lo[a]) lo[a] = p[a];
+            if (c == 0 || p[a] > hi[a]) hi[a] = p[a];
+        }
+    }
+    float org[2];
+    for (int a = 0; a < 2; ++a) {
+        const float extent = hi[a] - lo[a];
+        const double side = std::ceil(extent) + 10;                                // ceil(sizes()) + 2 * kPaddingPixel
+        if (!(side <= 32767.)) return RGRID_ERR_CAPACITY;
+        out->size[a] = (int)side;
+        org[a] = -lo[a] + 5.f;
+    }
+    out->origin[0] = (double)(-org[0]) * r;
+    out->origin[1] = (double)((float)(-out->size[1]) + org[1]) * r;                // int + float: a float32 sum
+    return RGRID_OK;
+}
+
+// Bytes between two rows of the interior block as the device writes it: rows start 16-byte aligned
+__host__ __device__ static inline int occupancy_stride(int h) { return (h + 15) & ~15; }
+// ... and what a grid of nx x ny cells needs at most for it (any box inside it)
+size_t occupancy_block_bytes(int nx, int ny) { return (size_t)nx * (size_t)occupancy_stride(ny); }
+
+// The image from the block: background everywhere (-1, or red 128), then row u of the block at image row u + 5, columns 5 .. h + 4;
+// the occupancy message lists the image's rows bottom-up (ros_node.cc:927).  A quirk row or column (size = side + 11) lies at the
+// far end and keeps the background.
+void occupancy_paint(int mode, const unsigned char *block, int w, int h, const int size[2], unsigned char *out)
+{
+    const size_t W = (size_t)size[0], H = (size_t)size[1];
+    std::memset(out, mode == OCC_MODE_OCCUPANCY ? 0xff : 128, W * H);
+    const size_t stride = (size_t)occupancy_stride(h);
+    for (int u = 0; u < w; ++u) {
+        const size_t Y = (size_t)u + 5, row = mode == OCC_MODE_OCCUPANCY ? H - 1 - Y : Y;
+        std::memcpy(out + row * W + 5, block + stride * (size_t)u, (size_t)h);
+    }
+}
+
+// The known-cells box of one slot, by one workgroup of KGT_THREADS threads (kgb_texture's and kgb_occupancy's phase 1): the slot is
+// walked as ONE array of n = nx * ny cells -- the cells in front of the first 16-byte boundary and behind the last one singly, the
+// eight-cell vectors between them whole.  Per-thread min / max, wave shuffles, LDS (s_box) across the waves; ends behind a barrier
+// with the box in every thread, wave-uniform: (0, 0, 1, 1) when no cell is known (grid_2d.cc:39-44).
+#define KGT_THREADS 512
+#define KGT_WAVES (KGT_THREADS / 64)
+#define KGT_PF 4                          // 16-byte vectors of cells a thread has in flight in phase 1
+__device__ static inline void known_box_of_slot(const unsigned short *__restrict__ cells, int nx, int n, int (*s_box)[4], int &bx0, int &by0,
+                                                int &bw, int &bh)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the columns [x0, x1] and the linear indices [k0, k1] the known cells span; the rows follow from k0 and k1
+    int x0 = 0x7fffffff, x1 = -1, k0 = 0x7fffffff, k1 = -1;
+    auto see = [&](int k, int x) { x0 = min(x0, x); x1 = max(x1, x); k0 = min(k0, k); k1 = max(k1, k); };
+    const int to_boundary = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(cells) & 15u)) & 15u) >> 1);
+    const int head = min(n, to_boundary), nvec = (n - head) >> 3, tail = head + 8 * nvec;
+    for (int k = tid; k < head; k += KGT_THREADS)
+        if (cells[k] != 0) see(k, k % nx);
+    for (int k = tail + tid; k < n; k += KGT_THREADS)
+        if (cells[k] != 0) see(k, k % nx);
+    const uint4 *__restrict__ vec = reinterpret_cast<const uint4 *>(cells + head);
+    for (int v0 = 0; v0 < nvec; v0 += KGT_THREADS * KGT_PF) {
+        uint4 q[KGT_PF];
+#pragma unroll
+        for (int u = 0; u < KGT_PF; ++u) {
+            const int v = v0 + u * KGT_THREADS + tid;
+            q[u] = v < nvec ? vec[v] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < KGT_PF; ++u) {
+            if ((q[u].x | q[u].y | q[u].z | q[u].w) == 0u) continue;                // eight unknown cells (or none at all)
+            const unsigned w32[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+            const int k = head + 8 * (v0 + u * KGT_THREADS + tid);
+            int x = k % nx;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                if (((w32[c >> 1] >> (16 * (c & 1))) & 0xffffu) != 0u) see(k + c, x);
+                if (++x == nx) x = 0;                                              // the vector runs on into the next row
+            }
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        x0 = min(x0, __shfl_xor(x0, off, 64)); x1 = max(x1, __shfl_xor(x1, off, 64));
+        k0 = min(k0, __shfl_xor(k0, off, 64)); k1 = max(k1, __shfl_xor(k1, off, 64));
+    }
+    if (lane == 0) { s_box[wave][0] = x0; s_box[wave][1] = x1; s_box[wave][2] = k0; s_box[wave][3] = k1; }
+    __syncthreads();
+    for (int w = 0; w < KGT_WAVES; ++w) {
+        x0 = min(x0, s_box[w][0]); x1 = max(x1, s_box[w][1]); k0 = min(k0, s_box[w][2]); k1 = max(k1, s_box[w][3]);
+    }
+    int y0 = 0, y1 = 0;
+    if (x1 < 0) { x0 = 0; x1 = 0; }                                                // nothing known: offset 0, CellLimits(1, 1) (grid_2d.cc:39-44)
+    else { y0 = k0 / nx; y1 = k1 / nx; }
+    bx0 = __builtin_amdgcn_readfirstlane(x0); by0 = __builtin_amdgcn_readfirstlane(y0);
+    bw = __builtin_amdgcn_readfirstlane(x1 - x0 + 1); bh = __builtin_amdgcn_readfirstlane(y1 - y0 + 1);
+}
+
+// The interior block of the image, a transposition with a column flip, through LDS tiles of OCC_T x OCC_T bytes so that both
+// global sides run along memory: a wave reads 64 consecutive cells of one grid row (128 B), looks each up in the byte table and
+// writes the bytes down one tile COLUMN; behind the barrier a lane takes 16 consecutive bytes of one tile ROW and stores them as one
+// aligned 16-byte vector, four lanes per 64-byte row segment.  Tile rows are OCC_PITCH = 72 bytes apart: the byte stores of a wave go
+// to dwords 18 apart, so the 64 lanes fall on 32 different dwords' banks, two lanes each (lanes l and l + 32 when the dword address
+// is taken mod 64, l and l + 16 when it is taken mod 32 as the guide gives it for stores): never more than a 2-way conflict, which a
+// store does not pay for -- and a row's 16 bytes are two aligned 8-byte loads.  The store phase has work for OCC_T * 4 = 256 threads:
+// in kgb_occupancy's workgroup of 512 four waves wait at the barrier meanwhile (a wider store side was not tried, no number).  Tiles are laid over the OUTPUT (u0, c0 multiples of 64), so every vector store is aligned whatever h is; columns
+// h .. stride - 1 of a row are padding and get 0.  The workgroup (any multiple of 64 threads) takes tiles first, first + step, ...
+#define OCC_T 64
+#define OCC_PITCH 72
+__device__ static inline void occupancy_tiles(const unsigned short *__restrict__ cells, int nx, int x0, int y0, int w, int h,
+                                              const unsigned char *__restrict__ table, unsigned char *__restrict__ out,
+                                              unsigned char (*tile)[OCC_PITCH], int first, int step)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+    const int stride = occupancy_stride(h);
+    const int tiles_u = (w + OCC_T - 1) / OCC_T, tiles_c = (stride + OCC_T - 1) / OCC_T;
+    for (int t = first; t < tiles_u * tiles_c; t += step) {
+        const int u0 = OCC_T * (t % tiles_u), c0 = OCC_T * (t / tiles_u);          // u fastest: neighbouring tiles read on along the grid's rows
+        const int u = u0 + lane;
+        for (int r = wave; r < OCC_T; r += waves) {
+            const int v = h - 1 - (c0 + r);                                        // the column flip
+            unsigned char byte = 0;
+            if (v >= 0 && u < w) byte = table[cells[(size_t)nx * (size_t)(y0 + v) + (size_t)(x0 + u)] & 32767u];
+            tile[lane][r] = byte;
+        }
+        __syncthreads();
+        for (int q = tid; q < OCC_T * (OCC_T / 16); q += blockDim.x) {
+            const int ul = q >> 2, c = c0 + 16 * (q & 3);
+            if (u0 + ul < w && c < stride) {
+                const uint2 *src = reinterpret_cast<const uint2 *>(&tile[ul][16 * (q & 3)]);
+                const uint2 a = src[0], b = src[1];
+                *reinterpret_cast<uint4 *>(out + (size_t)stride * (size_t)(u0 + ul) + (size_t)c) = make_uint4(a.x, a.y, b.x, b.y);
+            }
+        }
+        __syncthreads();
     }
 }
 

@@ -32,6 +32,12 @@ kgb_texture (one workgroup per named slot) and one wait turn resident slots into
 ``submap_textures(slots, submap_origins)`` gives the reference's ``SubmapTexture`` fields as ``MapBuilder.ToSubmapTexture`` does.
 The slots are only read and stay on the device.
 
+What a node publishes and saves is one step further, ``Node::PublishMap`` / ``Node::HandleSaveMap`` (src/ros_node.cc:845-863,947-1001):
+``occupancy_grids(slots, submap_origins, mode)`` is ONE launch of kgb_occupancy (one workgroup per named slot) and one wait -- per slot
+a ``FleetOccupancyGrid`` with the ``grid.OccupancyGrid`` that ``GridFrontEnd.OccupancyGrid`` returns for the same grid, byte for byte,
+plus a ``status``: the reference's cairo painting of the texture as nav_msgs::OccupancyGrid data (mode OCCUPANCY) or as the bytes of
+the saved PGM (mode IMAGE).
+
 All arithmetic happens in the HIP kernel behind librgrid.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -43,7 +49,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .grid import (AdaptiveVoxelFilterOptions, CeresScanMatcherOptions2D, MatchResult, RangeDataInserterOptions, RealTimeCorrelativeScanMatcherOptions, RefineResult,
+from .grid import (IMAGE, OCCUPANCY, AdaptiveVoxelFilterOptions, CeresScanMatcherOptions2D, MatchResult, OccupancyGrid, RangeDataInserterOptions, RealTimeCorrelativeScanMatcherOptions, RefineResult,
                    RgridError, _lib_rgrid, _MatchOptions, _RefineOptions, _RefineSummary)
 
 RGRID_OK, RGRID_ERR_INVALID, RGRID_ERR_CAPACITY, RGRID_ERR_EMPTY = 0, -1, -4, -6
@@ -105,6 +111,11 @@ class FleetTexture:
 
     def __iter__(self):
         return iter((self.cells, self.box, self.slice_max))
+
+
+@dataclass
+class FleetOccupancyGrid(OccupancyGrid):
+    status: int = 0                  # RGRID_OK, or -4: the slot lies outside the painting's domain (data is empty, origin zero then)
 
 
 @dataclass
@@ -204,6 +215,17 @@ def _declare_texture(L):
 
 
 _texture_lib = _lib.Feature(_batch_lib, "librgrid.so", ("rgrid_batch_texture_submit", "rgrid_batch_texture_collect"), (), _declare_texture)
+
+
+def _declare_occupancy(L):
+    """``_batch_lib()`` with the argtypes of the occupancy calls set.  Raises LibraryMissing when the built library has no such calls
+    (they are looked up by name); every other call keeps working then."""
+    vp = C.c_void_p
+    L.rgrid_batch_occupancy_submit.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    L.rgrid_batch_occupancy_collect.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_long]
+
+
+_occupancy_lib = _lib.Feature(_batch_lib, "librgrid.so", ("rgrid_batch_occupancy_submit", "rgrid_batch_occupancy_collect"), (), _declare_occupancy)
 
 
 def filter_max_points() -> int:
@@ -629,6 +651,68 @@ class ScanMatchFleet(_lib.Handle):
             out.append({"cells": tex.cells, "width": tex.box[2], "height": tex.box[3], "resolution": resolution,
                         "slice_pose": (tex.slice_max[0] - ox, tex.slice_max[1] - oy), "global_pose": (ox, oy)})
         return out
+
+    # -- Node::PublishMap / HandleSaveMap for a batch: the painted texture of every named slot ---------------------------
+    def submit_occupancy_code(self, slots, submap_origins, mode: int = OCCUPANCY) -> int:
+        """-> the code of rgrid_batch_occupancy_submit for the named slots (any order, a slot any number of times);
+        ``submap_origins[i]`` is the local_pose translation of the submap in ``slots[i]``."""
+        L = _occupancy_lib()
+        ids = np.ascontiguousarray([int(k) for k in slots], dtype=np.int32)
+        origins = np.ascontiguousarray([(float(o[0]), float(o[1])) for o in submap_origins], dtype=np.float64).reshape(-1, 2)
+        if origins.shape[0] != ids.size:
+            raise ValueError("one submap origin per named slot")
+        room, resolutions = 0, []                                                  # what collect's buffer must hold at most
+        for k in ids:
+            rc, lim = self.GetLimits_code(int(k)) if 0 <= k < self.num_grids else (RGRID_ERR_INVALID, None)
+            room += (lim[0] + 11) * (lim[1] + 11) if rc == 0 else 0
+            resolutions.append(lim[2] if rc == 0 else 0.0)
+        rc = self._submitted(L.rgrid_batch_occupancy_submit(self._h, int(mode), ids.ctypes.data if ids.size else None,
+                                                            origins.ctypes.data if ids.size else None, int(ids.size)), int(ids.size))
+        if rc == 0:
+            self._occupancy_room, self._occupancy_mode, self._occupancy_resolutions = room, int(mode), resolutions
+        return rc
+
+    def submit_occupancy(self, slots, submap_origins, mode: int = OCCUPANCY):
+        """ONE launch of kgb_occupancy, one workgroup per named slot; returns without waiting.  The slots are only read."""
+        self._chk(self.submit_occupancy_code(slots, submap_origins, mode), "rgrid_batch_occupancy_submit")
+
+    def collect_occupancy_code(self, cap: int | None = None):
+        """-> (rc, [FleetOccupancyGrid]) of the occupancy submit that has not been collected.  ``cap`` (default: what always
+        suffices, from the slots' limits) is the room offered for the bytes: when it is too small the answer is (RGRID_ERR_BUFFER,
+        [(status, size, origin, box, offset) per slot]) and the submit stays pending."""
+        L = _occupancy_lib()
+        count = self._pending or 0
+        n = max(count, 1)
+        room = int(getattr(self, "_occupancy_room", 0) if cap is None else cap)
+        mode = getattr(self, "_occupancy_mode", OCCUPANCY)
+        status, sizes, origins = np.zeros(n, np.int32), np.zeros((n, 2), np.int32), np.zeros((n, 2))
+        boxes, offs = np.zeros((n, 4), np.int32), np.zeros(n, dtype=C.c_long)
+        out = np.empty(max(room, 1), np.int8 if mode == OCCUPANCY else np.uint8)
+        rc = self._collected(L.rgrid_batch_occupancy_collect(self._h, status.ctypes.data, sizes.ctypes.data, origins.ctypes.data,
+                                                             boxes.ctypes.data, offs.ctypes.data, out.ctypes.data, room))
+        if rc == RGRID_ERR_BUFFER:
+            return rc, [(int(status[i]), tuple(int(v) for v in sizes[i]), (float(origins[i, 0]), float(origins[i, 1])),
+                         tuple(int(v) for v in boxes[i]), int(offs[i])) for i in range(count)]
+        if rc != 0:
+            return rc, []
+        results = []
+        for i in range(count):
+            sx, sy, at = int(sizes[i, 0]), int(sizes[i, 1]), int(offs[i])
+            # (a view: the images of a call share the one buffer the library filled, and nothing else holds it)
+            results.append(FleetOccupancyGrid(out[at:at + sx * sy].reshape(sy, sx), self._occupancy_resolutions[i],
+                                              (float(origins[i, 0]), float(origins[i, 1])), tuple(int(v) for v in boxes[i]), int(status[i])))
+        return 0, results
+
+    def collect_occupancy(self, cap: int | None = None):
+        """Waits for the launch: one FleetOccupancyGrid per named slot, in order."""
+        rc, out = self.collect_occupancy_code(cap)
+        self._chk(rc, "rgrid_batch_occupancy_collect")
+        return out
+
+    def occupancy_grids(self, slots, submap_origins, mode: int = OCCUPANCY):
+        """``GridFrontEnd.OccupancyGrid`` of every named slot in ONE launch: a list of FleetOccupancyGrid, in the order named."""
+        self.submit_occupancy(slots, submap_origins, mode)
+        return self.collect_occupancy()
 
     def GetLimits_code(self, slot: int):
         nx, ny = C.c_int(), C.c_int()

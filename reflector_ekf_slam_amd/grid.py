@@ -52,6 +52,18 @@ def _declare_rgrid(L):
 _lib_rgrid = _lib.Library("librgrid.so", ("rgrid_abi_version", RGRID_ABI_VERSION), _declare_rgrid)
 
 
+def _declare_occupancy(L):
+    """``_lib_rgrid()`` with the argtypes of rgrid_occupancy_grid set.  Raises LibraryMissing when the built library has no such call
+    (the ABI version does not tell: it is looked up by name); every other call keeps working then."""
+    vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
+    L.rgrid_occupancy_grid.argtypes = [vp, C.c_int, dp, vp, C.c_long, ip, dp, ip]
+
+
+_occupancy_lib = _lib.Feature(_lib_rgrid, "librgrid.so", ("rgrid_occupancy_grid",), (), _declare_occupancy)
+
+OCCUPANCY, IMAGE = 0, 1          # the modes of rgrid_occupancy_grid / rgrid_batch_occupancy_submit
+
+
 class _RefineOptions(C.Structure):
     _fields_ = [("occupied_space_weight", C.c_double), ("translation_weight", C.c_double), ("rotation_weight", C.c_double),
                 ("max_num_iterations", C.c_int), ("use_nonmonotonic_steps", C.c_int)]
@@ -112,6 +124,39 @@ class RangeDataInserterOptions:
     insert_free_space: bool = True
     hit_probability: float = 0.55
     miss_probability: float = 0.49
+
+
+@dataclass
+class OccupancyGrid:
+    """The painted submap texture as the reference's node hands it out.  Mode OCCUPANCY: ``data`` int8 (height, width) =
+    nav_msgs::OccupancyGrid::data of Node::CreateOccupancyGridMsg (src/ros_node.cc:897-945), row 0 the bottom image row, -1 unknown,
+    else 0 .. 100; mode IMAGE: ``data`` uint8 (height, width) = the bytes Node::WritePgm writes (:865-881), row 0 the top image row.
+    ``origin`` = info.origin.position (x, y) = the YAML origin of the saved map; ``box`` = the known-cells box (offset_x, offset_y,
+    width, height) the texture was cropped to."""
+    data: np.ndarray
+    resolution: float
+    origin: tuple
+    box: tuple
+
+    @property
+    def width(self):
+        return int(self.data.shape[1])
+
+    @property
+    def height(self):
+        return int(self.data.shape[0])
+
+
+def pgm_bytes(image: "OccupancyGrid") -> bytes:
+    """Node::WritePgm (src/ros_node.cc:865-881) of a mode-IMAGE OccupancyGrid; std::to_string of a double is "%f"."""
+    return ("P5\n# Cartographer map; " + "%f" % image.resolution + " m/pixel\n" + str(image.width) + " " + str(image.height) +
+            "\n255\n").encode() + np.ascontiguousarray(image.data, np.uint8).tobytes()
+
+
+def yaml_bytes(image: "OccupancyGrid", pgm_filename: str) -> bytes:
+    """Node::WriteYaml (src/ros_node.cc:883-895) for the saved map ``pgm_filename``."""
+    return ("image: " + pgm_filename + "\nresolution: " + "%f" % image.resolution + "\norigin: [" + "%f" % image.origin[0] + ", " +
+            "%f" % image.origin[1] + ", 0.0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n").encode()
 
 
 @dataclass
@@ -253,6 +298,20 @@ class GridFrontEnd(_lib.Handle):
         sm = (C.c_double * 2)()
         self._chk(self._L.rgrid_draw_texture(self._h, out.ctypes.data_as(C.c_void_p), out.size, box, sm), "DrawTexture")
         return out[: 2 * box[2] * box[3]].reshape(box[3], box[2], 2).copy(), tuple(box[:]), (sm[0], sm[1])
+
+    # Node::PublishMap / Node::HandleSaveMap up to the message fields / the image  (src/ros_node.cc:845-863,947-1001)
+    def OccupancyGrid(self, submap_origin, mode: int = OCCUPANCY) -> "OccupancyGrid":
+        """The resident grid's texture painted as the reference paints it (rgrid_occupancy_grid): the occupancy values in message
+        order (mode OCCUPANCY) or the red bytes in image order (mode IMAGE).  ``submap_origin`` = the translation of the submap's
+        local pose.  RgridError -4 outside the domain (include/rgrid.h)."""
+        L = _occupancy_lib()
+        ny, nx = self._grid_shape
+        out = np.empty((nx + 11) * (ny + 11), np.int8 if mode == OCCUPANCY else np.uint8)
+        so = (C.c_double * 2)(float(submap_origin[0]), float(submap_origin[1]))
+        size, origin, box = (C.c_int * 2)(), (C.c_double * 2)(), (C.c_int * 4)()
+        self._chk(L.rgrid_occupancy_grid(self._h, int(mode), so, out.ctypes.data_as(C.c_void_p), out.size, size, origin, box), "OccupancyGrid")
+        _, _, resolution, _, _ = self.GetLimits()
+        return OccupancyGrid(out[: size[0] * size[1]].reshape(size[1], size[0]).copy(), resolution, (origin[0], origin[1]), tuple(box[:]))
 
     def GetGrid(self) -> np.ndarray:
         out = np.zeros(self._grid_shape, np.uint16)

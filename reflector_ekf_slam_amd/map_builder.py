@@ -16,8 +16,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .grid import (AdaptiveVoxelFilterOptions, CeresScanMatcherOptions2D, GridFrontEnd, RangeDataInserterOptions,
-                   RealTimeCorrelativeScanMatcherOptions)
+from .grid import (IMAGE, OCCUPANCY, AdaptiveVoxelFilterOptions, CeresScanMatcherOptions2D, GridFrontEnd, RangeDataInserterOptions,
+                   RealTimeCorrelativeScanMatcherOptions, pgm_bytes, yaml_bytes)
 
 _f32 = np.float32
 
@@ -165,6 +165,27 @@ class MapBuilder:
         ox, oy = self._submap_origin
         return {"cells": cells, "width": box[2], "height": box[3], "resolution": resolution,
                 "slice_pose": (slice_max[0] - ox, slice_max[1] - oy), "global_pose": (ox, oy)}
+
+    # Node::PublishMap up to the message fields  (src/ros_node.cc:845-863 -> CreateOccupancyGridMsg, :897-945)
+    def OccupancyGrid(self, mode: int = OCCUPANCY):
+        """None without a submap; else the ``grid.OccupancyGrid`` the reference's node publishes: ``data`` int8 (height, width) in
+        message order, ``resolution``, ``origin`` = info.origin.position (x, y).  mode IMAGE gives the saved map's bytes instead."""
+        if not self._have_submap:
+            return None
+        return self._fe.OccupancyGrid(self._submap_origin, mode)
+
+    # Node::HandleSaveMap's grid map  (src/ros_node.cc:969-996 -> WritePgm, WriteYaml)
+    def SaveMap(self, filebase: str):
+        """Writes ``filebase``.pgm and ``filebase``.yaml with the reference's bytes; returns the two paths, None without a submap."""
+        image = self.OccupancyGrid(IMAGE)
+        if image is None:
+            return None
+        pgm, yaml = filebase + ".pgm", filebase + ".yaml"
+        with open(pgm, "wb") as f:
+            f.write(pgm_bytes(image))
+        with open(yaml, "wb") as f:
+            f.write(yaml_bytes(image, pgm))
+        return pgm, yaml
 
     # introspection used by the tests
     def grid(self):
