@@ -28,8 +28,12 @@
  * map per fleet, shared by its members (one hall): rfleet_set_map.  A member that uses it tries the map first (weighted distance
  * < 0.05), then its own state (< 0.6); a map-matched observation corrects the pose through rows without a landmark block.
  *
+ * What the node publishes of the filter after a scan (src/ros_node.cc:736-791 ReflectorToRosMarkers' covariance ellipses, :75-140
+ * SaveReflectorResult's positions and 2 x 2 blocks) is served for any list of members by ONE launch and without a copy of any
+ * covariance matrix: rfleet_get_reflectors.
+ *
  * Deliberately OUT OF SCOPE (use a rekf handle): a map per member, a map of more than RFLEET_MAX_MAP_POINTS points, scans
- * wider than RFLEET_MAX_OBS, auto-grow, PredictState's landmark part (the full state), marker ellipses.
+ * wider than RFLEET_MAX_OBS, auto-grow, PredictState's landmark part (the full state).
  *
  * The covariance of a member lives on the device as its lower triangle; the getters mirror it (as rekf_get_state does).
  */
@@ -97,6 +101,19 @@ int rfleet_get_last_match(rfleet_t *f, int member, int *n_state, int *state_pair
  * leaves the old map in place.  (Added without a new RFLEET_ABI_VERSION: a binding looks the two calls up by name.) */
 int rfleet_set_map(rfleet_t *f, const float *xy, const double *cov, int M, const unsigned char *use /*[B], nullable*/);
 int rfleet_get_map_size(rfleet_t *f, int *M);
+/* The reflectors of the listed members, compact and in the order listed: counts[g] rows of members[g] follow those of members[g - 1].
+ * members NULL = all B members in order (count must be B).  Each output may be NULL: ellipses5 = the marker ellipse {mx, my, angle,
+ * x_len, y_len} of rekf_get_marker_ellipses (the same bits), xy2 = the reflector's mean, cov4 = its covariance block row-major
+ * (a, b, c, d) with b = c, as rfleet_get_state mirrors it.  cap_rows = the rows each given output holds (with no output given
+ * it is not looked at: the call returns the counts).
+ * Enqueues ONE launch behind whatever rfleet_submit has enqueued and synchronises once: every event submitted before is in it.
+ * counts is written on success AND with REKF_ERR_BUFFER (the rows do not fit cap_rows: no output is touched, counts sizes the
+ * second call).  REKF_ERR_INVALID before any HIP call and before the handle is read: a null handle, count < 0, count > 0 with null
+ * counts, cap_rows < 0, an output given with cap_rows == 0 and count > 0; after the handle is read and before any launch: a member
+ * outside 0 .. B-1, a member listed twice, members NULL with count != B.  count == 0 with a list is REKF_OK and does nothing.
+ * (Added without a new RFLEET_ABI_VERSION: a binding looks the call up by name.) */
+int rfleet_get_reflectors(rfleet_t *f, const int *members, int count,   /* members NULL = all B, in order */
+                          int *counts /*[count]*/, double *ellipses5, double *xy2, double *cov4, long cap_rows);
 /* Wait for all enqueued work.  REKF_ERR_HIP when the device reported an error. */
 int rfleet_sync(rfleet_t *f);
 int rfleet_size(rfleet_t *f, int *B, int *max_landmarks);

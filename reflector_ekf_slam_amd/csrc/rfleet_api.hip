@@ -10,7 +10,11 @@
 // The map (rfleet_set_map) is one device buffer per fleet and a byte per member.  A submit takes k_fleet_step_map only when a member
 // with events in it uses a non-empty map.  The other two kernels never touch FleetMemberCtl::n_map / map_pairs, so the host
 // remembers per member whether its last scan's record was written by the map kernel (map_rec).
+//
+// rfleet_get_reflectors is one launch of k_fleet_reflectors (fleet_reflectors.hip) behind whatever has been submitted, into a pinned
+// buffer sized at rfleet_create for B x max_landmarks rows, one synchronisation, and a host copy of the rows into the caller's arrays.
 #include "fleet_dev.h"
+#include "fleet_reflectors.h"
 #include "../../include/rfleet.h"
 
 #include <cmath>
@@ -46,6 +50,8 @@ struct rfleet {
     unsigned char *map_use_dev = nullptr;
     int M_map = 0;
     std::vector<unsigned char> map_use, map_rec;
+    // rfleet_get_reflectors: ONE pinned allocation, ell5 [R][5] | xy2 [R][2] | cov4 [R][4] | counts [B] | members [B], R = B max_landmarks
+    char *refl_host = nullptr, *refl_dev = nullptr;
     std::vector<int> scanned;               // scratch of rfleet_submit: members with a scan event in the call
     // scratch of rfleet_submit (kept to avoid per-call allocation)
     std::vector<int> cnt, pos, order;
@@ -63,6 +69,14 @@ struct rfleet {
     } while (0)
 
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// the pinned buffer of rfleet_get_reflectors: byte offsets of its parts
+static size_t refl_rows(const rfleet *f) { return (size_t)f->B * (size_t)f->max_landmarks; }
+static size_t refl_off_xy(const rfleet *f) { return sizeof(double) * 5 * refl_rows(f); }
+static size_t refl_off_cov(const rfleet *f) { return sizeof(double) * 7 * refl_rows(f); }
+static size_t refl_off_counts(const rfleet *f) { return sizeof(double) * 11 * refl_rows(f); }
+static size_t refl_off_members(const rfleet *f) { return refl_off_counts(f) + sizeof(int) * (size_t)f->B; }
+static size_t refl_bytes(const rfleet *f) { return refl_off_members(f) + sizeof(int) * (size_t)f->B; }
 
 extern "C" {
 
@@ -88,6 +102,7 @@ void rfleet_destroy(rfleet_t *f)
     if (f->dev.ctl) (void)hipFree(f->dev.ctl);
     if (f->dev.opt) (void)hipFree((void *)f->dev.opt);
     if (f->pose_host) (void)hipHostFree(f->pose_host);
+    if (f->refl_host) (void)hipHostFree(f->refl_host);
     if (f->map_xy) (void)hipFree(f->map_xy);
     if (f->map_cov) (void)hipFree(f->map_cov);
     if (f->map_use_dev) (void)hipFree(f->map_use_dev);
@@ -109,6 +124,8 @@ static int fleet_create_body(rfleet_t *f, const rekf_options *opts)
     FLEET_HIP(f, hipMalloc((void **)&f->dev.opt, sizeof(FleetMemberOpt) * B));
     FLEET_HIP(f, hipHostMalloc((void **)&f->pose_host, sizeof(FleetPoseSlot) * B, hipHostMallocDefault));
     FLEET_HIP(f, hipHostGetDevicePointer((void **)&f->dev.pose, f->pose_host, 0));
+    FLEET_HIP(f, hipHostMalloc((void **)&f->refl_host, refl_bytes(f), hipHostMallocDefault));
+    FLEET_HIP(f, hipHostGetDevicePointer((void **)&f->refl_dev, f->refl_host, 0));
     FLEET_HIP(f, hipMemset(f->dev.mu, 0, sizeof(double) * ld * B));
     FLEET_HIP(f, hipMemset(f->dev.P, 0, sizeof(double) * ld * ld * B));
     FLEET_HIP(f, hipMemset(f->dev.W, 0, sizeof(double) * ld * RFLEET_PANEL_COLS * B));
@@ -495,6 +512,49 @@ int rfleet_get_map_size(rfleet_t *f, int *M)
 {
     if (!f || !M) return REKF_ERR_INVALID;
     *M = f->M_map;
+    return REKF_OK;
+}
+
+int rfleet_get_reflectors(rfleet_t *f, const int *members, int count, int *counts, double *ellipses5, double *xy2, double *cov4, long cap_rows)
+{
+    if (!f || count < 0 || (count > 0 && !counts) || cap_rows < 0) return REKF_ERR_INVALID;
+    if (count > 0 && cap_rows == 0 && (ellipses5 || xy2 || cov4)) return REKF_ERR_INVALID;   // (every member can hold a reflector)
+    const int B = f->B;
+    if (!members && count != B) return REKF_ERR_INVALID;
+    if (members) {
+        if (count > B) return REKF_ERR_INVALID;                            // (more than B members: one is listed twice)
+        std::fill(f->cnt.begin(), f->cnt.end(), 0);
+        for (int g = 0; g < count; ++g) {
+            if (members[g] < 0 || members[g] >= B || f->cnt[members[g]]++) return REKF_ERR_INVALID;
+        }
+    }
+    if (count == 0) return REKF_OK;
+    FLEET_HIP(f, hipSetDevice(f->device));
+    const size_t R = refl_rows(f);
+    const int *h_counts = (const int *)(f->refl_host + refl_off_counts(f));
+    FleetReflectorsLaunch L{};
+    if (members) {                                                         // (no launch reads the list any more: every call ends in a synchronisation)
+        memcpy(f->refl_host + refl_off_members(f), members, sizeof(int) * (size_t)count);
+        L.members = (const int *)(f->refl_dev + refl_off_members(f));
+    }
+    L.count = count;
+    L.cap_rows = cap_rows < (long)R ? cap_rows : (long)R;
+    L.counts = (int *)(f->refl_dev + refl_off_counts(f));
+    L.ell5 = ellipses5 ? (double *)f->refl_dev : nullptr;
+    L.xy2 = xy2 ? (double *)(f->refl_dev + refl_off_xy(f)) : nullptr;
+    L.cov4 = cov4 ? (double *)(f->refl_dev + refl_off_cov(f)) : nullptr;
+    FLEET_HIP(f, rfleet_launch_reflectors(f->dev, L, f->stream));
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    long rows = 0;
+    for (int g = 0; g < count; ++g) {
+        counts[g] = h_counts[g];
+        rows += h_counts[g];
+    }
+    if (rows > cap_rows && (ellipses5 || xy2 || cov4)) return REKF_ERR_BUFFER;    // (no output given: the call that asks for the counts)
+    if (ellipses5) memcpy(ellipses5, f->refl_host, sizeof(double) * 5 * (size_t)rows);
+    if (xy2) memcpy(xy2, f->refl_host + refl_off_xy(f), sizeof(double) * 2 * (size_t)rows);
+    if (cov4) memcpy(cov4, f->refl_host + refl_off_cov(f), sizeof(double) * 4 * (size_t)rows);
     return REKF_OK;
 }
 

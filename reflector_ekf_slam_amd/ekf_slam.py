@@ -112,30 +112,39 @@ def save_map_txt(path: str, state: State, loaded: Map | None = None, reference_b
     bytes the reference's ``std::ofstream <<`` would: 6 significant digits (iostream default = %g), map points
     formatted from their float32 values, and the "," the reference emits in front of the new landmarks even when
     no map was pre-loaded (:97-100,:124-127) -- which its own loader then chokes on; ours skips empty fields."""
-    pts, covs = [], []
-    n_loaded = 0
-    if loaded is not None:
-        for p, c in zip(loaded.reflector_map_, loaded.reflector_map_coviarance_):
-            pts.append((float(np.float32(p[0])), float(np.float32(p[1]))))
-            covs.append(np.asarray(c, dtype=np.float64).reshape(4))
-            n_loaded += 1
+    pts, covs = loaded_map_rows(loaded)
+    n_loaded = len(pts)
     L = (state.mu.shape[0] - 3) // 2
     for j in range(L):
         pts.append((state.mu[3 + 2 * j], state.mu[4 + 2 * j]))
         covs.append(state.sigma[3 + 2 * j: 5 + 2 * j, 3 + 2 * j: 5 + 2 * j].reshape(4))
+    with open(path, "wb") as f:
+        f.write(reflector_map_txt(pts, covs, n_loaded, reference_bytes))
+
+
+def loaded_map_rows(loaded: Map | None):
+    """-> (points, covs) of a pre-loaded map as the saved map lists them: the points from their float32 values, the weights flat."""
+    pts, covs = [], []
+    if loaded is not None:
+        for p, c in zip(loaded.reflector_map_, loaded.reflector_map_coviarance_):
+            pts.append((float(np.float32(p[0])), float(np.float32(p[1]))))
+            covs.append(np.asarray(c, dtype=np.float64).reshape(4))
+    return pts, covs
+
+
+def reflector_map_txt(points, covs, n_loaded: int, reference_bytes: bool = False) -> bytes:
+    """The saved map's two lines (``save_map_txt``) as bytes: ``points`` (x, y) and ``covs`` (four values, row-major 2 x 2) per
+    reflector, the first ``n_loaded`` of them the pre-loaded map's, the rest the filter's own."""
     if not reference_bytes:
-        with open(path, "w") as f:
-            f.write(",".join(f"{v:.17g}" for p in pts for v in p) + "\n")
-            f.write(",".join(f"{v:.17g}" for c in covs for v in c) + "\n")
-        return
+        return (",".join(f"{v:.17g}" for p in points for v in p) + "\n"
+                + ",".join(f"{v:.17g}" for c in covs for v in c) + "\n").encode()
+    own = len(points) - n_loaded
 
     def line(groups):
         old = ",".join("%g" % v for g in groups[:n_loaded] for v in g)
         new = ",".join("%g" % v for g in groups[n_loaded:] for v in g)
-        return old + (("," + new) if L > 0 else "")
-    with open(path, "w") as f:
-        f.write(line(pts) + "\n")
-        f.write(line(covs) + "\n")
+        return old + (("," + new) if own > 0 else "")
+    return (line(points) + "\n" + line(covs) + "\n").encode()
 
 
 class ReflectorEKFSLAM:

@@ -7,6 +7,10 @@ deployment: ``predict_poses(times)`` -> scan matcher -> ``scan_event(..., pose_f
 fleet ONE pre-loaded reflector map that its members localise against (the reference's LoadMapFromTxtFile deployment).  ``member(i)`` is a view with the snake_case filter interface of
 ``ReflectorEKFSLAM`` (each call a one-event submit), for code that drives one robot at a time.
 
+What the node publishes after a scan comes from ONE more launch (k_fleet_reflectors), without a copy of any covariance matrix:
+``marker_ellipses()`` (ReflectorToRosMarkers' covariance ellipses), ``landmarks()`` and ``save_map_txt`` (SaveReflectorResult).
+The node's tick: detect -> predict_poses -> match -> fleet.submit -> marker_ellipses.
+
 All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -16,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .ekf_slam import ReflectorMatchResult, RekfError, State
+from .ekf_slam import Map, ReflectorMatchResult, RekfError, State, loaded_map_rows, reflector_map_txt
 
 RFLEET_ABI_VERSION = 2        # must equal RFLEET_ABI_VERSION of include/rfleet.h and rfleet_abi_version() of the built library
 MAX_LANDMARKS = 128
@@ -64,6 +68,15 @@ def _declare_map(L):
 _map_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_set_map", "rfleet_get_map_size"), (), _declare_map)
 
 
+def _declare_reflectors(L):
+    """``rfleet()`` with the argtypes of rfleet_get_reflectors set.  It was added without a new ABI version and is looked up by name:
+    raises LibraryMissing when the built library has none; every other call keeps working then."""
+    L.rfleet_get_reflectors.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+
+
+_reflectors_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_get_reflectors",), (), _declare_reflectors)
+
+
 def odom_event(member, t, vx, vy, wz):
     return (int(member), EV_ODOM, float(t), (float(vx), float(vy), float(wz)), None)
 
@@ -78,6 +91,7 @@ def scan_event(member, t, cloud, pose_fix=None):
 class ReflectorEKFSLAMFleet(_lib.Handle):
     """B independent ekf::ReflectorEKFSLAM filters on one MI355X, one kernel launch per ``submit``."""
     _destroy = "rfleet_destroy"
+    _map = None                   # (Map, per-member switch or None) of the last successful set_map
 
     def __init__(self, options_list, max_landmarks: int = MAX_LANDMARKS, device: int = 0):
         self._L = rfleet()
@@ -233,8 +247,11 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
             use = np.zeros(self.B, np.uint8)
             use[np.asarray(list(members), np.int64)] = 1
         M = xy.shape[0]
-        return _map_lib().rfleet_set_map(self._h, xy.ctypes.data if M else None, cov.ctypes.data if M else None, M,
-                                         None if use is None else use.ctypes.data)
+        rc = _map_lib().rfleet_set_map(self._h, xy.ctypes.data if M else None, cov.ctypes.data if M else None, M,
+                                       None if use is None else use.ctypes.data)
+        if rc == 0:                                          # (kept for save_map_txt: the saved map lists the pre-loaded points first)
+            self._map = (Map(xy.copy(), cov.reshape(-1, 2, 2).copy()), use) if M else None
+        return rc
 
     def set_map(self, xy, cov, members=None):
         """The fleet's pre-loaded reflector map (sensor::Map as LoadMapFromTxtFile leaves it): xy [M, 2] float32, cov [M, 2, 2]
@@ -248,6 +265,70 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
         M = C.c_int()
         self._chk(_map_lib().rfleet_get_map_size(self._h, C.byref(M)), "rfleet_get_map_size")
         return M.value
+
+    def loaded_map(self, i: int) -> Map | None:
+        """The pre-loaded map member i matches against (``set_map``), or None."""
+        if self._map is None or (self._map[1] is not None and not self._map[1][int(i)]):
+            return None
+        return self._map[0]
+
+    # -- what the node publishes: the reflectors of any list of members in one launch ----------------
+    def reflectors(self, members=None, ellipses=True, xy=False, cov=False):
+        """-> (counts [len(members)], ellipses [R, 5] or None, xy [R, 2] or None, cov [R, 2, 2] or None): the rows of the listed
+        members (None = all, in order) one after the other, R = counts.sum().  ONE launch behind everything submitted and one
+        synchronisation, whatever the number of members; no copy of any state."""
+        L = _reflectors_lib()
+        if members is None:
+            mem, count = None, self.B
+        else:
+            mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+            count = mem.shape[0]
+        cap = count * self.max_landmarks
+        counts = np.zeros(max(count, 1), np.int32)
+        e = np.empty((cap, 5)) if ellipses else None
+        p = np.empty((cap, 2)) if xy else None
+        c = np.empty((cap, 2, 2)) if cov else None
+        rc = L.rfleet_get_reflectors(self._h, None if mem is None else mem.ctypes.data, count, counts.ctypes.data,
+                                     None if e is None else e.ctypes.data, None if p is None else p.ctypes.data,
+                                     None if c is None else c.ctypes.data, cap)
+        if rc != 0:
+            self._chk(rc, "rfleet_get_reflectors")
+        counts = counts[:count]
+        R = int(counts.sum())
+        return counts, None if e is None else e[:R], None if p is None else p[:R], None if c is None else c[:R]
+
+    @staticmethod
+    def _per_member(counts, rows):
+        out, at = [], 0
+        for k in counts.tolist():
+            out.append(rows[at: at + k])
+            at += k
+        return out
+
+    def marker_ellipses(self, members=None):
+        """ReflectorToRosMarkers' covariance ellipses (src/ros_node.cc:736-791) of the listed members (None = all): a list of
+        [L_b, 5] arrays {mx, my, angle, x_len, y_len}, the bits ``ReflectorEKFSLAM.marker_ellipses`` gives for the same state."""
+        counts, e, _, _ = self.reflectors(members, ellipses=True)
+        return self._per_member(counts, e)
+
+    def landmarks(self, members=None):
+        """-> a list of (xy [L_b, 2], cov [L_b, 2, 2]) of the listed members (None = all): each reflector's mean and its
+        covariance block as ``get_state`` mirrors it."""
+        counts, _, p, c = self.reflectors(members, ellipses=False, xy=True, cov=True)
+        return list(zip(self._per_member(counts, p), self._per_member(counts, c)))
+
+    def save_map_txt(self, member: int, path: str, reference_bytes: bool = False):
+        """SaveReflectorResult (src/ros_node.cc:75-140) for one member, the bytes of ``ekf_slam.save_map_txt`` on its state: the
+        shared pre-loaded map's points first when the member uses one, then the member's reflectors."""
+        if not 0 <= int(member) < self.B:
+            raise IndexError(member)
+        (xy, cov), = self.landmarks([int(member)])
+        pts, covs = loaded_map_rows(self.loaded_map(member))
+        n_loaded = len(pts)
+        pts.extend(xy)
+        covs.extend(cov.reshape(-1, 4))
+        with open(path, "wb") as f:
+            f.write(reflector_map_txt(pts, covs, n_loaded, reference_bytes))
 
 
 class FleetMember:
@@ -285,6 +366,9 @@ class FleetMember:
 
     def last_match(self) -> ReflectorMatchResult:
         return self.fleet.last_match(self.index)
+
+    def marker_ellipses(self) -> np.ndarray:
+        return self.fleet.marker_ellipses([self.index])[0]
 
     def pose(self):
         t, mu, sg = self.fleet.poses()
