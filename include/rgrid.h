@@ -398,6 +398,57 @@ int rgrid_batch_occupancy_submit(rgrid_batch_t *b, int mode, const int *grids, c
 int rgrid_batch_occupancy_collect(rgrid_batch_t *b, int *status, int *sizes, double *origins, int *boxes,
                                   long *offsets, int8_t *out, long cap);
 
+/* ---- fleet MapBuilder: mapping::MapBuilder::AddRangeData (src/mapping/map_builder.cc:57-108) for one scan of every robot in ONE
+ * call, each robot in its own resident slot.  The specification is the single handle: robot j's status, local_pose, returns_in_local
+ * and, after the call, its slot's cells and limits (rgrid_batch_get_grid / rgrid_batch_get_limits) are the bits an rgrid_t created
+ * with the batch's max_points and max_cells (and max_candidates large enough) gives and holds after the same scans through
+ * rgrid_add_range_data with the same options.  Nothing has a tolerance.
+ * Stages: (1) kgb_filter rotates the raw returns and misses into the gravity-aligned frame ON THE DEVICE as it loads them -- per point
+ * (c x - s y) + 0, (s x + c y) + 0 with the host's float (cos, sin) of the scan -- and filters them; (2) the host decides from the
+ * counts; (3) kgb_match and kgb_refine, for the scans whose slot has a grid, on the adaptively filtered clouds where the filter wrote
+ * them; (4) the host composes the poses (double cos / sin / atan2 of the host's libm: the device has no bit-identical ones, which is
+ * why the call waits between its stages) and moves the filtered clouds into the insert's segment; (5) kgb_insert and kgb_to_local --
+ * the RAW returns, still on the device from (1), through Rigid2f(pose_estimate.cast<float>()) into pinned host memory.  At most 5
+ * kernel launches (6 with RGRID_BATCH_REDUCE_LAUNCH) and 3 stream synchronisations per call whatever count is;
+ * rgrid_batch_last_call_counts reports both for the last call.  Not counted: a slot's creation is one hipMemsetAsync of 100 x 100 cells
+ * on the handle's stream, and the handle's first call allocates its staging and uploads the insert's two lookup tables as the first
+ * filter and insert submits do.
+ * A slot that was never set is created as MapBuilder::CreateGrid creates it (:112-126: 100 x 100 unknown cells around the scan's origin
+ * in local, resolution = opt->resolution, read only then -- an existing slot keeps its own), before growth: a scan whose growth fails
+ * leaves the slot created.  Its scan is not matched, its estimate is the prediction.
+ * Per scan: codes[j] = RGRID_OK or the first error of the scan's own stages, the other scans unaffected -- RGRID_ERR_CAPACITY (a cloud
+ * above min(max_points, rgrid_batch_filter_max_points()); the match's or the insert's own capacity rules; creation with max_cells <
+ * 10000), RGRID_ERR_INVALID (a non-finite raw coordinate: the single handle is not the reference for such a scan; creation with a
+ * resolution not > 0).  status[j] = RGRID_SCAN_INSERTED, RGRID_SCAN_DROPPED_EMPTY or RGRID_SCAN_FILTERED_EMPTY with
+ * rgrid_add_range_data's meaning; with a code it is never RGRID_SCAN_INSERTED.  local_poses (3 * count) = what rgrid_add_range_data
+ * returns in local_pose, zero for a scan that did not get that far.  origins_in_local (2 * count) = the origin of range_data_in_local2
+ * (the gravity-aligned origin through Embed3D(pose_estimate_2d.cast<float>())): for a scan that creates its slot, the submap's origin,
+ * which rgrid_batch_occupancy_submit wants later.  returns_in_local (nullable, cap_points rows of room): scan j's n_returns rows at the
+ * prefix sum of the n_returns before it; rows of scans that were not inserted are left untouched.
+ * The whole call is RGRID_ERR_BUFFER, before anything is launched, when returns_in_local is given and cap_points is below the sum of
+ * n_returns.  It is RGRID_ERR_INVALID, nothing launched and the handle still usable, for: a null b, opt, scans, codes, status,
+ * local_poses or origins_in_local; count outside [0, max_scans]; a slot out of range; a negative point count or a null pointer with a
+ * positive one; two scans naming one slot (rgrid_batch_insert_submit's rule); voxel_filter_size or adaptive_max_length not > 0, the
+ * refinement options rgrid_refine_match refuses, a probability not strictly inside (0, 1); a pending submit of any kind.  The call is
+ * synchronous: nothing is pending when it returns.  Coordinates whose voxel index no int holds are outside the contract.
+ * The ABI version stays 4: a caller that may meet an older library looks for these symbols. */
+typedef struct rgrid_batch_range_data {   /* 64 bytes on LP64 */
+    int grid;                              /* the robot's resident slot; may be a slot that was never set */
+    int n_returns, n_misses;
+    const float *returns_xy, *misses_xy;   /* tracking frame, NULL when n == 0 */
+    float origin_xy[2];
+    double ekf_pose[3];                    /* x, y, yaw as the node builds it */
+} rgrid_batch_range_data;
+
+int rgrid_batch_add_range_data(rgrid_batch_t *b, const rgrid_map_builder_options *opt, const rgrid_batch_range_data *scans, int count,
+                               int *codes, int *status, double *local_poses, float *origins_in_local, float *returns_in_local,
+                               long cap_points);
+int rgrid_batch_sizeof_range_data(void);
+
+/* (kernel launches, stream synchronisations) of the handle's last rgrid_batch_add_range_data that was not refused as a whole;
+ * (0, 0) before the first and after a call without scans. */
+int rgrid_batch_last_call_counts(rgrid_batch_t *b, int launches_syncs[2]);
+
 int rgrid_batch_sizeof_scan(void);
 int rgrid_batch_sizeof_refine_scan(void);
 int rgrid_batch_sizeof_insert_scan(void);

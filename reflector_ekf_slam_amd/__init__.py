@@ -10,5 +10,6 @@ from .ekf_slam import (DIFF, OMNI, EKFOptions, Map, Observation, OdometryData,  
 from .fleet import ReflectorEKFSLAMFleet  # noqa: F401
 from .fleet_detect import LaserReflectorDetectFleet, PointCloud, PointCloudReflectorDetectFleet, cloud_events, scan_events  # noqa: F401
 from .grid import OccupancyGrid  # noqa: F401
-from .fleet_match import (FleetFilterResult, FleetOccupancyGrid, FleetRefineResult, FleetScanMatchResult, FleetTexture, RgridBatchFilterScan,  # noqa: F401
-                          RgridBatchInsertScan, ScanMatchFleet, gravity_aligned_scans, pose_fixes)
+from .fleet_match import (FleetFilterResult, FleetOccupancyGrid, FleetRangeDataResult, FleetRefineResult, FleetScanMatchResult, FleetTexture,  # noqa: F401
+                          RgridBatchFilterScan, RgridBatchInsertScan, RgridBatchRangeData, ScanMatchFleet, gravity_aligned_scans, pose_fixes)
+from .map_builder import FleetMapBuilder  # noqa: F401

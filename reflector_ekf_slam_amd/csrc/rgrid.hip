@@ -999,33 +999,8 @@ int rgrid_match(rgrid_t *h, const rgrid_match_options *opt, const double initial
 // ---- mapping::MapBuilder::AddRangeData (src/mapping/map_builder.cc:57-108) as one call ------------------------------
 // Host side = what the reference's host does between the steps: a few rigid transforms (its float32 round trips
 // through Eigen quaternions restated operation by operation, as in reflector_ekf_slam_amd/map_builder.py) and the
-// decisions; every per-point / per-cell step is one of the entry points above.
-namespace {
-float yaw_of_quaternion_f32(float w, float z)          // transform::GetYaw(Quaternionf(w,0,0,z)): q * UnitX = (1 - z 2z, w 2z, 0)
-{
-#pragma clang fp contract(off)
-    const float two_z = z + z;
-    const float y = w * two_z, x = 1.f - z * two_z;
-    return (float)std::atan2((double)y, (double)x);
-}
-double yaw_of_quaternion_f64(double w, double z)
-{
-#pragma clang fp contract(off)
-    const double two_z = z + z;
-    return std::atan2(w * two_z, 1.0 - z * two_z);
-}
-void rigid2f_apply(float tx, float ty, float yaw, const float *in, int n, float *out)   // Rigid2f(t, Rotation2Df(yaw)) * p
-{
-#pragma clang fp contract(off)
-    const float c = (float)std::cos((double)yaw), s = (float)std::sin((double)yaw);
-    for (int i = 0; i < n; ++i) {
-        const float x = in[2 * i], y = in[2 * i + 1];
-        out[2 * i] = (c * x - s * y) + tx;
-        out[2 * i + 1] = (s * x + c * y) + ty;
-    }
-}
-}  // namespace
-
+// decisions; every per-point / per-cell step is one of the entry points above.  The transforms themselves (yaw_of_quaternion_f32 /
+// _f64, rigid2f_apply) are rgrid_dev.h's: rgrid_batch_add_range_data composes its poses with the same text.
 int rgrid_add_range_data(rgrid_t *h, const rgrid_map_builder_options *opt, const float origin_xy[2], const float *returns_xy,
                          int n_returns, const float *misses_xy, int n_misses, const double ekf_pose[3], double local_pose[3],
                          float *returns_in_local, int *status)

@@ -21,6 +21,12 @@
 // scan runs kg_refine's solve (the device text of rgrid_refine_dev.h), alone (rgrid_batch_refine_*) or right behind the match on the
 // same stream, starting from the winner the match published (rgrid_batch_scan_match_*).
 //
+// MapBuilder::AddRangeData itself for a batch is rgrid_batch_add_range_data at the end of this file: the stages above -- the filter
+// (kgb_filter<true>, which rotates the raw clouds into the gravity-aligned frame as it loads them), match and refinement, the
+// insert -- in ONE synchronous call, with the host composing the poses between them as rgrid_add_range_data does, and kgb_to_local
+// for the raw returns in the local frame.  It packs, stages and launches through the functions the single-kind
+// submits call; there is one text of each.
+//
 // Per-call data -- a record per scan, the workgroup -> (record, rotation) map, the rotation tables and the rotated points --
 // is packed into one of two staging segments that the kernel reads in place: fine-grained device memory the host writes
 // directly where the platform maps it, else pinned host memory (host_visible.h).  Results land in pinned host memory, a slot
@@ -598,19 +604,30 @@ __device__ __forceinline__ int kgf_emit(const float (&px)[KGF_PER], const float 
     return base;
 }
 
-__device__ __forceinline__ unsigned kgf_load(const float2 *__restrict__ src, int n, float (&px)[KGF_PER], float (&py)[KGF_PER])
+// ROT: the point goes through Rigid2f(0, Rotation2Df(yaw)) on its way into the registers, rgrid_add_range_data's gravity alignment
+// (map_builder.cc:20-28) with the host's (cos, sin) -- the translation of 0 is added as the host adds it (it turns a -0 sum into +0)
+template <bool ROT>
+__device__ __forceinline__ unsigned kgf_load(const float2 *__restrict__ src, int n, float (&px)[KGF_PER], float (&py)[KGF_PER], float c, float s)
 {
     unsigned in = 0;
 #pragma unroll
     for (int u = 0; u < KGF_PER; ++u) {
         const int i = u * KGF_THREADS + (int)threadIdx.x;
         px[u] = 0.f; py[u] = 0.f;
-        if (i < n) { const float2 p = src[i]; px[u] = p.x; py[u] = p.y; in |= 1u << u; }
+        if (i < n) {
+            const float2 p = src[i];
+            if (ROT) rigid2f_point(c, s, 0.f, 0.f, p.x, p.y, px[u], py[u]);
+            else { px[u] = p.x; py[u] = p.y; }
+            in |= 1u << u;
+        }
     }
     return in;
 }
 
-__global__ __launch_bounds__(KGF_THREADS) void kgb_filter(FilterBufs B)
+// ROT = false: rgrid_batch_filter_submit's kernel, the clouds as they come (`rot` is not read).  ROT = true: the first stage of
+// rgrid_batch_add_range_data, raw tracking-frame clouds and one (cos, sin) per record in `rot`.
+template <bool ROT>
+__global__ __launch_bounds__(KGF_THREADS) void kgb_filter(FilterBufs B, const float2 *__restrict__ rot)
 {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char kgf_lds[];
@@ -624,9 +641,11 @@ __global__ __launch_bounds__(KGF_THREADS) void kgb_filter(FilterBufs B)
     if (threadIdx.x == 0) { s_cnt[0] = 0; s_cnt[1] = 0; s_cnt[2] = 0; }            // (the first pass's first barrier publishes them)
     int turn = 0;
     float px[KGF_PER], py[KGF_PER];
+    float rc = 1.f, rs = 0.f;
+    if (ROT) { const float2 cs = rot[blockIdx.x]; rc = cs.x; rs = cs.y; }
     // ---- VoxelFilter(voxel_filter_size).Filter(returns) (map_builder.cc:30)
     const int nr = R.n_ret;
-    unsigned in = kgf_load(pin + R.ret_off, nr, px, py);
+    unsigned in = kgf_load<ROT>(pin + R.ret_off, nr, px, py, rc, rs);
     int m;
     const unsigned fr = kgf_pass(px, py, in, B.vsize, nr, key, tab, s_cnt, turn, m);
     const int n_fr = kgf_emit(px, py, fr, nr, out, s_w);
@@ -660,10 +679,44 @@ __global__ __launch_bounds__(KGF_THREADS) void kgb_filter(FilterBufs B)
     const int n_av = kgf_emit(px, py, av, nr, out + nr + R.n_mis, s_w);
     // ---- VoxelFilter(voxel_filter_size).Filter(misses) (map_builder.cc:31): a fresh filter, a fresh table
     const int nm = R.n_mis;
-    in = kgf_load(pin + R.mis_off, nm, px, py);
+    in = kgf_load<ROT>(pin + R.mis_off, nm, px, py, rc, rs);
     const unsigned fm = kgf_pass(px, py, in, B.vsize, nm, key, tab, s_cnt, turn, m);
     const int n_fm = kgf_emit(px, py, fm, nm, out + nr, s_w);
     if (threadIdx.x == 0) { int *c = B.counts + 3 * blockIdx.x; c[0] = n_fr; c[1] = n_fm; c[2] = n_av; }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// MatchingResult::range_data_in_local.returns for a batch (map_builder.cc:89-90): every inserted scan's RAW returns, still lying
+// where the filter read them, through Rigid2f(pose_estimate.cast<float>()) -- rigid2f_apply's line with the host's (cos, sin) and
+// translation -- compactly into pinned host memory.  One float2 per lane, consecutive lanes consecutive points.  A workgroup is a
+// tile of KGL_THREADS points of one scan, named by a table as kgb_match's workgroups are: a scan of n points costs
+// ceil(n / KGL_THREADS) workgroups whatever its neighbours' sizes.  DESIGN.md 10.10.
+#define KGL_THREADS 256
+
+struct ToLocalRec {
+    int src_off;                          // its raw returns in the filter's input points
+    int dst_off;                          // its rows in the output
+    int n, pad;
+    float c, s, tx, ty;
+};
+
+struct ToLocalBufs {
+    const unsigned char *tab;             // ToLocalRec[nrec] | int2 (record, tile) per workgroup at wgmap_off
+    int wgmap_off;
+    const float2 *src;                    // the filter's input points
+    float2 *out;                          // pinned host memory
+};
+
+__global__ __launch_bounds__(KGL_THREADS) void kgb_to_local(ToLocalBufs B)
+{
+    const int2 wg = reinterpret_cast<const int2 *>(B.tab + B.wgmap_off)[blockIdx.x];
+    const ToLocalRec R = reinterpret_cast<const ToLocalRec *>(B.tab)[wg.x];
+    const int i = wg.y * KGL_THREADS + (int)threadIdx.x;
+    if (i >= R.n) return;
+    const float2 p = B.src[R.src_off + i];
+    float2 o;
+    rigid2f_point(R.c, R.s, R.tx, R.ty, p.x, p.y, o.x, o.y);
+    B.out[R.dst_off + i] = o;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -785,6 +838,18 @@ enum { KIND_MATCH = 1, KIND_REFINE = 2, KIND_SCAN_MATCH = 3, KIND_INSERT = 4, KI
 // what collect needs of a scan of a filter submit
 struct FilterPending { int status, rec, out_off, n_ret, n_mis; };
 
+// what rgrid_batch_add_range_data hands from stage to stage for one scan
+struct RangeScan {
+    int code, status;
+    int frec;                             // its filter record, -1 without one
+    int src_off, out_off;                 // its raw returns in the filter's input points, its three clouds in the filter's output
+    int n_fr, n_fm, n_av;
+    int mrec;                             // its place among the scans that are matched, -1 without a grid
+    int dst_off;                          // its rows in kgb_to_local's output
+    bool packed;                          // the insert has a record for it: b->sub[j] is its Pending
+    double est[3];                        // MapBuilder::ScanMatch's answer: the refinement's, or the prediction without a grid
+};
+
 // what collect needs of a named slot of a texture submit
 struct TexturePending { int grid; long long out_off; };
 
@@ -850,7 +915,20 @@ struct rgrid_batch {
         batch_host::Pinned<float2> out;
         batch_host::Pinned<int> cnt;         // allocated last: it marks the staging as complete
         std::vector<FilterPending> sub;
+        size_t rot_off = 0;                  // a (cos, sin) per record behind the input points: what kgb_filter<true> rotates by
     } fil;
+    // AddRangeData (range_data_staging, allocated by the first rgrid_batch_add_range_data): kgb_to_local's records and workgroup
+    // table, its output rows; per scan what the stages hand on; the moved clouds of one scan on their way into the insert's segment
+    struct {
+        batch_host::Staging<unsigned char> tab;
+        size_t wgmap_off = 0;
+        batch_host::Pinned<float2> out;      // allocated last: it marks the staging as complete
+        std::vector<RangeScan> scan;
+        std::vector<rgrid_batch_scan> match;
+        std::vector<float> ret, mis;
+        int last_counts[2] = {0, 0};         // launches, synchronisations of the last call
+    } ard;
+    unsigned long long n_launches = 0, n_syncs = 0;   // kernels launched (launch_*) and streams waited for (collect_head) so far
     // the texture (texture_staging): the (value, alpha) table (uint16[32768]) on the device, uploaded by the first texture submit;
     // the output area and the box records, allocated by the first texture submit, the area grown only when a call needs more
     struct {
@@ -932,6 +1010,7 @@ int collect_head(rgrid_batch_t *b, int kind, bool outputs, bool clear_first, int
     if (*count > 0 && !outputs) return RGRID_ERR_INVALID;
     if (clear_first) b->outstanding = false;
     G_TRY(b, hipSetDevice(b->device));
+    ++b->n_syncs;
     G_TRY(b, hipStreamSynchronize(b->stream));
     return RGRID_OK;
 }
@@ -1017,6 +1096,7 @@ void launch_match(rgrid_batch_t *b, int k, const MatchWork &W)
     Bf.cells = b->d_cells; Bf.bb = b->res.d_bb; Bf.arrived = b->res.d_arrived; Bf.out = b->res.best.dv;
     Bf.max_rotations = b->max_rotations < KGB_MAX_ROT ? b->max_rotations : KGB_MAX_ROT;
     const size_t lds = sizeof(int2) * (size_t)((W.n_max + KGB_PF - 1) / KGB_PF * KGB_PF);
+    b->n_launches += b->mode == RGRID_BATCH_REDUCE_ARRIVAL ? 1 : 2;
     if (b->mode == RGRID_BATCH_REDUCE_ARRIVAL) {
         hipLaunchKernelGGL(kgb_match<true>, dim3((unsigned)W.nwg), dim3(KGB_THREADS), lds, b->stream, Bf);
     } else {
@@ -1047,6 +1127,7 @@ void launch_refine(rgrid_batch_t *b, int k, int nrec, int threads)
     RefineBufs Rf;
     Rf.seg = b->seg.buf[k].dv; Rf.rrec_off = (int)b->seg.rrec_off; Rf.raw_off = (int)b->seg.raw_off;
     Rf.cells = b->d_cells; Rf.best = b->res.best.dv; Rf.out = b->res.fine.dv;
+    ++b->n_launches;
     hipLaunchKernelGGL(kgb_refine, dim3((unsigned)nrec), dim3((unsigned)threads), 0, b->stream, Rf);
 }
 
@@ -1076,43 +1157,101 @@ void refine_result(const rgrid_batch_t *b, const Pending &P, double *pose, rgrid
     if (summary) { summary->initial_cost = o.initial_cost; summary->final_cost = o.final_cost; summary->iterations = o.iterations; summary->termination = o.termination; }
 }
 
-// Plans every scan of an insert into b->sub, the slots' limits and the segment's image; the points go forward, straight into
-// segment k.  Gives the number of records.
-int pack_insert(rgrid_batch_t *b, int k, const rgrid_batch_insert_scan *scans, int count)
+// how far an insert's packing has come: records, returns and misses in segment k
+struct InsertWork { int k, nrec, nret, nmis; };
+
+// Plans scan j of an insert into b->sub[j], its slot's limits and the segment's image; the points go forward, straight into
+// segment W.k (they are read here for the last time: the caller may reuse their memory for the next scan).
+void pack_insert_scan(rgrid_batch_t *b, InsertWork &W, const rgrid_batch_insert_scan &s, int j)
 {
     InsertRec *recs = reinterpret_cast<InsertRec *>(b->seg.pack.data());
-    float *ret = reinterpret_cast<float *>(b->seg.buf[k].h + b->seg.f2_off), *mis = reinterpret_cast<float *>(b->seg.buf[k].h + b->seg.raw_off);
-    int nrec = 0, nret = 0, nmis = 0;
-    for (int j = 0; j < count; ++j) {
-        const rgrid_batch_insert_scan &s = scans[j];
-        GridSlot &g = b->grids[(size_t)s.grid];
-        Pending &P = fresh_pending(b, j);
-        // rgrid_grow_as_needed: on the host, from the points that are copied anyway; the move itself is the workgroup's first phase
-        int nx = g.nx, ny = g.ny, off_x = 0, off_y = 0;
-        double max_x = g.max_x, max_y = g.max_y;
-        P.status = plan_growth(s.origin_xy, s.returns_xy, s.n_returns, s.misses_xy, s.n_misses, g.resolution, (long long)b->max_cells, nx, ny,
-                               max_x, max_y, off_x, off_y);
-        if (P.status != RGRID_OK) continue;                                        // the slot stays as it is
-        // rgrid_insert: more points than the handle stages.  The pair has grown the grid by then, so this scan's workgroup grows it too
-        const bool fits = s.n_returns <= b->max_points && s.n_misses <= b->max_points;
-        if (!fits) P.status = RGRID_ERR_CAPACITY;
-        if (!fits && nx == g.nx && ny == g.ny) continue;
-        InsertRec &R = recs[nrec];
-        std::memset(&R, 0, sizeof(R));
-        R.A.nx = nx; R.A.ny = ny; R.A.n_ret = fits ? s.n_returns : 0; R.A.n_miss = fits ? s.n_misses : 0;
-        R.A.max_x = max_x; R.A.max_y = max_y; R.A.rs = g.resolution / SUBPX;
-        R.A.ox = s.origin_xy[0]; R.A.oy = s.origin_xy[1];
-        R.cells_off = cells_offset(b, s.grid);
-        R.old_nx = g.nx; R.old_ny = g.ny; R.off_x = off_x; R.off_y = off_y;
-        R.ret_off = nret; R.mis_off = nmis;
-        if (R.A.n_ret > 0) std::memcpy(ret + 2 * (size_t)nret, s.returns_xy, sizeof(float) * 2 * (size_t)R.A.n_ret);   // forward, straight into the segment
-        if (R.A.n_miss > 0) std::memcpy(mis + 2 * (size_t)nmis, s.misses_xy, sizeof(float) * 2 * (size_t)R.A.n_miss);
-        nret += R.A.n_ret; nmis += R.A.n_miss;
-        g.nx = nx; g.ny = ny; g.max_x = max_x; g.max_y = max_y;                    // what later submits' records are filled from
-        P.rec = nrec;
-        ++nrec;
+    float *ret = reinterpret_cast<float *>(b->seg.buf[W.k].h + b->seg.f2_off), *mis = reinterpret_cast<float *>(b->seg.buf[W.k].h + b->seg.raw_off);
+    int &nrec = W.nrec, &nret = W.nret, &nmis = W.nmis;
+    GridSlot &g = b->grids[(size_t)s.grid];
+    Pending &P = fresh_pending(b, j);
+    // rgrid_grow_as_needed: on the host, from the points that are copied anyway; the move itself is the workgroup's first phase
+    int nx = g.nx, ny = g.ny, off_x = 0, off_y = 0;
+    double max_x = g.max_x, max_y = g.max_y;
+    P.status = plan_growth(s.origin_xy, s.returns_xy, s.n_returns, s.misses_xy, s.n_misses, g.resolution, (long long)b->max_cells, nx, ny,
+                           max_x, max_y, off_x, off_y);
+    if (P.status != RGRID_OK) return;                                          // the slot stays as it is
+    // rgrid_insert: more points than the handle stages.  The pair has grown the grid by then, so this scan's workgroup grows it too
+    const bool fits = s.n_returns <= b->max_points && s.n_misses <= b->max_points;
+    if (!fits) P.status = RGRID_ERR_CAPACITY;
+    if (!fits && nx == g.nx && ny == g.ny) return;
+    InsertRec &R = recs[nrec];
+    std::memset(&R, 0, sizeof(R));
+    R.A.nx = nx; R.A.ny = ny; R.A.n_ret = fits ? s.n_returns : 0; R.A.n_miss = fits ? s.n_misses : 0;
+    R.A.max_x = max_x; R.A.max_y = max_y; R.A.rs = g.resolution / SUBPX;
+    R.A.ox = s.origin_xy[0]; R.A.oy = s.origin_xy[1];
+    R.cells_off = cells_offset(b, s.grid);
+    R.old_nx = g.nx; R.old_ny = g.ny; R.off_x = off_x; R.off_y = off_y;
+    R.ret_off = nret; R.mis_off = nmis;
+    if (R.A.n_ret > 0) std::memcpy(ret + 2 * (size_t)nret, s.returns_xy, sizeof(float) * 2 * (size_t)R.A.n_ret);   // forward, straight into the segment
+    if (R.A.n_miss > 0) std::memcpy(mis + 2 * (size_t)nmis, s.misses_xy, sizeof(float) * 2 * (size_t)R.A.n_miss);
+    nret += R.A.n_ret; nmis += R.A.n_miss;
+    g.nx = nx; g.ny = ny; g.max_x = max_x; g.max_y = max_y;                    // what later submits' records are filled from
+    P.rec = nrec;
+    ++nrec;
+}
+
+// The lookup tables of an insert (they only depend on the two probabilities) and its next segment
+int begin_insert(rgrid_batch_t *b, const rgrid_insert_options *opt, InsertWork &W)
+{
+    G_TRY(b, hipSetDevice(b->device));
+    if (opt->hit_probability != b->ins.tab_hit_p || opt->miss_probability != b->ins.tab_miss_p) {
+        std::vector<unsigned short> t(32768);
+        lookup_table(opt->hit_probability, t.data());
+        G_TRY(b, hipMemcpy(b->ins.d_hit, t.data(), 2 * 32768, hipMemcpyHostToDevice));
+        lookup_table(opt->miss_probability, t.data());
+        G_TRY(b, hipMemcpy(b->ins.d_miss, t.data(), 2 * 32768, hipMemcpyHostToDevice));
+        b->ins.tab_hit_p = opt->hit_probability; b->ins.tab_miss_p = opt->miss_probability;
     }
-    return nrec;
+    W = InsertWork{next_segment(b), 0, 0, 0};
+    return RGRID_OK;
+}
+
+// the packed records into their segment, which is taken when there are any
+void stage_insert(rgrid_batch_t *b, const InsertWork &W)
+{
+    if (W.nrec == 0) return;
+    take_segment(b);
+    std::memcpy(b->seg.buf[W.k].h, b->seg.pack.data(), sizeof(InsertRec) * (size_t)W.nrec);
+}
+
+void launch_insert(rgrid_batch_t *b, const rgrid_insert_options *opt, const InsertWork &W)
+{
+    InsertBufs If;
+    If.seg = b->seg.buf[W.k].dv; If.f2_off = (int)b->seg.f2_off; If.raw_off = (int)b->seg.raw_off;
+    If.cells = b->d_cells; If.hit = b->ins.d_hit; If.miss = b->ins.d_miss; If.bad = b->ins.bad.dv; If.free_space = opt->insert_free_space ? 1 : 0;
+    ++b->n_launches;
+    hipLaunchKernelGGL(kgb_insert, dim3((unsigned)W.nrec), dim3(KGI_THREADS), 0, b->stream, If);
+}
+
+bool insert_options_ok(const rgrid_insert_options *o)
+{
+    return o->hit_probability > 0.f && o->hit_probability < 1.f && o->miss_probability > 0.f && o->miss_probability < 1.f;
+}
+
+// A slot at most once per call: two insertions into one grid in one launch have no reference meaning (FinishUpdate lies between).
+// The call is counted, and its slots marked, before anything else can refuse it.
+template <typename Scan>
+bool slots_named_once(rgrid_batch_t *b, const Scan *scans, int count)
+{
+    ++b->ins.n_calls;
+    for (int j = 0; j < count; ++j) {
+        unsigned long long &seen = b->ins.slot_call[(size_t)scans[j].grid];
+        if (seen == b->ins.n_calls) return false;
+        seen = b->ins.n_calls;
+    }
+    return true;
+}
+
+// scan j's status of an insert whose launch has been waited for
+int insert_status(const rgrid_batch_t *b, int j)
+{
+    const Pending &P = b->sub[(size_t)j];
+    return (P.status == RGRID_OK && b->ins.bad.h[P.rec]) ? RGRID_ERR_CAPACITY : P.status;   // an end point outside the grid after growth
 }
 
 // points per cloud of a filter submit: what the handle stages and what one workgroup of kgb_filter holds
@@ -1136,18 +1275,81 @@ int filter_staging(rgrid_batch_t *b)
 {
     const size_t nS = (size_t)b->max_scans, nP = (size_t)filter_point_cap(b);
     b->fil.pts_off = align_up(sizeof(FilterRec) * nS, 256);
-    const size_t in_bytes = b->fil.pts_off + sizeof(float2) * 2 * nS * nP, out_points = 3 * nS * nP;
+    b->fil.rot_off = b->fil.pts_off + sizeof(float2) * 2 * nS * nP;
+    const size_t in_bytes = b->fil.rot_off + sizeof(float2) * nS, out_points = 3 * nS * nP;
     if (out_points > 0x7fffffffu) return RGRID_ERR_CAPACITY;                       // a record's offsets are ints
     if (b->seg.pack.size() < sizeof(FilterRec) * nS) b->seg.pack.resize(sizeof(FilterRec) * nS);
     b->fil.sub.resize(nS);
     if (!b->fil.in.h) G_TRY(b, b->fil.in.alloc(in_bytes));
     if (!b->fil.out.h) G_TRY(b, b->fil.out.alloc(out_points));
     // the keys and the table of an 8192-point cloud: 128 KB of LDS, above the 64 KB a launch gets unasked
-    G_TRY(b, hipFuncSetAttribute((const void *)kgb_filter, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(KGF_SCRATCH + sizeof(int2) * (KGF_MAX_POINTS + 16) + sizeof(int) * (size_t)kgf_table_size(KGF_MAX_POINTS))));
+    const int lds_max = (int)(KGF_SCRATCH + sizeof(int2) * (KGF_MAX_POINTS + 16) + sizeof(int) * (size_t)kgf_table_size(KGF_MAX_POINTS));
+    G_TRY(b, hipFuncSetAttribute((const void *)kgb_filter<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    G_TRY(b, hipFuncSetAttribute((const void *)kgb_filter<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
     G_TRY(b, b->fil.cnt.alloc(3 * nS));
     std::memset(b->fil.cnt.h, 0, sizeof(int) * 3 * nS);
     return RGRID_OK;
+}
+
+bool filter_options_ok(const rgrid_filter_options *o) { return o->voxel_filter_size > 0.f && o->adaptive_max_length > 0.; }
+
+// how far a filter's packing has come: records, input points, output points, the largest cloud
+struct FilterWork { int nrec, nin, nout, n_max; };
+
+// the filter's staging (made by the handle's first filter) and an empty packing
+int begin_filter(rgrid_batch_t *b, FilterWork &W)
+{
+    G_TRY(b, hipSetDevice(b->device));
+    if (!b->fil.cnt.h) {
+        const int rc = filter_staging(b);
+        if (rc != RGRID_OK) return rc;
+    }
+    W = FilterWork{0, 0, 0, 0};
+    return RGRID_OK;
+}
+
+// Scan j of a filter into b->fil.sub[j] and, when it can run, into a record (in the image of a match's records: free between
+// submits) with its points forward, straight into the staging.  Gives the record, or null with the scan's status set.
+FilterRec *pack_filter_scan(rgrid_batch_t *b, FilterWork &W, int j, const float *returns_xy, int n_returns, const float *misses_xy, int n_misses)
+{
+    const int cap = filter_point_cap(b);
+    float *pts = reinterpret_cast<float *>(b->fil.in.h + b->fil.pts_off);
+    FilterPending &P = b->fil.sub[(size_t)j];
+    P.status = RGRID_OK; P.rec = -1; P.out_off = 0; P.n_ret = n_returns; P.n_mis = n_misses;
+    if (n_returns > cap || n_misses > cap) { P.status = RGRID_ERR_CAPACITY; return nullptr; }
+    if (!all_finite(returns_xy, 2 * (size_t)n_returns) || !all_finite(misses_xy, 2 * (size_t)n_misses)) { P.status = RGRID_ERR_INVALID; return nullptr; }
+    FilterRec &R = reinterpret_cast<FilterRec *>(b->seg.pack.data())[W.nrec];
+    R.n_ret = n_returns; R.n_mis = n_misses; R.ret_off = W.nin; R.mis_off = W.nin + n_returns; R.out_off = W.nout; R.pad = 0;
+    if (n_returns > 0) std::memcpy(pts + 2 * (size_t)R.ret_off, returns_xy, sizeof(float) * 2 * (size_t)n_returns);   // forward, straight into the staging
+    if (n_misses > 0) std::memcpy(pts + 2 * (size_t)R.mis_off, misses_xy, sizeof(float) * 2 * (size_t)n_misses);
+    W.nin += n_returns + n_misses;
+    W.nout += 2 * n_returns + n_misses;
+    if (n_returns > W.n_max) W.n_max = n_returns;
+    if (n_misses > W.n_max) W.n_max = n_misses;
+    P.rec = W.nrec; P.out_off = R.out_off;
+    ++W.nrec;
+    return &R;
+}
+
+// the packed records into the staging (its own: no segment is taken)
+void stage_filter(rgrid_batch_t *b, const FilterWork &W)
+{
+    std::memcpy(b->fil.in.h, b->seg.pack.data(), sizeof(FilterRec) * (size_t)W.nrec);
+}
+
+// one workgroup per record; ROT: every record has its (cos, sin) at rot_off of the staging
+template <bool ROT>
+void launch_filter(rgrid_batch_t *b, const rgrid_filter_options *opt, const FilterWork &W)
+{
+    FilterBufs Ff;
+    Ff.in = b->fil.in.dv; Ff.pts_off = (int)b->fil.pts_off; Ff.key_cap = (W.n_max + 15) / 16 * 16 + 16;
+    Ff.out = b->fil.out.dv; Ff.counts = b->fil.cnt.dv;
+    Ff.min_pts = opt->adaptive_min_num_points;
+    Ff.vsize = opt->voxel_filter_size; Ff.maxl = (float)opt->adaptive_max_length; Ff.max_range = (float)opt->adaptive_max_range;
+    const size_t lds = KGF_SCRATCH + sizeof(int2) * (size_t)Ff.key_cap + sizeof(int) * (size_t)kgf_table_size(W.n_max);
+    const float2 *rot = ROT ? reinterpret_cast<const float2 *>(b->fil.in.dv + b->fil.rot_off) : nullptr;
+    ++b->n_launches;
+    hipLaunchKernelGGL(kgb_filter<ROT>, dim3((unsigned)W.nrec), dim3(KGF_THREADS), lds, b->stream, Ff, rot);
 }
 
 // the texture's staging for a call that writes `pairs` pairs: the table and the box records once, the output area when it is too small
@@ -1199,6 +1401,70 @@ int occupancy_staging(rgrid_batch_t *b, size_t bytes)
         b->occ.out_bytes = bytes;
     }
     return RGRID_OK;
+}
+
+// MapBuilder::ScanMatch for scans that passed match_scans_ok: the match's records, a refine record per match record (same index:
+// the start pose is the match's winner, decoded on the device), both launches behind each other, KIND_SCAN_MATCH pending
+int submit_scan_match(rgrid_batch_t *b, const rgrid_match_options *mopt, const rgrid_refine_options *ropt, const rgrid_batch_scan *scans, int count)
+{
+    const auto t_begin = std::chrono::steady_clock::now();
+    const MatchWork W = pack_match(b, mopt, scans, count);
+    int k = 0, nraw = 0, threads = 0;
+    if (W.nrec > 0) {
+        G_TRY(b, hipSetDevice(b->device));
+        k = take_segment(b);
+        for (int j = 0; j < count; ++j) {
+            const Pending &P = b->sub[(size_t)j];
+            if (P.status != RGRID_OK) continue;
+            const rgrid_batch_scan &s = scans[j];
+            RefineRec &R = pack_refine(b, k, P.rec, ropt, s.grid, s.points_xy, s.n, nraw, threads);
+            R.plan_res = P.plan.res; R.plan_step = P.plan.step;
+            R.ip[0] = s.initial_pose[0]; R.ip[1] = s.initial_pose[1]; R.ip[2] = s.initial_pose[2];
+            R.match_rec = P.rec; R.num_linear = P.plan.num_linear; R.num_angular = P.plan.num_angular;
+        }
+        stage_match(b, k, W);
+        std::memcpy(b->seg.buf[k].h + b->seg.rrec_off, b->seg.pack.data() + b->seg.rrec_off, sizeof(RefineRec) * (size_t)W.nrec);
+    }
+    return submit_tail(b, KIND_SCAN_MATCH, count, W.nrec, t_begin, [&] {
+        launch_match(b, k, W);                                // the stream orders the refinement behind the match: no host wait between them
+        launch_refine(b, k, W.nrec, threads);
+    });
+}
+
+// tiles of KGL_THREADS points a cloud of the largest size has
+int to_local_tiles(const rgrid_batch_t *b) { return (filter_point_cap(b) + KGL_THREADS - 1) / KGL_THREADS; }
+
+// AddRangeData's own staging: kgb_to_local's records and workgroup table for max_scans scans, its output rows, the host's per-scan
+// notes.  A call that fails part-way keeps what it allocated, and the next one goes on from there.
+int range_data_staging(rgrid_batch_t *b)
+{
+    const size_t nS = (size_t)b->max_scans, nP = (size_t)filter_point_cap(b);
+    b->ard.wgmap_off = align_up(sizeof(ToLocalRec) * nS, 256);
+    b->ard.scan.resize(nS);
+    b->ard.match.resize(nS);
+    b->ard.ret.resize(2 * nP);
+    b->ard.mis.resize(2 * nP);
+    if (!b->ard.tab.h) G_TRY(b, b->ard.tab.alloc(b->ard.wgmap_off + sizeof(int2) * nS * (size_t)to_local_tiles(b)));
+    G_TRY(b, b->ard.out.alloc(nS * nP));
+    return RGRID_OK;
+}
+
+// one workgroup per (record, tile) of the table in the staging
+void launch_to_local(rgrid_batch_t *b, int nwg)
+{
+    ToLocalBufs Lf;
+    Lf.tab = b->ard.tab.dv; Lf.wgmap_off = (int)b->ard.wgmap_off;
+    Lf.src = reinterpret_cast<const float2 *>(b->fil.in.dv + b->fil.pts_off); Lf.out = b->ard.out.dv;
+    ++b->n_launches;
+    hipLaunchKernelGGL(kgb_to_local, dim3((unsigned)nwg), dim3(KGL_THREADS), 0, b->stream, Lf);
+}
+
+// the caller's quaternion of an EKF yaw (src/ros_node.cc:548) and the gravity alignment's yaw (map_builder.cc:20-28): Rotation(q)
+// .cast<float>() -> Project2D -> GetYaw
+void gravity_alignment(double theta, double &qw, double &qz, float &yaw_g)
+{
+    qw = std::cos(theta / 2); qz = std::sin(theta / 2);
+    yaw_g = yaw_of_quaternion_f32((float)qw, (float)qz);
 }
 
 }  // namespace
@@ -1275,6 +1541,7 @@ void rgrid_batch_destroy(rgrid_batch_t *b)
     for (auto &s : b->seg.buf) s.release();
     b->res.best.release(); b->res.fine.release(); b->ins.bad.release();
     b->fil.in.release(); b->fil.out.release(); b->fil.cnt.release();
+    b->ard.tab.release(); b->ard.out.release();
     b->tex.out.release(); b->tex.box.release();
     b->occ.out.release(); b->occ.box.release();
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -1376,29 +1643,7 @@ int rgrid_batch_scan_match_submit(rgrid_batch_t *b, const rgrid_match_options *m
     if (!b || !mopt || !ropt || count < 0 || count > b->max_scans || (count > 0 && !scans) || b->outstanding || !refine_options_ok(ropt))
         return RGRID_ERR_INVALID;
     if (!match_scans_ok(b, scans, count)) return RGRID_ERR_INVALID;
-    const auto t_begin = std::chrono::steady_clock::now();
-    const MatchWork W = pack_match(b, mopt, scans, count);
-    int k = 0, nraw = 0, threads = 0;
-    if (W.nrec > 0) {
-        G_TRY(b, hipSetDevice(b->device));
-        k = take_segment(b);
-        // a refine record per match record, same index: the start pose is the match's winner, decoded on the device
-        for (int j = 0; j < count; ++j) {
-            const Pending &P = b->sub[(size_t)j];
-            if (P.status != RGRID_OK) continue;
-            const rgrid_batch_scan &s = scans[j];
-            RefineRec &R = pack_refine(b, k, P.rec, ropt, s.grid, s.points_xy, s.n, nraw, threads);
-            R.plan_res = P.plan.res; R.plan_step = P.plan.step;
-            R.ip[0] = s.initial_pose[0]; R.ip[1] = s.initial_pose[1]; R.ip[2] = s.initial_pose[2];
-            R.match_rec = P.rec; R.num_linear = P.plan.num_linear; R.num_angular = P.plan.num_angular;
-        }
-        stage_match(b, k, W);
-        std::memcpy(b->seg.buf[k].h + b->seg.rrec_off, b->seg.pack.data() + b->seg.rrec_off, sizeof(RefineRec) * (size_t)W.nrec);
-    }
-    return submit_tail(b, KIND_SCAN_MATCH, count, W.nrec, t_begin, [&] {
-        launch_match(b, k, W);                                // the stream orders the refinement behind the match: no host wait between them
-        launch_refine(b, k, W.nrec, threads);
-    });
+    return submit_scan_match(b, mopt, ropt, scans, count);
 }
 
 int rgrid_batch_scan_match_collect(rgrid_batch_t *b, int *status, double *coarse_poses, double *scores, int *best3, int *info3,
@@ -1443,42 +1688,19 @@ int rgrid_batch_insert_submit(rgrid_batch_t *b, const rgrid_insert_options *opt,
 {
     // (scans == NULL is refused at count == 0 too, unlike the match, the refinement and the texture: callers may rely on it)
     if (!b || !opt || !scans || count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
-    if (!(opt->hit_probability > 0.f && opt->hit_probability < 1.f) || !(opt->miss_probability > 0.f && opt->miss_probability < 1.f))
-        return RGRID_ERR_INVALID;
+    if (!insert_options_ok(opt)) return RGRID_ERR_INVALID;
     for (int j = 0; j < count; ++j) {
         const rgrid_batch_insert_scan &s = scans[j];
         if (!slot_ok(b, s.grid) || !two_clouds_ok(s.returns_xy, s.n_returns, s.misses_xy, s.n_misses)) return RGRID_ERR_INVALID;
     }
-    // a slot at most once per call: two insertions into one grid in one launch have no reference meaning (FinishUpdate lies between).
-    // The call is counted, and its slots marked, before anything else can refuse it
-    ++b->ins.n_calls;
-    for (int j = 0; j < count; ++j) {
-        unsigned long long &seen = b->ins.slot_call[(size_t)scans[j].grid];
-        if (seen == b->ins.n_calls) return RGRID_ERR_INVALID;
-        seen = b->ins.n_calls;
-    }
+    if (!slots_named_once(b, scans, count)) return RGRID_ERR_INVALID;
     const auto t_begin = std::chrono::steady_clock::now();
-    G_TRY(b, hipSetDevice(b->device));
-    if (opt->hit_probability != b->ins.tab_hit_p || opt->miss_probability != b->ins.tab_miss_p) {   // the tables only depend on the two options
-        std::vector<unsigned short> t(32768);
-        lookup_table(opt->hit_probability, t.data());
-        G_TRY(b, hipMemcpy(b->ins.d_hit, t.data(), 2 * 32768, hipMemcpyHostToDevice));
-        lookup_table(opt->miss_probability, t.data());
-        G_TRY(b, hipMemcpy(b->ins.d_miss, t.data(), 2 * 32768, hipMemcpyHostToDevice));
-        b->ins.tab_hit_p = opt->hit_probability; b->ins.tab_miss_p = opt->miss_probability;
-    }
-    const int k = next_segment(b);
-    const int nrec = pack_insert(b, k, scans, count);
-    if (nrec > 0) {
-        take_segment(b);
-        std::memcpy(b->seg.buf[k].h, b->seg.pack.data(), sizeof(InsertRec) * (size_t)nrec);
-    }
-    return submit_tail(b, KIND_INSERT, count, nrec, t_begin, [&] {
-        InsertBufs If;
-        If.seg = b->seg.buf[k].dv; If.f2_off = (int)b->seg.f2_off; If.raw_off = (int)b->seg.raw_off;
-        If.cells = b->d_cells; If.hit = b->ins.d_hit; If.miss = b->ins.d_miss; If.bad = b->ins.bad.dv; If.free_space = opt->insert_free_space ? 1 : 0;
-        hipLaunchKernelGGL(kgb_insert, dim3((unsigned)nrec), dim3(KGI_THREADS), 0, b->stream, If);
-    });
+    InsertWork W;
+    const int rc = begin_insert(b, opt, W);
+    if (rc != RGRID_OK) return rc;
+    for (int j = 0; j < count; ++j) pack_insert_scan(b, W, scans[j], j);
+    stage_insert(b, W);
+    return submit_tail(b, KIND_INSERT, count, W.nrec, t_begin, [&] { launch_insert(b, opt, W); });
 }
 
 int rgrid_batch_insert_collect(rgrid_batch_t *b, int *status)
@@ -1486,10 +1708,7 @@ int rgrid_batch_insert_collect(rgrid_batch_t *b, int *status)
     int count = 0;
     const int rc = collect_head(b, KIND_INSERT, status != nullptr, true, &count);
     if (rc != RGRID_OK) return rc;
-    for (int j = 0; j < count; ++j) {
-        const Pending &P = b->sub[(size_t)j];
-        status[j] = (P.status == RGRID_OK && b->ins.bad.h[P.rec]) ? RGRID_ERR_CAPACITY : P.status;   // an end point outside the grid after growth
-    }
+    for (int j = 0; j < count; ++j) status[j] = insert_status(b, j);
     return RGRID_OK;
 }
 
@@ -1501,46 +1720,16 @@ int rgrid_batch_filter_submit(rgrid_batch_t *b, const rgrid_filter_options *opt,
 {
     // (scans == NULL is refused at count == 0 too, as by the inserter)
     if (!b || !opt || !scans || count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
-    if (!(opt->voxel_filter_size > 0.f) || !(opt->adaptive_max_length > 0.)) return RGRID_ERR_INVALID;
+    if (!filter_options_ok(opt)) return RGRID_ERR_INVALID;
     for (int j = 0; j < count; ++j)
         if (!two_clouds_ok(scans[j].returns_xy, scans[j].n_returns, scans[j].misses_xy, scans[j].n_misses)) return RGRID_ERR_INVALID;
     const auto t_begin = std::chrono::steady_clock::now();
-    G_TRY(b, hipSetDevice(b->device));
-    const int cap = filter_point_cap(b);
-    if (!b->fil.cnt.h) {                                                           // the first filter submit of this handle
-        const int rc = filter_staging(b);
-        if (rc != RGRID_OK) return rc;
-    }
-    FilterRec *recs = reinterpret_cast<FilterRec *>(b->seg.pack.data());           // (the image of a match's records: free between submits)
-    float *pts = reinterpret_cast<float *>(b->fil.in.h + b->fil.pts_off);
-    int nrec = 0, nin = 0, nout = 0, n_max = 0;
-    for (int j = 0; j < count; ++j) {
-        const rgrid_batch_filter_scan &s = scans[j];
-        FilterPending &P = b->fil.sub[(size_t)j];
-        P.status = RGRID_OK; P.rec = -1; P.out_off = 0; P.n_ret = s.n_returns; P.n_mis = s.n_misses;
-        if (s.n_returns > cap || s.n_misses > cap) { P.status = RGRID_ERR_CAPACITY; continue; }
-        if (!all_finite(s.returns_xy, 2 * (size_t)s.n_returns) || !all_finite(s.misses_xy, 2 * (size_t)s.n_misses)) { P.status = RGRID_ERR_INVALID; continue; }
-        FilterRec &R = recs[nrec];
-        R.n_ret = s.n_returns; R.n_mis = s.n_misses; R.ret_off = nin; R.mis_off = nin + s.n_returns; R.out_off = nout; R.pad = 0;
-        if (s.n_returns > 0) std::memcpy(pts + 2 * (size_t)R.ret_off, s.returns_xy, sizeof(float) * 2 * (size_t)s.n_returns);   // forward, straight into the staging
-        if (s.n_misses > 0) std::memcpy(pts + 2 * (size_t)R.mis_off, s.misses_xy, sizeof(float) * 2 * (size_t)s.n_misses);
-        nin += s.n_returns + s.n_misses;
-        nout += 2 * s.n_returns + s.n_misses;
-        if (s.n_returns > n_max) n_max = s.n_returns;
-        if (s.n_misses > n_max) n_max = s.n_misses;
-        P.rec = nrec; P.out_off = R.out_off;
-        ++nrec;
-    }
-    std::memcpy(b->fil.in.h, recs, sizeof(FilterRec) * (size_t)nrec);              // (its own staging: no segment is taken)
-    return submit_tail(b, KIND_FILTER, count, nrec, t_begin, [&] {
-        FilterBufs Ff;
-        Ff.in = b->fil.in.dv; Ff.pts_off = (int)b->fil.pts_off; Ff.key_cap = (n_max + 15) / 16 * 16 + 16;
-        Ff.out = b->fil.out.dv; Ff.counts = b->fil.cnt.dv;
-        Ff.min_pts = opt->adaptive_min_num_points;
-        Ff.vsize = opt->voxel_filter_size; Ff.maxl = (float)opt->adaptive_max_length; Ff.max_range = (float)opt->adaptive_max_range;
-        const size_t lds = KGF_SCRATCH + sizeof(int2) * (size_t)Ff.key_cap + sizeof(int) * (size_t)kgf_table_size(n_max);
-        hipLaunchKernelGGL(kgb_filter, dim3((unsigned)nrec), dim3(KGF_THREADS), lds, b->stream, Ff);
-    });
+    FilterWork W;
+    const int rc = begin_filter(b, W);
+    if (rc != RGRID_OK) return rc;
+    for (int j = 0; j < count; ++j) pack_filter_scan(b, W, j, scans[j].returns_xy, scans[j].n_returns, scans[j].misses_xy, scans[j].n_misses);
+    stage_filter(b, W);
+    return submit_tail(b, KIND_FILTER, count, W.nrec, t_begin, [&] { launch_filter<false>(b, opt, W); });
 }
 
 int rgrid_batch_filter_collect(rgrid_batch_t *b, int *status, int *counts, float *out_xy, long out_cap_points)
@@ -1692,6 +1881,186 @@ int rgrid_batch_occupancy_collect(rgrid_batch_t *b, int *status, int *sizes, dou
         if (status[j] == RGRID_OK)
             occupancy_paint(b->occ.mode, b->occ.out.h + b->occ.sub[(size_t)j].out_off, boxes[4 * j + 2], boxes[4 * j + 3], &sizes[2 * j],
                             reinterpret_cast<unsigned char *>(out) + offsets[j]);
+    return RGRID_OK;
+}
+
+int rgrid_batch_sizeof_range_data(void) { return (int)sizeof(rgrid_batch_range_data); }
+
+int rgrid_batch_last_call_counts(rgrid_batch_t *b, int launches_syncs[2])
+{
+    if (!b || !launches_syncs) return RGRID_ERR_INVALID;
+    launches_syncs[0] = b->ard.last_counts[0]; launches_syncs[1] = b->ard.last_counts[1];
+    return RGRID_OK;
+}
+
+// mapping::MapBuilder::AddRangeData (map_builder.cc:57-108) for one scan of every robot: rgrid_add_range_data's steps, each of them
+// the batch's own stage -- the single-kind submits' packing and launches, a collect_head per wait -- with the host doing between
+// them what rgrid_add_range_data's host does, through the same functions (rgrid_dev.h).  DESIGN.md 10.10.
+int rgrid_batch_add_range_data(rgrid_batch_t *b, const rgrid_map_builder_options *opt, const rgrid_batch_range_data *scans, int count,
+                               int *codes, int *status, double *local_poses, float *origins_in_local, float *returns_in_local, long cap_points)
+{
+#pragma clang fp contract(off)
+    if (!b || !opt || !scans || !codes || !status || !local_poses || !origins_in_local) return RGRID_ERR_INVALID;
+    if (count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
+    const rgrid_filter_options fopt = {opt->voxel_filter_size, opt->adaptive_max_length, opt->adaptive_min_num_points, opt->adaptive_max_range};
+    const rgrid_insert_options iopt = {opt->hit_probability, opt->miss_probability, opt->insert_free_space};
+    if (!filter_options_ok(&fopt) || !refine_options_ok(&opt->refine) || !insert_options_ok(&iopt)) return RGRID_ERR_INVALID;
+    long total = 0;
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_range_data &s = scans[j];
+        if (s.grid < 0 || s.grid >= b->num_grids || !two_clouds_ok(s.returns_xy, s.n_returns, s.misses_xy, s.n_misses)) return RGRID_ERR_INVALID;
+        total += s.n_returns;
+    }
+    if (!slots_named_once(b, scans, count)) return RGRID_ERR_INVALID;
+    if (returns_in_local && cap_points < total) return RGRID_ERR_BUFFER;
+    b->ard.last_counts[0] = b->ard.last_counts[1] = 0;
+    if (count == 0) return RGRID_OK;
+    const unsigned long long launches0 = b->n_launches, syncs0 = b->n_syncs;
+    auto t_begin = std::chrono::steady_clock::now();
+    int waited = 0;
+    // ---- 1. gravity alignment and the three filters: one launch of kgb_filter<true>, one wait
+    FilterWork F;
+    int rc = begin_filter(b, F);
+    if (rc != RGRID_OK) return rc;
+    if (!b->ard.out.h && (rc = range_data_staging(b)) != RGRID_OK) return rc;     // the first call of this handle
+    float2 *rot = reinterpret_cast<float2 *>(b->fil.in.h + b->fil.rot_off);
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_range_data &s = scans[j];
+        RangeScan &S = b->ard.scan[(size_t)j];
+        std::memset(&S, 0, sizeof(S));
+        S.frec = S.mrec = -1;
+        codes[j] = RGRID_OK; status[j] = RGRID_SCAN_DROPPED_EMPTY;
+        zero3(&local_poses[3 * j]);
+        origins_in_local[2 * j] = origins_in_local[2 * j + 1] = 0.f;
+        if (s.n_returns == 0) continue;                                          // "Dropped empty horizontal range data." (:63-67)
+        const FilterRec *R = pack_filter_scan(b, F, j, s.returns_xy, s.n_returns, s.misses_xy, s.n_misses);
+        if (!R) { codes[j] = b->fil.sub[(size_t)j].status; continue; }
+        double qw, qz;
+        float yaw_g, c, sn;
+        gravity_alignment(s.ekf_pose[2], qw, qz, yaw_g);
+        rigid2f_cs(yaw_g, &c, &sn);
+        S.frec = b->fil.sub[(size_t)j].rec; S.src_off = R->ret_off; S.out_off = R->out_off;
+        rot[S.frec] = make_float2(c, sn);
+    }
+    if (F.nrec > 0) {
+        stage_filter(b, F);
+        if ((rc = submit_tail(b, KIND_FILTER, count, F.nrec, t_begin, [&] { launch_filter<true>(b, &fopt, F); })) != RGRID_OK) return rc;
+        if ((rc = collect_head(b, KIND_FILTER, true, true, &waited)) != RGRID_OK) return rc;
+    }
+    // ---- 2. the decisions (:61-77), 3. ScanMatch for the scans that have a grid: the adaptively filtered clouds read where the
+    // filter wrote them, the prediction (x, y, 0) -- the rotations cancel (:70-71) -- as start; two launches, one wait
+    int nm = 0;
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_range_data &s = scans[j];
+        RangeScan &S = b->ard.scan[(size_t)j];
+        if (S.frec < 0) continue;
+        const int *c = b->fil.cnt.h + 3 * S.frec;
+        S.n_fr = c[0]; S.n_fm = c[1]; S.n_av = c[2];
+        status[j] = RGRID_SCAN_FILTERED_EMPTY;
+        S.est[0] = s.ekf_pose[0]; S.est[1] = s.ekf_pose[1]; S.est[2] = 0.0;
+        if (S.n_av == 0 || !b->grids[(size_t)s.grid].set) continue;              // (:74-77); no submap yet -> the prediction (:34-55)
+        rgrid_batch_scan &m = b->ard.match[(size_t)nm];
+        m.grid = s.grid; m.n = S.n_av;
+        m.points_xy = reinterpret_cast<const float *>(b->fil.out.h + S.out_off + s.n_returns + s.n_misses);
+        m.initial_pose[0] = S.est[0]; m.initial_pose[1] = S.est[1]; m.initial_pose[2] = S.est[2];
+        S.mrec = nm++;
+    }
+    if (nm > 0) {
+        if ((rc = submit_scan_match(b, &opt->match, &opt->refine, b->ard.match.data(), nm)) != RGRID_OK) return rc;
+        if ((rc = collect_head(b, KIND_SCAN_MATCH, true, true, &waited)) != RGRID_OK) return rc;
+        for (int j = 0; j < count; ++j) {                                        // (the insert's packing reuses b->sub)
+            RangeScan &S = b->ard.scan[(size_t)j];
+            if (S.mrec < 0) continue;
+            const Pending &P = b->sub[(size_t)S.mrec];
+            if (P.status != RGRID_OK) { codes[j] = P.status; continue; }
+            refine_result(b, P, S.est, nullptr);
+        }
+    }
+    // ---- 4. the pose compositions (rgrid_add_range_data's lines) and the insert's packing: the filtered clouds moved by
+    // Embed3D(pose_estimate_2d.cast<float>()) on their way from the filter's output into the insert's segment
+    t_begin = std::chrono::steady_clock::now();
+    InsertWork I;
+    if ((rc = begin_insert(b, &iopt, I)) != RGRID_OK) return rc;
+    ToLocalRec *lrecs = reinterpret_cast<ToLocalRec *>(b->ard.tab.h);
+    int2 *wgmap = reinterpret_cast<int2 *>(b->ard.tab.h + b->ard.wgmap_off);
+    int nl = 0, nwg = 0, ndst = 0;
+    for (int j = 0; j < count; ++j) {
+        const rgrid_batch_range_data &s = scans[j];
+        RangeScan &S = b->ard.scan[(size_t)j];
+        if (S.frec < 0 || S.n_av == 0 || codes[j] != RGRID_OK) continue;
+        const double *est = S.est;
+        double qw, qz;
+        float yaw_g;
+        gravity_alignment(s.ekf_pose[2], qw, qz, yaw_g);
+        // pose_estimate = Embed3D(pose_estimate_2d) * gravity_alignment: quaternion product about z, in double (:86-87)
+        const double aw = std::cos(0.5 * est[2]), az = std::sin(0.5 * est[2]);
+        const double pw = aw * qw - az * qz, pz = aw * qz + az * qw;
+        double *local_pose = &local_poses[3 * j];
+        local_pose[0] = est[0]; local_pose[1] = est[1]; local_pose[2] = yaw_of_quaternion_f64(pw, pz);
+        // range_data_in_local2 = TransformRangeData(gravity-aligned filtered data, Embed3D(pose_estimate_2d.cast<float>())) (:92-94)
+        const float af = (float)est[2], ha = 0.5f * af;
+        const float yaw2 = yaw_of_quaternion_f32((float)std::cos((double)ha), (float)std::sin((double)ha));
+        float org[2], org2[2];
+        rigid2f_apply(0.f, 0.f, yaw_g, s.origin_xy, 1, org);
+        rigid2f_apply((float)est[0], (float)est[1], yaw2, org, 1, org2);
+        origins_in_local[2 * j] = org2[0]; origins_in_local[2 * j + 1] = org2[1];
+        const float *fr = reinterpret_cast<const float *>(b->fil.out.h + S.out_off), *fm = fr + 2 * (size_t)s.n_returns;
+        rigid2f_apply((float)est[0], (float)est[1], yaw2, fr, S.n_fr, b->ard.ret.data());
+        if (S.n_fm > 0) rigid2f_apply((float)est[0], (float)est[1], yaw2, fm, S.n_fm, b->ard.mis.data());
+        GridSlot &g = b->grids[(size_t)s.grid];
+        if (!g.set) {                                                            // InsertIntoSubmap / CreateGrid (:110-126)
+            const int n0 = 100;                                                  // kInitialSubmapSize
+            if ((long long)n0 * n0 > (long long)b->max_cells) { codes[j] = RGRID_ERR_CAPACITY; continue; }
+            const double resolution = (double)opt->resolution;                   // `float resolution = options_.resolution`
+            if (!(resolution > 0.)) { codes[j] = RGRID_ERR_INVALID; continue; }
+            const double half = 0.5 * n0 * resolution;
+            G_TRY(b, hipMemsetAsync(b->d_cells + cells_offset(b, s.grid), 0, sizeof(uint16_t) * (size_t)n0 * n0, b->stream));
+            g.set = true; g.nx = n0; g.ny = n0; g.resolution = resolution; g.max_x = (double)org2[0] + half; g.max_y = (double)org2[1] + half;
+        }
+        rgrid_batch_insert_scan is;
+        is.grid = s.grid; is.n_returns = S.n_fr; is.n_misses = S.n_fm;
+        is.returns_xy = b->ard.ret.data(); is.misses_xy = S.n_fm > 0 ? b->ard.mis.data() : nullptr;
+        is.origin_xy[0] = org2[0]; is.origin_xy[1] = org2[1];
+        pack_insert_scan(b, I, is, j);
+        const Pending &P = b->sub[(size_t)j];
+        if (P.status != RGRID_OK) { codes[j] = P.status; continue; }
+        S.packed = true;
+        if (!returns_in_local) continue;
+        // range_data_in_local.returns = the RAW returns through pose_estimate.cast<float>() (:89-90): kgb_to_local's record
+        ToLocalRec L;
+        L.src_off = S.src_off; L.dst_off = S.dst_off = ndst; L.n = s.n_returns; L.pad = 0;
+        rigid2f_cs(yaw_of_quaternion_f32((float)pw, (float)pz), &L.c, &L.s);
+        L.tx = (float)est[0]; L.ty = (float)est[1];
+        lrecs[nl] = L;
+        for (int t = 0; t * KGL_THREADS < s.n_returns; ++t) wgmap[nwg++] = make_int2(nl, t);
+        ndst += s.n_returns;
+        ++nl;
+    }
+    // ---- 5. the insert and the raw returns: two launches behind each other, one wait
+    stage_insert(b, I);
+    if (I.nrec > 0) {
+        rc = submit_tail(b, KIND_INSERT, count, I.nrec, t_begin, [&] {
+            launch_insert(b, &iopt, I);
+            if (nwg > 0) launch_to_local(b, nwg);
+        });
+        if (rc != RGRID_OK) return rc;
+        if ((rc = collect_head(b, KIND_INSERT, true, true, &waited)) != RGRID_OK) return rc;
+    }
+    long at = 0;
+    for (int j = 0; j < count; ++j) {
+        const RangeScan &S = b->ard.scan[(size_t)j];
+        const long n = scans[j].n_returns;
+        if (S.packed) {
+            const int st = insert_status(b, j);
+            if (st != RGRID_OK) codes[j] = st;
+            else {
+                status[j] = RGRID_SCAN_INSERTED;
+                if (returns_in_local) std::memcpy(returns_in_local + 2 * at, b->ard.out.h + S.dst_off, sizeof(float2) * (size_t)n);
+            }
+        }
+        at += n;
+    }
+    b->ard.last_counts[0] = (int)(b->n_launches - launches0); b->ard.last_counts[1] = (int)(b->n_syncs - syncs0);
     return RGRID_OK;
 }
 

@@ -38,6 +38,14 @@ a ``FleetOccupancyGrid`` with the ``grid.OccupancyGrid`` that ``GridFrontEnd.Occ
 plus a ``status``: the reference's cairo painting of the texture as nav_msgs::OccupancyGrid data (mode OCCUPANCY) or as the bytes of
 the saved PGM (mode IMAGE).
 
+The reference's entry point itself, ``MapBuilder::AddRangeData`` (map_builder.cc:57-108), for one scan of every robot is
+``add_range_data(range_datas, ekf_poses, slots)``: ONE C call (rgrid_batch_add_range_data) runs the five stages above -- the gravity
+alignment of the raw clouds on the device inside the filter's launch, the match and the refinement for the robots that have a
+submap, the insert (a robot's first scan creates its 100 x 100 submap), and ``range_data_in_local.returns`` from the raw returns that
+are still on the device -- with at most five launches and three waits whatever the number of robots (``last_call_counts``).  Per
+robot it gives what ``GridFrontEnd.AddRangeData`` gives for the same scans, bit for bit.  ``map_builder.FleetMapBuilder`` is the
+reference's interface over it.
+
 All arithmetic happens in the HIP kernel behind librgrid.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -50,11 +58,12 @@ import numpy as np
 
 from . import _lib
 from .grid import (IMAGE, OCCUPANCY, AdaptiveVoxelFilterOptions, CeresScanMatcherOptions2D, MatchResult, OccupancyGrid, RangeDataInserterOptions, RealTimeCorrelativeScanMatcherOptions, RefineResult,
-                   RgridError, _lib_rgrid, _MatchOptions, _RefineOptions, _RefineSummary)
+                   RgridError, _lib_rgrid, _MapBuilderOptionsC, _MatchOptions, _RefineOptions, _RefineSummary)
 
 RGRID_OK, RGRID_ERR_INVALID, RGRID_ERR_CAPACITY, RGRID_ERR_EMPTY = 0, -1, -4, -6
 RGRID_ERR_BUFFER = -5
 REDUCE_ARRIVAL, REDUCE_LAUNCH = 0, 1        # rgrid_batch_set_reduction
+SCAN_INSERTED, SCAN_DROPPED_EMPTY, SCAN_FILTERED_EMPTY = 0, 1, 2    # status of a scan of add_range_data (RGRID_SCAN_*)
 
 
 class RgridBatchScan(C.Structure):
@@ -82,6 +91,24 @@ class _InsertOptions(C.Structure):
 class RgridBatchFilterScan(C.Structure):
     """struct rgrid_batch_filter_scan (include/rgrid.h)."""
     _fields_ = [("n_returns", C.c_int), ("n_misses", C.c_int), ("returns_xy", C.c_void_p), ("misses_xy", C.c_void_p)]
+
+
+class RgridBatchRangeData(C.Structure):
+    """struct rgrid_batch_range_data (include/rgrid.h)."""
+    _fields_ = [("grid", C.c_int), ("n_returns", C.c_int), ("n_misses", C.c_int), ("returns_xy", C.c_void_p), ("misses_xy", C.c_void_p),
+                ("origin_xy", C.c_float * 2), ("ekf_pose", C.c_double * 3)]
+
+
+@dataclass
+class FleetRangeDataResult:
+    """What rgrid_batch_add_range_data returns for one scan: ``code`` RGRID_OK or the scan's own error, ``status`` SCAN_INSERTED /
+    SCAN_DROPPED_EMPTY / SCAN_FILTERED_EMPTY, ``local_pose`` (x, y, yaw), ``origin_in_local`` the origin of range_data_in_local2 (the
+    submap's origin when the scan created its slot), ``returns_in_local`` (n_returns, 2) float32, zero unless inserted."""
+    code: int
+    status: int
+    local_pose: np.ndarray
+    origin_in_local: tuple
+    returns_in_local: np.ndarray
 
 
 class _FilterOptions(C.Structure):
@@ -226,6 +253,30 @@ def _declare_occupancy(L):
 
 
 _occupancy_lib = _lib.Feature(_batch_lib, "librgrid.so", ("rgrid_batch_occupancy_submit", "rgrid_batch_occupancy_collect"), (), _declare_occupancy)
+
+
+def _declare_range_data(L):
+    """``_batch_lib()`` with the argtypes of rgrid_batch_add_range_data and rgrid_batch_last_call_counts set.  Raises LibraryMissing
+    when the built library has no such calls or packs another structure (they are looked up by name); every other call keeps working
+    then."""
+    vp = C.c_void_p
+    L.rgrid_batch_add_range_data.argtypes = [vp, C.POINTER(_MapBuilderOptionsC), vp, C.c_int, vp, vp, vp, vp, vp, C.c_long]
+    L.rgrid_batch_last_call_counts.argtypes = [vp, vp]
+
+
+_range_data_lib = _lib.Feature(_batch_lib, "librgrid.so", ("rgrid_batch_add_range_data", "rgrid_batch_last_call_counts"),
+                               [("rgrid_batch_sizeof_range_data", RgridBatchRangeData)], _declare_range_data)
+
+
+def _map_builder_options(o):
+    """struct rgrid_map_builder_options of a ``map_builder.MapBuilderOptions`` (None: the defaults), as GridFrontEnd.AddRangeData packs it."""
+    if o is None:
+        from .map_builder import MapBuilderOptions
+        o = MapBuilderOptions()
+    m, r = o.real_time_scan_matcher_options, o.ceres_scan_matcher_options
+    a, ins = o.adaptive_voxel_options, o.range_data_inserter_options
+    return _MapBuilderOptionsC(o.resolution, o.voxel_filter_size, a.max_length, a.min_num_points, a.max_range, _match_options(m), _refine_options(r),
+                               ins.hit_probability, ins.miss_probability, 1 if ins.insert_free_space else 0)
 
 
 def filter_max_points() -> int:
@@ -713,6 +764,80 @@ class ScanMatchFleet(_lib.Handle):
         """``GridFrontEnd.OccupancyGrid`` of every named slot in ONE launch: a list of FleetOccupancyGrid, in the order named."""
         self.submit_occupancy(slots, submap_origins, mode)
         return self.collect_occupancy()
+
+    # -- MapBuilder::AddRangeData for a batch: every stage above in ONE C call ------------------------------------------------
+    @staticmethod
+    def pack_range_data(range_datas, ekf_poses, slots=None):
+        """One ``map_builder.RangeData`` (tracking frame) and one EKF pose (x, y, yaw) per scan, scan i into slot ``slots[i]``
+        (default: slot i).  -> (ctypes array of rgrid_batch_range_data, count, the arrays it points into)."""
+        range_datas, ekf_poses = list(range_datas), list(ekf_poses)
+        slots = list(range(len(range_datas))) if slots is None else [int(k) for k in slots]
+        if not len(range_datas) == len(ekf_poses) == len(slots):
+            raise ValueError("one EKF pose and one slot per scan")
+        arr = (RgridBatchRangeData * max(len(range_datas), 1))()
+        keep = []
+        for i, (rd, pose, slot) in enumerate(zip(range_datas, ekf_poses, slots)):
+            ret = np.ascontiguousarray(rd.returns, dtype=np.float32).reshape(-1, 2)
+            mis = np.zeros((0, 2), np.float32) if rd.misses is None else np.ascontiguousarray(rd.misses, dtype=np.float32).reshape(-1, 2)
+            keep += [ret, mis]
+            s = arr[i]
+            s.grid, s.n_returns, s.n_misses = slot, ret.shape[0], mis.shape[0]
+            s.returns_xy = ret.ctypes.data if s.n_returns else None
+            s.misses_xy = mis.ctypes.data if s.n_misses else None
+            s.origin_xy[0], s.origin_xy[1] = float(rd.origin[0]), float(rd.origin[1])
+            s.ekf_pose[0], s.ekf_pose[1], s.ekf_pose[2] = float(pose[0]), float(pose[1]), float(pose[2])
+        return arr, len(range_datas), keep
+
+    def add_range_data_packed_code(self, packed, options=None, cap_points: int | None = None, want_returns: bool = True):
+        """``add_range_data_code`` for what ``pack_range_data`` returned.  ``cap_points`` (default: the sum of the counts) is the room
+        offered for the returns; without ``want_returns`` the raw returns are not transformed at all."""
+        L = _range_data_lib()
+        arr, count, _ = packed
+        n = max(count, 1)
+        co = _map_builder_options(options)
+        total = sum(arr[i].n_returns for i in range(count))
+        room = total if cap_points is None else int(cap_points)
+        codes, status, poses = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 3))
+        origins, out = np.zeros((n, 2), np.float32), np.zeros((max(room, total, 1), 2), np.float32)
+        rc = L.rgrid_batch_add_range_data(self._h, C.byref(co), C.cast(arr, C.c_void_p), count, codes.ctypes.data, status.ctypes.data,
+                                          poses.ctypes.data, origins.ctypes.data, out.ctypes.data if want_returns else None, room)
+        if rc != 0:
+            return rc, []
+        results, at = [], 0
+        for i in range(count):
+            k = arr[i].n_returns
+            results.append(FleetRangeDataResult(int(codes[i]), int(status[i]), poses[i].copy(), (float(origins[i, 0]), float(origins[i, 1])),
+                                                out[at:at + k].copy()))
+            at += k
+            if codes[i] == 0 and status[i] == SCAN_INSERTED:
+                self._set_slots.add(int(arr[i].grid))
+        return 0, results
+
+    def add_range_data_code(self, range_datas, ekf_poses, slots=None, options=None):
+        """-> (rc, [FleetRangeDataResult]): rc concerns the whole call (RGRID_ERR_INVALID, RGRID_ERR_BUFFER: nothing was launched),
+        a scan's own error is its result's ``code``."""
+        return self.add_range_data_packed_code(self.pack_range_data(range_datas, ekf_poses, slots), options)
+
+    def add_range_data(self, range_datas, ekf_poses, slots=None, options=None, times=None):
+        """``MapBuilder.AddRangeData`` for one scan of every robot in ONE call: per scan a ``map_builder.MatchingResult`` -- ``local_pose``
+        and ``range_data_in_local.returns`` the bits ``GridFrontEnd.AddRangeData`` returns for that robot; ``range_data_in_local``'s origin
+        and misses are not computed (None) -- or None where the reference returns nullptr (no returns, nothing left after the
+        filters).  A scan's own error raises RgridError after the whole call has run; ``add_range_data_code`` hands the codes out."""
+        from .map_builder import MatchingResult, RangeData
+        rc, results = self.add_range_data_code(range_datas, ekf_poses, slots, options)
+        self._chk(rc, "rgrid_batch_add_range_data")
+        for i, r in enumerate(results):
+            if r.code != 0:
+                raise self._error(r.code, f"rgrid_batch_add_range_data: scan {i}")
+        times = [None] * len(results) if times is None else list(times)
+        return [MatchingResult(t, r.local_pose, RangeData(None, r.returns_in_local, None)) if r.status == SCAN_INSERTED else None
+                for t, r in zip(times, results)]
+
+    def last_call_counts(self):
+        """(kernel launches, stream synchronisations) of the last ``add_range_data``: independent of the number of scans."""
+        out = (C.c_int * 2)()
+        self._chk(_range_data_lib().rgrid_batch_last_call_counts(self._h, C.cast(out, C.c_void_p)), "rgrid_batch_last_call_counts")
+        return int(out[0]), int(out[1])
 
     def GetLimits_code(self, slot: int):
         nx, ny = C.c_int(), C.c_int()

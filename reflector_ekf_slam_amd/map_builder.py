@@ -190,3 +190,95 @@ class MapBuilder:
     # introspection used by the tests
     def grid(self):
         return self._fe.GetGrid(), self._fe.GetLimits()
+
+
+class FleetMapBuilder:
+    """One mapping::MapBuilder per robot of a fleet, member m's submap in slot m of ONE ``fleet_match.ScanMatchFleet``: a tick of the
+    whole fleet is one ``AddRangeData`` -- one C call (rgrid_batch_add_range_data) whose launches and waits do not grow with the number
+    of robots -- and member m's results, map and counters are what a ``MapBuilder`` of its own would give for the same scans.  The host
+    keeps per member what MapBuilder keeps: ``num_range_data`` and the submap's origin.  ``fleet`` lets the caller hand in the handle
+    (anything with ScanMatchFleet's ``add_range_data_code``, ``GetLimits_code``, ``submap_textures`` and ``occupancy_grids``)."""
+
+    def __init__(self, num_robots: int, options: MapBuilderOptions | None = None, fleet=None, max_points: int = 8192,
+                 max_cells: int = 1024 * 1024, max_rotations: int = 256, device: int = 0):
+        self.options_ = options or MapBuilderOptions()
+        self.num_robots = int(num_robots)
+        if fleet is None:
+            from .fleet_match import ScanMatchFleet
+            fleet = ScanMatchFleet(max_scans=self.num_robots, max_points=max_points, num_grids=self.num_robots, max_cells=max_cells,
+                                   max_rotations=max_rotations, device=device)
+        self._fleet = fleet
+        self.num_range_data = [0] * self.num_robots
+        self._submap_origin = [None] * self.num_robots          # Submap2D local_pose translation of every member that has a submap
+        self.last_results = []
+
+    def _members(self, members, count=None):
+        members = list(range(self.num_robots if count is None else count)) if members is None else [int(m) for m in members]
+        if any(not 0 <= m < self.num_robots for m in members):
+            raise ValueError("a member is a number below num_robots")
+        return members
+
+    def submap_origin(self, member: int):
+        """The translation of member ``member``'s submap (x, y), None while it has none."""
+        return self._submap_origin[int(member)]
+
+    # MapBuilder::AddRangeData  (map_builder.cc:57-108) for one scan of every listed member
+    def AddRangeData(self, times, range_datas, ekf_poses, members=None):
+        """``range_datas[i]`` (tracking frame) and ``ekf_poses[i]`` belong to member ``members[i]`` (default: member i); a member is
+        listed at most once.  -> per scan a MatchingResult (``range_data_in_local`` carries the returns only) or None where the
+        reference returns nullptr.  A scan's own error raises after every member's bookkeeping is done."""
+        from .fleet_match import SCAN_INSERTED
+        from .grid import RgridError
+        range_datas, times = list(range_datas), list(times)
+        members = self._members(members, len(range_datas))
+        rc, results = self._fleet.add_range_data_code(range_datas, ekf_poses, members, self.options_)
+        if rc != 0:
+            raise RgridError(rc, "rgrid_batch_add_range_data")
+        self.last_results = results
+        out = []
+        for m, t, r in zip(members, times, results):
+            if self._submap_origin[m] is None and self._fleet.GetLimits_code(m)[0] == 0:     # this scan created the slot (CreateGrid)
+                self._submap_origin[m] = (float(r.origin_in_local[0]), float(r.origin_in_local[1]))
+            inserted = r.code == 0 and r.status == SCAN_INSERTED
+            self.num_range_data[m] += inserted                                               # Submap2D::InsertRangeData (submap_2d.cc:27-35)
+            out.append(MatchingResult(t, r.local_pose, RangeData(None, r.returns_in_local, None)) if inserted else None)
+        for i, r in enumerate(results):
+            if r.code != 0:
+                raise RgridError(r.code, f"rgrid_batch_add_range_data: member {members[i]}")
+        return out
+
+    def _with_submap(self, members):
+        members = self._members(members)
+        return members, [m for m in members if self._submap_origin[m] is not None]
+
+    def _spread(self, members, have, values):
+        at = dict(zip(have, values))
+        return [at.get(m) for m in members]
+
+    # MapBuilder::ToSubmapTexture  (map_builder.cc:128-134) of every listed member, one launch
+    def ToSubmapTextures(self, members=None):
+        """Per listed member (default: all) what ``MapBuilder.ToSubmapTexture`` returns: None without a submap."""
+        members, have = self._with_submap(members)
+        return self._spread(members, have, self._fleet.submap_textures(have, [self._submap_origin[m] for m in have]) if have else [])
+
+    # Node::PublishMap up to the message fields of every listed member, one launch
+    def OccupancyGrids(self, members=None, mode: int = OCCUPANCY):
+        """Per listed member (default: all) what ``MapBuilder.OccupancyGrid`` returns: None without a submap."""
+        members, have = self._with_submap(members)
+        return self._spread(members, have, self._fleet.occupancy_grids(have, [self._submap_origin[m] for m in have], mode) if have else [])
+
+    # Node::HandleSaveMap's grid map of one member
+    def SaveMap(self, member: int, filebase: str):
+        """Writes ``filebase``.pgm and ``filebase``.yaml with the reference's bytes; returns the two paths, None without a submap."""
+        image = self.OccupancyGrids([member], IMAGE)[0]
+        if image is None:
+            return None
+        pgm, yaml = filebase + ".pgm", filebase + ".yaml"
+        with open(pgm, "wb") as f:
+            f.write(pgm_bytes(image))
+        with open(yaml, "wb") as f:
+            f.write(yaml_bytes(image, pgm))
+        return pgm, yaml
+
+    def grid(self, member: int):
+        return self._fleet.GetGrid(member), self._fleet.GetLimits(member)
