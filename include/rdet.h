@@ -124,6 +124,20 @@ int rdet2d_batch_collect(rdet2d_batch_t *b, int *status, int *K, float *centers_
  * RDET_ERR_INVALID between submit and collect. */
 int rdet2d_batch_get_range_data(rdet2d_batch_t *b, int member, float origin_xy[2],
                                 float *returns_xy, int cap_points, int *n_returns);
+
+/* GetRangeData of any list of members in ONE launch and ONE synchronisation (members NULL = all B, in
+ * order; added without a new ABI version: look it up by name).  For every listed member counts[g],
+ * origins_xy[2 g ..] and its rows are the bits rdet2d_batch_get_range_data(b, members[g], ...) gives
+ * at that moment; the rows lie compactly in returns_xy, members[g]'s behind members[g-1]'s.
+ * counts is written on success and on RDET_ERR_BUFFER (cap_points below the sum of the counts: no row
+ * and no origin is touched, counts sizes the second call).  returns_xy NULL: counts and origins only,
+ * nothing is launched or waited for (cap_points is not looked at beyond its sign).  origins_xy may be
+ * NULL.  RDET_ERR_INVALID before any HIP call: a null handle, count < 0, null counts with count > 0,
+ * cap_points < 0, a member out of range or listed twice, members NULL with count != B, a submit that
+ * has not been collected.  count == 0 is RDET_OK and does nothing; a zero sum of counts launches
+ * nothing.  The handle's first launching call allocates B * max_beams points of pinned host memory. */
+int rdet2d_batch_get_range_data_all(rdet2d_batch_t *b, const int *members, int count, int *counts,
+                                    float *origins_xy, float *returns_xy, long cap_points);
 int rdet2d_batch_sizeof_scan(void);
 const char *rdet2d_batch_last_hip_error(rdet2d_batch_t *b);
 

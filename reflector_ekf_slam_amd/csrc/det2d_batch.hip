@@ -506,6 +506,55 @@ __global__ __launch_bounds__(1024) void k_det2d_batch(BatchBufs B)
     if (tid == 0) { out->K = K; out->n_returns = n_cloud; out->err = s_tot[2]; out->n_runs = n_runs; }
 }
 
+// ================================================================================================
+// GetRangeData of any list of members in ONE launch (rdet2d_batch_get_range_data_all): k_det2d_batch left member m's de-skewed
+// returns at returns[m * max_beams ...]; this kernel copies the rows of the listed members, one member's behind the other's, into
+// pinned host memory, which the end of the launch publishes.  The host knows every count (collect stored last_n_returns), so it
+// builds the records and a workgroup table (record, tile) as kgb_to_local's callers do: a workgroup is a tile of one member's rows,
+// no workgroup waits for another, there is no atomic and nothing to clear.
+//
+// A lane moves two points, 16 bytes.  The destination of a record is 16-byte aligned only when the counts in front of it sum to an
+// even number, so a record's pairs are laid on the DESTINATION's 16-byte grid: with lead = dst_off & 1, lane p of the record holds
+// the slots j = 2p and 2p + 1 of row i = j - lead; the one row in front of the first boundary and the one behind the last go as
+// 8-byte stores, every pair between them as one 16-byte store.  The load of a pair is one 16-byte load when the source is on the
+// same grid ((src_off + i) even), else two 8-byte loads: uniform over the record.  A member with n rows costs
+// ceil((n + lead) / RDET2DB_RANGE_TILE) workgroups, an empty one none.
+#define RDET2DB_RANGE_THREADS 256
+#define RDET2DB_RANGE_TILE (2 * RDET2DB_RANGE_THREADS)    // rows (slots) per workgroup
+
+struct RangeRec {
+    long long src_off;             // the member's first row in `returns` (member * max_beams)
+    long long dst_off;             // its first row in the output
+    int n, pad;
+};
+
+struct RangeBufs {
+    const RangeRec *recs;          // [records], pinned host memory
+    const int2 *wgmap;             // (record, tile) per workgroup, pinned host memory
+    const float2 *returns;         // k_det2d_batch's [B][max_beams]
+    float2 *out;                   // pinned host memory, [B * max_beams]
+};
+
+__global__ __launch_bounds__(RDET2DB_RANGE_THREADS) void k_det2d_batch_range_data(RangeBufs B)
+{
+    const int2 wg = B.wgmap[blockIdx.x];
+    const RangeRec R = B.recs[wg.x];
+    const int lead = (int)(R.dst_off & 1);
+    const int j0 = wg.y * RDET2DB_RANGE_TILE + 2 * (int)threadIdx.x, end = R.n + lead;      // slots [lead, end) hold rows
+    if (j0 >= end) return;
+    const int i0 = j0 - lead;                                                               // (-1 for the slot in front of the first row)
+    const float2 *__restrict__ src = B.returns + R.src_off;
+    float2 *__restrict__ dst = B.out + R.dst_off;
+    const bool lo = j0 >= lead, hi = j0 + 1 < end;
+    if (lo && hi) {
+        float4 v;
+        if (((R.src_off + i0) & 1) == 0) v = *reinterpret_cast<const float4 *>(src + i0);
+        else { const float2 a = src[i0], b = src[i0 + 1]; v = make_float4(a.x, a.y, b.x, b.y); }
+        *reinterpret_cast<float4 *>(dst + i0) = v;                                          // (dst_off + i0 = dst_off - lead + j0: even)
+    } else if (lo) dst[i0] = src[i0];
+    else if (hi) dst[i0 + 1] = src[i0 + 1];
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -543,6 +592,10 @@ struct rdet2d_batch {
     std::vector<int> sub_member, sub_status, sub_runs;
     std::vector<double> sub_stamp;
     std::vector<char> seen;
+    // rdet2d_batch_get_range_data_all, allocated by its first call that launches: the rows of a call, and its records with the
+    // workgroup table behind them
+    batch_host::Pinned<float2> rd_out;           // [B][max_beams]
+    batch_host::Pinned<unsigned char> rd_tab;    // RangeRec[B] | int2 [B * range_tiles]
     std::string hip_error;
 };
 
@@ -620,7 +673,7 @@ void rdet2d_batch_destroy(rdet2d_batch_t *b)
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     (void)hipFree(b->d_tables); (void)hipFree(b->d_contrib); (void)hipFree(b->d_returns);
     if (b->h_tables) (void)hipHostFree(b->h_tables);
-    b->stage.release(); b->recs.release(); b->out.release();
+    b->stage.release(); b->recs.release(); b->out.release(); b->rd_out.release(); b->rd_tab.release();
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -796,6 +849,72 @@ int rdet2d_batch_get_range_data(rdet2d_batch_t *b, int member, float origin_xy[2
                                   sizeof(float) * 2 * (size_t)M.last_n_returns, hipMemcpyDeviceToHost));
         }
     }
+    return RDET_OK;
+}
+
+int rdet2d_batch_get_range_data_all(rdet2d_batch_t *b, const int *members, int count, int *counts, float *origins_xy, float *returns_xy,
+                                    long cap_points)
+{
+    if (!b || count < 0 || (count > 0 && !counts) || cap_points < 0 || b->outstanding) return RDET_ERR_INVALID;
+    const int B = b->B;
+    if (!members && count != B) return RDET_ERR_INVALID;
+    if (members) {
+        if (count > B) return RDET_ERR_INVALID;                            // (more than B members: one is listed twice)
+        bool bad = false;
+        for (int g = 0; g < count && !bad; ++g) {
+            const int m = members[g];
+            if (m < 0 || m >= B || b->seen[(size_t)m]) bad = true;
+            else b->seen[(size_t)m] = 1;
+        }
+        for (int g = 0; g < count; ++g)
+            if (members[g] >= 0 && members[g] < B) b->seen[(size_t)members[g]] = 0;
+        if (bad) return RDET_ERR_INVALID;
+    }
+    if (count == 0) return RDET_OK;
+    const size_t mb = (size_t)b->max_beams;
+    long total = 0;
+    for (int g = 0; g < count; ++g) {
+        int n = b->m[(size_t)(members ? members[g] : g)].last_n_returns;
+        n = n < 0 ? 0 : (n > b->max_beams ? b->max_beams : n);             // (never true for a count k_det2d_batch wrote: keeps every access inside the buffers)
+        counts[g] = n;
+        total += n;
+    }
+    if (returns_xy && cap_points < total) return RDET_ERR_BUFFER;
+    if (origins_xy)
+        for (int g = 0; g < count; ++g) {
+            const rdet2d_batch_member &M = b->m[(size_t)(members ? members[g] : g)];
+            origins_xy[2 * g] = (float)M.s2b[0]; origins_xy[2 * g + 1] = (float)M.s2b[1];   // :243
+        }
+    if (!returns_xy || total == 0) return RDET_OK;
+    DETB_TRY(b, hipSetDevice(b->device));
+    const size_t tiles = (mb + 1 + RDET2DB_RANGE_TILE - 1) / RDET2DB_RANGE_TILE;            // of a member with max_beams rows behind an odd offset
+    const size_t wgmap_off = (sizeof(RangeRec) * (size_t)B + 255) / 256 * 256;
+    if (!b->rd_out.h) DETB_TRY(b, b->rd_out.alloc(mb * (size_t)B));
+    if (!b->rd_tab.h) DETB_TRY(b, b->rd_tab.alloc(wgmap_off + sizeof(int2) * tiles * (size_t)B));
+    RangeRec *recs = reinterpret_cast<RangeRec *>(b->rd_tab.h);
+    int2 *wgmap = reinterpret_cast<int2 *>(b->rd_tab.h + wgmap_off);
+    int nrec = 0, nwg = 0;
+    long long at = 0;
+    for (int g = 0; g < count; ++g) {
+        if (counts[g] == 0) continue;
+        RangeRec &R = recs[nrec];
+        R.src_off = (long long)(members ? members[g] : g) * (long long)mb;
+        R.dst_off = at;
+        R.n = counts[g]; R.pad = 0;
+        const int slots = counts[g] + (int)(at & 1);
+        for (int t = 0; t * RDET2DB_RANGE_TILE < slots; ++t) wgmap[nwg++] = make_int2(nrec, t);
+        at += counts[g];
+        ++nrec;
+    }
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // the records and the table are written before the doorbell
+    RangeBufs Rf;
+    Rf.recs = reinterpret_cast<const RangeRec *>(b->rd_tab.dv);
+    Rf.wgmap = reinterpret_cast<const int2 *>(b->rd_tab.dv + wgmap_off);
+    Rf.returns = b->d_returns; Rf.out = b->rd_out.dv;
+    hipLaunchKernelGGL(k_det2d_batch_range_data, dim3((unsigned)nwg), dim3(RDET2DB_RANGE_THREADS), 0, b->stream, Rf);
+    DETB_TRY(b, hipGetLastError());
+    DETB_TRY(b, hipStreamSynchronize(b->stream));
+    std::memcpy(returns_xy, b->rd_out.h, sizeof(float2) * (size_t)total);
     return RDET_OK;
 }
 

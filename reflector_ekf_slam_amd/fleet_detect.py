@@ -4,7 +4,8 @@ rdet3d_batch_* of include/rdet.h).
 ``LaserReflectorDetectFleet(options_list)`` holds B members, each a reflector_detect::LaserReflectorDetect with its own options,
 sensor_to_base_link and odometry.  ``submit(scans)`` takes at most one ``LaserScan`` per member and enqueues one launch of
 k_det2d_batch (one workgroup per scan); ``collect()`` waits and returns ``(status, Observation)`` per scan, in the order given.
-``scan_events`` turns a tick's result into the events ``ReflectorEKFSLAMFleet.submit`` takes.
+``scan_events`` turns a tick's result into the events ``ReflectorEKFSLAMFleet.submit`` takes; ``range_data(members)`` is GetRangeData
+of any list of members -- what ``FleetMapBuilder.AddRangeData`` takes -- from ONE launch of k_det2d_batch_range_data.
 
 ``PointCloudReflectorDetectFleet(options_list)`` is the same for reflector_detect::PointCloudReflectorDetect: ``submit(clouds)`` takes
 at most one cloud per member, ``(member, stamp, xyzi)`` or ``(member, PointCloud)``, and enqueues one launch of k_det3d_batch (one
@@ -63,6 +64,15 @@ def _declare_batch(L):
 
 
 _batch_lib = _lib.Feature(_rdet, "librdet.so", ("rdet2d_batch_create",), [("rdet2d_batch_sizeof_scan", Rdet2dScan)], _declare_batch)
+
+
+def _declare_range_data(L):
+    """``_batch_lib()`` with the argtypes of rdet2d_batch_get_range_data_all set.  It was added without a new ABI version and is
+    looked up by name: raises LibraryMissing when the built library has none; every other call keeps working then."""
+    L.rdet2d_batch_get_range_data_all.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+
+
+_range_data_lib = _lib.Feature(_batch_lib, "librdet.so", ("rdet2d_batch_get_range_data_all",), (), _declare_range_data)
 
 
 def _declare_batch3(L):
@@ -219,6 +229,37 @@ class LaserReflectorDetectFleet(_DetectFleet):
         self._chk(self._L.rdet2d_batch_get_range_data(self._h, int(member), C.addressof(origin), ret.ctypes.data, ret.shape[0], C.byref(n)),
                   "GetRangeData")
         return RangeData(np.array(origin[:], dtype=np.float32), ret[: n.value].copy())
+
+    def range_data_code(self, members=None):
+        """-> (rc, counts [len(members)], origins [len(members), 2], rows [sum of counts, 2]) of ONE
+        rdet2d_batch_get_range_data_all with room for ``max_beams`` rows per listed member (None = all, in order)."""
+        L = _range_data_lib()
+        if members is None:
+            mem, count = None, self.B
+        else:
+            mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+            count = mem.shape[0]
+        cap = count * self.max_beams
+        counts = np.zeros(max(count, 1), np.int32)
+        origins = np.zeros((max(count, 1), 2), np.float32)
+        rows = np.empty((max(cap, 1), 2), np.float32)
+        rc = L.rdet2d_batch_get_range_data_all(self._h, None if mem is None else mem.ctypes.data, count, counts.ctypes.data,
+                                               origins.ctypes.data, rows.ctypes.data, cap)
+        if rc != 0:
+            return rc, counts[:0], origins[:0], rows[:0]
+        counts = counts[:count]
+        return 0, counts, origins[:count], rows[: int(counts.sum())]
+
+    def range_data(self, members=None):
+        """``GetRangeData`` of the listed members (None = all, in order): a list of ``RangeData``, the bits ``GetRangeData(member)``
+        gives for each.  ONE launch (k_det2d_batch_range_data) and ONE synchronisation whatever the number of members."""
+        rc, counts, origins, rows = self.range_data_code(members)
+        self._chk(rc, "rdet2d_batch_get_range_data_all")
+        out, at = [], 0
+        for g, n in enumerate(counts.tolist()):
+            out.append(RangeData(origins[g].copy(), rows[at: at + n].copy()))
+            at += n
+        return out
 
     @staticmethod
     def pack(scans):

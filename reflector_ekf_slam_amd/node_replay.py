@@ -25,6 +25,10 @@ Messages are replayed in stamp order (ties: odometry first -- ros::spin() is sin
 
 The three components are injected (``Backend``): the default is the HIP path (detect.LaserReflectorDetect, ReflectorEKFSLAM,
 map_builder.MapBuilder); the GPU suite runs the same harness over the CPU oracle's components for comparison.
+
+``FleetNode`` is the same node for B robots over the three fleets (``FleetBackend``: LaserReflectorDetectFleet,
+ReflectorEKFSLAMFleet, map_builder.FleetMapBuilder): a ``tick`` hands every robot its odometry and its scan, with launches and
+synchronisations that do not grow with B.
 """
 from __future__ import annotations
 
@@ -217,4 +221,199 @@ class Node:
 def replay(dump: Dump, backend: Backend | None = None) -> Node:
     node = Node(dump.meta, backend or hip_backend())
     node.run(dump)
+    return node
+
+
+# ------------------------------------------------------------------------------------------------ the node of a fleet
+@dataclass
+class FleetBackend:
+    """Factories of the three fleets ``FleetNode`` owns: what ``Backend`` is to ``Node``."""
+    make_detector_fleet: object    # ([ReflectorDetectOptions], sensor_to_base_link [B, 3]) -> HandleOdometryData(member, msg) / submit / collect / range_data
+    make_filter_fleet: object      # ([EKFOptions]) -> set_state / set_map / submit / poses / n / marker_ellipses / save_map_txt
+    make_map_builder: object       # (B) -> AddRangeData(times, range_datas, poses, members) / OccupancyGrids / SaveMap
+
+
+def hip_fleet_backend(max_landmarks: int = 64, device: int = 0, max_beams: int = 8192, max_cells: int = 2048 * 2048,
+                      max_rotations: int = 1024) -> FleetBackend:
+    """The three HIP fleets.  ``max_rotations`` is the single handle's limit (rgrid_match: 1024): a lidar that sees 24 m needs about
+    255 rotated scans for the node's 15 degree window, one more than ScanMatchFleet's default of 256 a little beyond that."""
+    from .fleet import ReflectorEKFSLAMFleet
+    from .fleet_detect import LaserReflectorDetectFleet
+    from .map_builder import FleetMapBuilder, MapBuilderOptions
+    return FleetBackend(
+        make_detector_fleet=lambda opts, s2b: LaserReflectorDetectFleet(opts, max_beams=max_beams, device=device, sensor_to_base_link=s2b),
+        make_filter_fleet=lambda opts: ReflectorEKFSLAMFleet(opts, max_landmarks=max_landmarks, device=device),
+        make_map_builder=lambda B: FleetMapBuilder(B, MapBuilderOptions(), max_points=max_beams, max_cells=max_cells, max_rotations=max_rotations,
+                                                           device=device))
+
+
+@dataclass
+class FleetReplayLog:
+    """One member's part of a ``FleetNode``'s log."""
+    path: list = field(default_factory=list)                 # (stamp, x, y, theta) of every scan that saw reflectors (:524)
+    observations: list = field(default_factory=list)         # (obs time, centres) per processed scan
+    match_poses: list = field(default_factory=list)          # MatchingResult.local_pose per processed scan (or None)
+    match_results: list = field(default_factory=list)        # the MatchingResult itself (or None)
+    mapper_inputs: list = field(default_factory=list)        # (stamp, RangeData, (x, y, yaw)): exactly what the mapper was given
+    skipped: list = field(default_factory=list)              # (stamp, detector status) of every scan the detector refused
+
+
+class FleetNode:
+    """The reference's default-build ``Node`` (src/ros_node.cc:420-660) for B robots over the three fleets: member m is what a ``Node``
+    made from ``metas[m]`` is, and a ``tick`` gives every member the messages ``Node.OdometryCallback`` / ``Node.ScanCallback`` would
+    get -- its odometry in the order given, then its scan -- with a number of launches and synchronisations that does not grow with B:
+
+        odometry  -> the detector fleet always; an ``odom_event`` of the tick's ONE ``fleet.submit`` only for a member whose filter
+                     exists (:630-638)
+        a member's first scan only creates its filter: set_state(member, stamp, initial_pose, zeros, vt = 0); the scan itself is
+                     not processed (:424-441)
+        the other scans: detector submit / collect -> ``scan_events`` of the status-0 scans, with the odometry events, in ONE
+                     ``fleet.submit`` -> ``poses()`` -> ``range_data(members)`` -> ONE ``AddRangeData(stamps, range datas, poses,
+                     members)`` with the pose after the update (:546-552)
+
+    ``map_path`` of a meta is served by the filter fleet's ONE shared map (``load_map_txt`` -> ``set_map`` for the members that name
+    it): two different non-empty paths in one fleet raise ValueError.  A scan the detector refuses (status != 0) is logged in
+    ``skipped`` and left out for that member -- the reference exits there.  A scan with more than ``fleet.MAX_OBS`` centres raises
+    ValueError before anything is submitted to the filter: include/rfleet.h puts such scans out of scope.
+
+    OUT OF SCOPE: the USE_GPS ordering of ScanCallback (:450-508: predict, match, then the update with the pose fix);
+    PointCloudCallback; a pose log after every odometry message (``Node`` keeps one: a ``poses()`` per message would be a
+    synchronisation per message); a device-to-device route from the detector's returns into rgrid_batch_add_range_data (the range
+    data crosses the host once per tick, DESIGN.md 10.11 "not built")."""
+
+    def __init__(self, metas, backend: FleetBackend | None = None):
+        from .detect import ReflectorDetectOptions
+        from .ekf_slam import load_map_txt
+        self.metas = [dict(m) for m in metas]
+        self.B = len(self.metas)
+        self.backend = backend or hip_fleet_backend()
+        paths = sorted({m.get("map_path", "") for m in self.metas} - {""})
+        if len(paths) > 1:
+            raise ValueError(f"a fleet has one shared map; the metas name {len(paths)}: {paths}")
+        s2b = np.array([tuple(m.get("sensor_to_base_link", (0.0, 0.0, 0.0))) for m in self.metas], np.float64).reshape(self.B, 3)
+        self.detector = self.backend.make_detector_fleet([ReflectorDetectOptions(**m.get("detector", {})) for m in self.metas], s2b)
+        self.fleet = self.backend.make_filter_fleet([self._ekf_options(m) for m in self.metas])
+        self.map_builder = self.backend.make_map_builder(self.B)
+        if paths:
+            loaded = load_map_txt(paths[0])
+            if loaded.reflector_map_.shape[0] > 0:
+                self.fleet.set_map(loaded.reflector_map_, loaded.reflector_map_coviarance_,
+                                   [i for i, m in enumerate(self.metas) if m.get("map_path", "") == paths[0]])
+        self.has_filter = [False] * self.B
+        self.logs = [FleetReplayLog() for _ in range(self.B)]
+
+    @staticmethod
+    def _ekf_options(m):
+        from .ekf_slam import DIFF, OMNI, EKFOptions
+        return EKFOptions(use_imu=False, init_time=0.0, init_pose=tuple(m.get("initial_pose", (0.0, 0.0, 0.0))), map_path="",
+                          odom_model=DIFF if m.get("odom_model", "diff") == "diff" else OMNI,
+                          linear_velocity_cov=float(m["linear_velocity_sigma"]) ** 2,        # the node squares the launch sigmas
+                          angular_velocity_cov=float(m["angular_velocity_sigma"]) ** 2,      # (src/ros_node.cc:207-238)
+                          observation_cov=float(m["observation_sigma"]) ** 2)
+
+    def tick(self, odometry=(), scans=()):
+        """odometry = [(member, t, pose4, twist3), ...] (pose4 = position x, y, orientation z, w; twist3 = linear x, y, angular z);
+        scans = [(member, LaserScan), ...], at most one per member.  -> the members whose scan reached the mapper."""
+        from . import fleet as F
+        from .ekf_slam import OdometryData
+        from .fleet_detect import scan_events
+        from .map_builder import RangeData
+        scans = [(int(m), sc) for m, sc in scans]
+        listed = [m for m, _ in scans]
+        if len(set(listed)) != len(listed) or any(not 0 <= m < self.B for m in listed):
+            raise ValueError("at most one scan per member, and a member is a number below B")
+        events = []
+        for member, t, pose4, twist3 in odometry:                                            # src/ros_node.cc:627-660
+            member = int(member)
+            px, py, qz, qw = (float(v) for v in pose4)
+            vx, vy, wz = (float(v) for v in twist3)
+            self.detector.HandleOdometryData(member, OdometryData(float(t), (vx, vy, 0.0), (0.0, 0.0, wz), (px, py, 0.0), (qw, 0.0, 0.0, qz)))
+            if self.has_filter[member]:
+                events.append(F.odom_event(member, t, vx, vy, wz))
+        first = [(m, sc) for m, sc in scans if not self.has_filter[m]]
+        later = [(m, sc) for m, sc in scans if self.has_filter[m]]
+        kept = []
+        if later:
+            observations = self.detector.detect(later)
+            for (m, sc), (status, obs) in zip(later, observations):
+                if status != 0:
+                    self.logs[m].skipped.append((float(sc.stamp), int(status)))
+                elif obs.cloud_.shape[0] > F.MAX_OBS:
+                    raise ValueError(f"member {m}: {obs.cloud_.shape[0]} centres in one scan, the fleet filter takes {F.MAX_OBS}")
+                else:
+                    kept.append((m, sc, obs))
+            events += scan_events(later, observations)
+        if events:
+            self.fleet.submit(events)
+        for m, sc in first:                                                                  # :424-441: the first scan is not processed (Q11)
+            self.fleet.set_state(m, float(sc.stamp), np.array(self.metas[m].get("initial_pose", (0.0, 0.0, 0.0)), np.float64),
+                                 np.zeros((3, 3)), vt=np.zeros(3))
+            self.has_filter[m] = True
+        if not kept:
+            return []
+        members = [m for m, _, _ in kept]
+        _, mu, _ = self.fleet.poses()
+        range_datas = self.detector.range_data(members)
+        stamps = [float(sc.stamp) for _, sc, _ in kept]
+        poses = [(float(mu[m, 0]), float(mu[m, 1]), float(mu[m, 2])) for m in members]
+        rds = [RangeData(rd.origin, rd.returns, np.zeros((0, 2), np.float32)) for rd in range_datas]
+        results = self.map_builder.AddRangeData(stamps, rds, poses, members)
+        for (m, sc, obs), stamp, rd, pose, res in zip(kept, stamps, rds, poses, results):
+            log = self.logs[m]
+            log.observations.append((obs.time_, np.array(obs.cloud_, np.float32)))
+            if obs.cloud_.shape[0] > 0:                                                      # :524: publishes only with reflectors in view
+                log.path.append((stamp,) + pose)
+            log.mapper_inputs.append((stamp, rd, pose))
+            log.match_poses.append(None if res is None else np.array(res.local_pose))
+            log.match_results.append(res)
+        return members
+
+    # -- what the node hands out ------------------------------------------------------------------
+    def markers(self, members=None):
+        """ReflectorToRosMarkers' ellipses of the listed members (src/ros_node.cc:736-791), one launch."""
+        return self.fleet.marker_ellipses(members)
+
+    def occupancy_grids(self, members=None):
+        """Node::PublishMap's message fields of the listed members (None where a member has no submap), one launch."""
+        return self.map_builder.OccupancyGrids(members)
+
+    def SaveReflectorResult(self, member: int, filebase: str, reference_bytes: bool = True) -> str:   # src/ros_node.cc:75-140
+        if not self.has_filter[int(member)]:
+            return ""
+        path = filebase + ".txt"
+        self.fleet.save_map_txt(int(member), path, reference_bytes=reference_bytes)
+        return path
+
+    def SaveMap(self, member: int, filebase: str):                                           # src/ros_node.cc:947-1001
+        return self.map_builder.SaveMap(int(member), filebase)
+
+    def run(self, dumps, start_tick=None):
+        """Replays B ``rekf-dump-v1`` dumps: member m's k-th segment -- its odometry since its previous scan and its k-th scan -- goes
+        into tick ``start_tick[m] + k`` (default 0); odometry behind its last scan into the tick after it.  -> the logs."""
+        dumps = list(dumps)
+        if len(dumps) != self.B:
+            raise ValueError("one dump per member")
+        start = [0] * self.B if start_tick is None else [int(v) for v in start_tick]
+        ticks = {}
+        for m, d in enumerate(dumps):
+            k, od = start[m], []
+            for kind, i in d.events():
+                if kind == "odom":
+                    od.append((m, d.odom_t[i], d.odom_pose[i], d.odom_twist[i]))
+                else:
+                    ticks.setdefault(k, ([], []))
+                    ticks[k][0].extend(od)
+                    ticks[k][1].append((m, d.scan(i)))
+                    k, od = k + 1, []
+            if od:
+                ticks.setdefault(k, ([], []))[0].extend(od)
+        for k in sorted(ticks):
+            self.tick(*ticks[k])
+        return self.logs
+
+
+def replay_fleet(dumps, backend: FleetBackend | None = None, start_tick=None) -> FleetNode:
+    dumps = list(dumps)
+    node = FleetNode([d.meta for d in dumps], backend)
+    node.run(dumps, start_tick)
     return node
