@@ -1,6 +1,7 @@
-// batch_host.h -- the two kinds of buffer a fleet handle shares with the device.  Each knows how its memory was taken: what
-// alloc() took, release() gives back the same way, and release() of an empty buffer does nothing.  Plain aggregates: a handle
-// holds them by value and releases them when it is destroyed; nothing copies them.
+// batch_host.h -- the buffers a handle owns: the two kinds a fleet handle shares with the device (Pinned, Staging) and the two
+// that copies run between (Device, Host).  Each knows how its memory was taken: what alloc() took, release() gives back the same
+// way, and release() of an empty buffer does nothing.  Plain aggregates: a handle holds them by value and releases them when it is
+// destroyed; nothing copies them (two of a handle's buffers may change places: std::swap).
 #pragma once
 #include "host_visible.h"
 
@@ -47,6 +48,26 @@ struct Staging : Pinned<T> {
         else Pinned<T>::release();
     }
 };
+
+// n elements of device memory
+template <typename T>
+struct Device {
+    T *d = nullptr;
+    hipError_t alloc(size_t n) { const hipError_t e = hipMalloc((void **)&d, sizeof(T) * n); if (e != hipSuccess) d = nullptr; return e; }
+    void release() { if (d) (void)hipFree(d); d = nullptr; }
+};
+
+// n elements of pinned host memory taken with the default flags (neither mapped nor coherent): one end of a copy, never a kernel's argument
+template <typename T>
+struct Host {
+    T *h = nullptr;
+    hipError_t alloc(size_t n) { const hipError_t e = hipHostMalloc((void **)&h, sizeof(T) * n, hipHostMallocDefault); if (e != hipSuccess) h = nullptr; return e; }
+    void release() { if (h) (void)hipHostFree(h); h = nullptr; }
+};
+
+// release() of every buffer named: what a handle's destroy calls
+template <typename... B>
+void release_all(B &...b) { (b.release(), ...); }
 
 }  // namespace
 }  // namespace batch_host

@@ -17,7 +17,9 @@
 // shares its voxel: all-pairs, the candidates arrive through the scalar cache), kg_compact (order-preserving
 // ballot-scan compaction; also the range gate of the adaptive filter).  The bisection over voxel sizes of the
 // adaptive filter (:47-73) stays on the host: a dozen dependent decisions on one integer each.
+// The host steps this handle has in common with the fleet handle (rgrid_batch.hip) are rgrid_dev.h's, one text for both.
 #include "../../include/rgrid.h"
+#include "batch_host.h"
 #include "rgrid_dev.h"
 #include "rgrid_refine_dev.h"
 
@@ -34,14 +36,20 @@
 namespace {
 
 // ---- voxel filter -----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void kg_keys(const float *__restrict__ xy, int n, float res, int2 *__restrict__ key,
-                                               unsigned char *__restrict__ keep)
+// The voxel of point i = blockIdx.x * 256 + threadIdx.x and its flag in slice `slice` of key / keep: the body of kg_keys (one slice) and kg_keys_b
+__device__ static inline void voxel_keys(const float *__restrict__ xy, int n, float res, size_t slice, int2 *__restrict__ key, unsigned char *__restrict__ keep)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     // GetCellIndex (voxel_filter.cc:105-110): RoundToInt(point / resolution), float division, lround
-    key[i] = make_int2((int)lroundf(xy[2 * i] / res), (int)lroundf(xy[2 * i + 1] / res));
-    keep[i] = 1;                                                       // kg_first clears it when an earlier point shares the voxel
+    key[slice + i] = make_int2((int)lroundf(xy[2 * i] / res), (int)lroundf(xy[2 * i + 1] / res));
+    keep[slice + i] = 1;                                               // kg_first clears it when an earlier point shares the voxel
+}
+
+__global__ __launch_bounds__(256) void kg_keys(const float *__restrict__ xy, int n, float res, int2 *__restrict__ key,
+                                               unsigned char *__restrict__ keep)
+{
+    voxel_keys(xy, n, res, 0, key, keep);
 }
 
 // Workgroup (bi, bj), bj <= bi: the 256 points i of block bi against the 256 candidates j of block bj (j < i).
@@ -73,11 +81,8 @@ struct VoxBatch { int r; float res[VOX_BATCH]; };
 __global__ __launch_bounds__(256) void kg_keys_b(const float *__restrict__ xy, int n, VoxBatch B, int2 *__restrict__ key,
                                                  unsigned char *__restrict__ keep)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
-    if (i >= n) return;
-    const float res = B.res[r];
-    key[(size_t)r * n + i] = make_int2((int)lroundf(xy[2 * i] / res), (int)lroundf(xy[2 * i + 1] / res));
-    keep[(size_t)r * n + i] = 1;
+    const int r = blockIdx.y;
+    voxel_keys(xy, n, B.res[r], (size_t)r * n, key, keep);
 }
 __global__ __launch_bounds__(256) void kg_first_b(const int2 *__restrict__ key_all, int n, unsigned char *__restrict__ keep_all)
 {
@@ -472,38 +477,33 @@ __global__ __launch_bounds__(256) void kg_occupancy(const unsigned short *__rest
 
 }  // namespace
 
+using batch_host::Device;
+using batch_host::Host;
+
+// The buffers are batch_host.h's aggregates (Host: pinned, default flags): rgrid_create allocates them, rgrid_destroy releases every one.
 struct rgrid {
-    int max_points, max_cells, max_candidates, device;
-    hipStream_t stream;
-    float *d_in, *d_a, *d_b, *d_cs;       // points in / two result buffers / per-scan (cos, sin)
-    int2 *d_key, *d_idx;
-    int2 *d_key_b;                              // VOX_BATCH key slices (adaptive filter search)
-    unsigned char *d_keep_b;                    // VOX_BATCH + 1 flag slices (the last one parks the current result)
-    int *d_counts, *h_counts;
-    unsigned char *d_keep;
-    unsigned short *d_cells, *d_hit, *d_miss;   // grid; hit / miss lookup tables (uint16[32768])
-    unsigned short *d_cells2;                   // second grid buffer: target of a growth (then swapped with d_cells), texture staging
-    unsigned short *d_tex;                      // (value, alpha) table of the texture export, built on first use
-    int *d_box, *h_box;
-    unsigned char *d_occ_tables;                // the occupancy grid's two byte tables (occupancy, then red), built on first use
-    unsigned char *d_occ;                       // ... and its interior block on the device, occ_bytes long, grown when a grid needs more
-    size_t occ_bytes;
-    std::vector<unsigned char> h_occ;           // the block on the host
-    float *d_mis;                               // misses of an insertion
-    int2 *d_ends;
-    int *d_bad;
-    float tab_hit_p, tab_miss_p;                // probabilities the resident tables were built for
-    BestRec *d_bb, *d_best;
-    int *d_count;
-    // pinned staging
-    float *h_pts;
-    int *h_count;
-    BestRec *h_best;
-    RefineOut *d_refine, *h_refine;
-    // grid
-    int nx, ny;
-    double resolution, max_x, max_y;
-    bool have_grid;
+    int max_points = 0, max_cells = 0, max_candidates = 0, device = 0;
+    hipStream_t stream = nullptr;
+    Device<float> d_in, d_a, d_b, d_cs, d_mis;        // points in / two result buffers / per-scan (cos, sin) / misses of an insertion
+    Host<float> h_pts;
+    Device<int2> d_key, d_idx, d_ends, d_key_b;       // d_key_b: VOX_BATCH key slices (adaptive filter search)
+    Device<unsigned char> d_keep, d_keep_b;           // d_keep_b: VOX_BATCH + 1 flag slices (the last one parks the current result)
+    Device<int> d_counts, d_count, d_bad, d_box;
+    Host<int> h_counts, h_count, h_box;
+    Device<unsigned short> d_cells, d_hit, d_miss;    // grid; hit / miss lookup tables (uint16[32768])
+    Device<unsigned short> d_cells2, d_tex;           // target of a growth (then swapped with d_cells) and texture staging; the texture's table
+    Device<unsigned char> d_occ_tables;               // the occupancy grid's two byte tables (occupancy, then red), built on first use
+    Device<unsigned char> d_occ;                      // ... and its interior block on the device, occ_bytes long, grown when a grid needs more
+    size_t occ_bytes = 0;
+    std::vector<unsigned char> h_occ;                 // the block on the host
+    float tab_hit_p = -1.f, tab_miss_p = -1.f;        // probabilities the resident tables were built for
+    Device<BestRec> d_bb, d_best;
+    Host<BestRec> h_best;
+    Device<RefineOut> d_refine;
+    Host<RefineOut> h_refine;
+    int nx = 0, ny = 0;                               // the grid
+    double resolution = 0., max_x = 0., max_y = 0.;
+    bool have_grid = false;
     std::string hip_error;
 };
 
@@ -514,12 +514,12 @@ int voxel_pass(rgrid_t *h, const float *src, int n, float res, float *dst, int *
 {
     if (n == 0) { *m = 0; return RGRID_OK; }
     const int blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(kg_keys, dim3(blocks), dim3(256), 0, h->stream, src, n, res, h->d_key, h->d_keep);
-    hipLaunchKernelGGL(kg_first, dim3(blocks, blocks), dim3(256), 0, h->stream, h->d_key, n, h->d_keep);
-    hipLaunchKernelGGL(kg_compact, dim3(1), dim3(1024), 0, h->stream, src, h->d_keep, n, dst, h->d_count);
-    G_TRY(h, hipMemcpyAsync(h->h_count, h->d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    hipLaunchKernelGGL(kg_keys, dim3(blocks), dim3(256), 0, h->stream, src, n, res, h->d_key.d, h->d_keep.d);
+    hipLaunchKernelGGL(kg_first, dim3(blocks, blocks), dim3(256), 0, h->stream, h->d_key.d, n, h->d_keep.d);
+    hipLaunchKernelGGL(kg_compact, dim3(1), dim3(1024), 0, h->stream, src, h->d_keep.d, n, dst, h->d_count.d);
+    G_TRY(h, hipMemcpyAsync(h->h_count.h, h->d_count.d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
-    *m = *h->h_count;
+    *m = *h->h_count.h;
     return RGRID_OK;
 }
 
@@ -531,19 +531,19 @@ int voxel_counts(rgrid_t *h, const float *src, int n, const float *res, int R, i
     B.r = R;
     for (int r = 0; r < R; ++r) B.res[r] = res[r];
     const int blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(kg_keys_b, dim3(blocks, R), dim3(256), 0, h->stream, src, n, B, h->d_key_b, h->d_keep_b);
-    hipLaunchKernelGGL(kg_first_b, dim3(blocks, blocks, R), dim3(256), 0, h->stream, h->d_key_b, n, h->d_keep_b);
-    hipLaunchKernelGGL(kg_count_b, dim3(R), dim3(256), 0, h->stream, h->d_keep_b, n, h->d_counts);
-    G_TRY(h, hipMemcpyAsync(h->h_counts, h->d_counts, sizeof(int) * R, hipMemcpyDeviceToHost, h->stream));
+    hipLaunchKernelGGL(kg_keys_b, dim3(blocks, R), dim3(256), 0, h->stream, src, n, B, h->d_key_b.d, h->d_keep_b.d);
+    hipLaunchKernelGGL(kg_first_b, dim3(blocks, blocks, R), dim3(256), 0, h->stream, h->d_key_b.d, n, h->d_keep_b.d);
+    hipLaunchKernelGGL(kg_count_b, dim3(R), dim3(256), 0, h->stream, h->d_keep_b.d, n, h->d_counts.d);
+    G_TRY(h, hipMemcpyAsync(h->h_counts.h, h->d_counts.d, sizeof(int) * R, hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
-    for (int r = 0; r < R; ++r) counts[r] = h->h_counts[r];
+    for (int r = 0; r < R; ++r) counts[r] = h->h_counts.h[r];
     return RGRID_OK;
 }
 
 int upload_points(rgrid_t *h, const float *xy, int n)
 {
-    std::memcpy(h->h_pts, xy, sizeof(float) * 2 * (size_t)n);
-    G_TRY(h, hipMemcpyAsync(h->d_in, h->h_pts, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    std::memcpy(h->h_pts.h, xy, sizeof(float) * 2 * (size_t)n);
+    G_TRY(h, hipMemcpyAsync(h->d_in.d, h->h_pts.h, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
     return RGRID_OK;
 }
 
@@ -551,10 +551,22 @@ int download_points(rgrid_t *h, const float *d_src, int m, float *out_xy, int ou
 {
     if (m > out_cap) return RGRID_ERR_BUFFER;
     if (m > 0) {
-        G_TRY(h, hipMemcpyAsync(h->h_pts, d_src, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToHost, h->stream));
+        G_TRY(h, hipMemcpyAsync(h->h_pts.h, d_src, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToHost, h->stream));
         G_TRY(h, hipStreamSynchronize(h->stream));
-        std::memcpy(out_xy, h->h_pts, sizeof(float) * 2 * (size_t)m);
+        std::memcpy(out_xy, h->h_pts.h, sizeof(float) * 2 * (size_t)m);
     }
+    return RGRID_OK;
+}
+
+// Grid2D::ComputeCroppedLimits of the resident grid: kg_known_box and its round trip, box = (offset_x, offset_y, width, height)
+int known_box(rgrid_t *h, int box[4])
+{
+    h->h_box.h[0] = h->h_box.h[1] = INT_MAX; h->h_box.h[2] = h->h_box.h[3] = -1;
+    G_TRY(h, hipMemcpyAsync(h->d_box.d, h->h_box.h, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(kg_known_box, dim3((h->nx + 255) / 256, h->ny), dim3(256), 0, h->stream, h->d_cells.d, h->nx, h->ny, h->d_box.d);
+    G_TRY(h, hipMemcpyAsync(h->h_box.h, h->d_box.d, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    G_TRY(h, hipStreamSynchronize(h->stream));
+    box_of_known(h->h_box.h, box);
     return RGRID_OK;
 }
 
@@ -568,27 +580,15 @@ int rgrid_draw_texture(rgrid_t *h, uint8_t *cells, long cap, int box[4], double 
 {
     if (!h || !cells || !box || !slice_max || !h->have_grid) return RGRID_ERR_INVALID;
     G_TRY(h, hipSetDevice(h->device));
-    if (!h->d_tex) {
-        std::vector<unsigned short> t(32768);
-        texture_table(t.data());
-        G_TRY(h, hipMalloc(&h->d_tex, 2 * 32768));
-        G_TRY(h, hipMemcpy(h->d_tex, t.data(), 2 * 32768, hipMemcpyHostToDevice));
-    }
-    h->h_box[0] = h->h_box[1] = INT_MAX; h->h_box[2] = h->h_box[3] = -1;
-    G_TRY(h, hipMemcpyAsync(h->d_box, h->h_box, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(kg_known_box, dim3((h->nx + 255) / 256, h->ny), dim3(256), 0, h->stream, h->d_cells, h->nx, h->ny, h->d_box);
-    G_TRY(h, hipMemcpyAsync(h->h_box, h->d_box, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    G_TRY(h, hipStreamSynchronize(h->stream));
-    int x0 = h->h_box[0], y0 = h->h_box[1], x1 = h->h_box[2], y1 = h->h_box[3];
-    if (x1 < 0) { x0 = y0 = 0; x1 = y1 = 0; }                                     // nothing known: offset 0, CellLimits(1, 1) (grid_2d.cc:39-44)
-    const int w = x1 - x0 + 1, hh = y1 - y0 + 1;
-    box[0] = x0; box[1] = y0; box[2] = w; box[3] = hh;
-    slice_max[0] = h->max_x - h->resolution * y0;                                // (:122-123)
-    slice_max[1] = h->max_y - h->resolution * x0;
+    G_TRY(h, resident_texture_table(h->d_tex.d));
+    const int rc = known_box(h, box);
+    if (rc != RGRID_OK) return rc;
+    const int x0 = box[0], y0 = box[1], w = box[2], hh = box[3];
+    slice_max_of(box, h->resolution, h->max_x, h->max_y, slice_max);
     if (2l * w * hh > cap) return RGRID_ERR_BUFFER;
-    hipLaunchKernelGGL(kg_texture, dim3((w + 255) / 256, hh), dim3(256), 0, h->stream, h->d_cells, h->nx, x0, y0, w, h->d_tex, h->d_cells2);
+    hipLaunchKernelGGL(kg_texture, dim3((w + 255) / 256, hh), dim3(256), 0, h->stream, h->d_cells.d, h->nx, x0, y0, w, h->d_tex.d, h->d_cells2.d);
     G_TRY(h, hipGetLastError());
-    G_TRY(h, hipMemcpyAsync(cells, h->d_cells2, 2 * (size_t)w * hh, hipMemcpyDeviceToHost, h->stream));
+    G_TRY(h, hipMemcpyAsync(cells, h->d_cells2.d, 2 * (size_t)w * hh, hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
     return RGRID_OK;
 }
@@ -598,43 +598,30 @@ int rgrid_occupancy_grid(rgrid_t *h, int mode, const double submap_origin[2], in
     if (!h || !submap_origin || !out || !size || !origin || !box || !h->have_grid || (mode != OCC_MODE_OCCUPANCY && mode != OCC_MODE_IMAGE))
         return RGRID_ERR_INVALID;
     G_TRY(h, hipSetDevice(h->device));
-    if (!h->d_occ_tables) {
-        std::vector<unsigned char> t(2 * 32768);
-        occupancy_tables(reinterpret_cast<signed char *>(t.data()), t.data() + 32768);
-        unsigned char *d = nullptr;
-        G_TRY(h, hipMalloc(&d, 2 * 32768));
-        if (hipMemcpy(d, t.data(), 2 * 32768, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); h->hip_error = "occupancy tables: upload failed"; return RGRID_ERR_HIP; }
-        h->d_occ_tables = d;
-    }
+    G_TRY(h, resident_occupancy_tables(h->d_occ_tables.d));
     const size_t need = occupancy_block_bytes(h->nx, h->ny);
     if (need > h->occ_bytes) {
-        (void)hipFree(h->d_occ);
-        h->d_occ = nullptr; h->occ_bytes = 0;
-        G_TRY(h, hipMalloc(&h->d_occ, need));
+        h->d_occ.release();
+        h->occ_bytes = 0;
+        G_TRY(h, h->d_occ.alloc(need));
         h->occ_bytes = need;
     }
-    h->h_box[0] = h->h_box[1] = INT_MAX; h->h_box[2] = h->h_box[3] = -1;
-    G_TRY(h, hipMemcpyAsync(h->d_box, h->h_box, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(kg_known_box, dim3((h->nx + 255) / 256, h->ny), dim3(256), 0, h->stream, h->d_cells, h->nx, h->ny, h->d_box);
-    G_TRY(h, hipMemcpyAsync(h->h_box, h->d_box, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    G_TRY(h, hipStreamSynchronize(h->stream));
-    int x0 = h->h_box[0], y0 = h->h_box[1], x1 = h->h_box[2], y1 = h->h_box[3];
-    if (x1 < 0) { x0 = y0 = 0; x1 = y1 = 0; }                                     // nothing known: offset 0, CellLimits(1, 1) (grid_2d.cc:39-44)
-    const int w = x1 - x0 + 1, hh = y1 - y0 + 1;
-    box[0] = x0; box[1] = y0; box[2] = w; box[3] = hh;
+    int rc = known_box(h, box);
+    if (rc != RGRID_OK) return rc;
+    const int x0 = box[0], y0 = box[1], w = box[2], hh = box[3];
     OccupancyFrame F;
-    const int rc = occupancy_frame(box, h->resolution, h->max_x, h->max_y, submap_origin, &F);
+    rc = occupancy_frame(box, h->resolution, h->max_x, h->max_y, submap_origin, &F);
     if (rc != RGRID_OK) return rc;                                                // outside the domain: no image
     size[0] = F.size[0]; size[1] = F.size[1]; origin[0] = F.origin[0]; origin[1] = F.origin[1];
     if ((long)F.size[0] * F.size[1] > cap) return RGRID_ERR_BUFFER;
     const int stride = occupancy_stride(hh);
     const int tiles = ((w + OCC_T - 1) / OCC_T) * ((stride + OCC_T - 1) / OCC_T);
-    hipLaunchKernelGGL(kg_occupancy, dim3((unsigned)(tiles < 65536 ? tiles : 65536)), dim3(256), 0, h->stream, h->d_cells, h->nx, x0, y0, w, hh,
-                       h->d_occ_tables + (mode == OCC_MODE_IMAGE ? 32768 : 0), h->d_occ);
+    hipLaunchKernelGGL(kg_occupancy, dim3((unsigned)(tiles < 65536 ? tiles : 65536)), dim3(256), 0, h->stream, h->d_cells.d, h->nx, x0, y0, w, hh,
+                       h->d_occ_tables.d + (mode == OCC_MODE_IMAGE ? 32768 : 0), h->d_occ.d);
     G_TRY(h, hipGetLastError());
     const size_t bytes = (size_t)stride * (size_t)w;
     if (h->h_occ.size() < bytes) h->h_occ.resize(bytes);
-    G_TRY(h, hipMemcpyAsync(h->h_occ.data(), h->d_occ, bytes, hipMemcpyDeviceToHost, h->stream));
+    G_TRY(h, hipMemcpyAsync(h->h_occ.data(), h->d_occ.d, bytes, hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
     occupancy_paint(mode, h->h_occ.data(), w, hh, F.size, reinterpret_cast<unsigned char *>(out));
     return RGRID_OK;
@@ -644,29 +631,23 @@ int rgrid_refine_match(rgrid_t *h, const rgrid_refine_options *opt, const double
                        const float *points_xy, int n, double pose_estimate[3], rgrid_refine_summary *summary)
 {
     if (!h || !opt || !target_translation || !initial_pose || !pose_estimate || n < 0 || (n > 0 && !points_xy)) return RGRID_ERR_INVALID;
-    if (!h->have_grid || !(opt->occupied_space_weight > 0.) || !(opt->translation_weight > 0.) || !(opt->rotation_weight > 0.) ||
-        opt->max_num_iterations < 0)
-        return RGRID_ERR_INVALID;                                                // the reference CHECK_GTs the weights (ceres_scan_matcher_2d.cc:37,47,52)
+    if (!h->have_grid || !refine_options_ok(opt)) return RGRID_ERR_INVALID;
     if (n == 0) return RGRID_ERR_EMPTY;
     if (n > h->max_points) return RGRID_ERR_CAPACITY;
     G_TRY(h, hipSetDevice(h->device));
-    std::memcpy(h->h_pts, points_xy, sizeof(float) * 2 * (size_t)n);
-    G_TRY(h, hipMemcpyAsync(h->d_in, h->h_pts, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if (upload_points(h, points_xy, n) != RGRID_OK) return RGRID_ERR_HIP;
     RefineArgs A;
-    A.nx = h->nx; A.ny = h->ny; A.n = n; A.max_iter = opt->max_num_iterations; A.max_nonmono = opt->use_nonmonotonic_steps ? 5 : 0;
-    A.res = h->resolution; A.max_x = h->max_x; A.max_y = h->max_y;
-    A.w_occ = opt->occupied_space_weight; A.w_t = opt->translation_weight; A.w_r = opt->rotation_weight;
+    refine_args(A, h->nx, h->ny, h->resolution, h->max_x, h->max_y, opt, n);
     A.tx = target_translation[0]; A.ty = target_translation[1];
     A.x0 = initial_pose[0]; A.y0 = initial_pose[1]; A.a0 = initial_pose[2];
-    const int threads = std::min(1024, ((n + 63) / 64) * 64);                      // no idle waves in the barriers and the partial sums
-    hipLaunchKernelGGL(kg_refine, dim3(1), dim3(threads), 0, h->stream, A, h->d_cells, h->d_in, h->d_refine);
+    hipLaunchKernelGGL(kg_refine, dim3(1), dim3(refine_threads(n)), 0, h->stream, A, h->d_cells.d, h->d_in.d, h->d_refine.d);
     G_TRY(h, hipGetLastError());
-    G_TRY(h, hipMemcpyAsync(h->h_refine, h->d_refine, sizeof(RefineOut), hipMemcpyDeviceToHost, h->stream));
+    G_TRY(h, hipMemcpyAsync(h->h_refine.h, h->d_refine.d, sizeof(RefineOut), hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
-    pose_estimate[0] = h->h_refine->pose[0]; pose_estimate[1] = h->h_refine->pose[1]; pose_estimate[2] = h->h_refine->pose[2];
+    pose_estimate[0] = h->h_refine.h->pose[0]; pose_estimate[1] = h->h_refine.h->pose[1]; pose_estimate[2] = h->h_refine.h->pose[2];
     if (summary) {
-        summary->initial_cost = h->h_refine->initial_cost; summary->final_cost = h->h_refine->final_cost;
-        summary->iterations = h->h_refine->iterations; summary->termination = h->h_refine->termination;
+        summary->initial_cost = h->h_refine.h->initial_cost; summary->final_cost = h->h_refine.h->final_cost;
+        summary->iterations = h->h_refine.h->iterations; summary->termination = h->h_refine.h->termination;
     }
     return RGRID_OK;
 }
@@ -674,7 +655,7 @@ int rgrid_refine_match(rgrid_t *h, const rgrid_refine_options *opt, const double
 #ifdef RGRID_DEBUG_TIMING
 int rgrid_debug_refine_cycles(rgrid_t *h, long long out[16])
 {
-    for (int k = 0; k < 16; ++k) out[k] = h->h_refine->dbg[k];
+    for (int k = 0; k < 16; ++k) out[k] = h->h_refine.h->dbg[k];
     return RGRID_OK;
 }
 #endif
@@ -701,30 +682,26 @@ int rgrid_create(int max_points, int max_cells, int max_candidates, int device, 
     rgrid_t *h = new (std::nothrow) rgrid();
     if (!h) return RGRID_ERR_INVALID;
     h->max_points = max_points; h->max_cells = max_cells; h->max_candidates = max_candidates; h->device = device;
-    h->have_grid = false;
-    h->tab_hit_p = h->tab_miss_p = -1.f;
     const size_t np = (size_t)max_points;
     // discretised scans: every candidate's scan must fit: num_scans <= max_candidates, num_scans * n <= np * scans_cap
     int rc = [&]() -> int {
         G_TRY(h, hipSetDevice(device));
         G_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        G_TRY(h, hipMalloc(&h->d_in, 8 * np)); G_TRY(h, hipMalloc(&h->d_a, 8 * np)); G_TRY(h, hipMalloc(&h->d_b, 8 * np));
-        G_TRY(h, hipMalloc(&h->d_key, 8 * np + 64)); G_TRY(h, hipMemset(h->d_key, 0, 8 * np + 64)); G_TRY(h, hipMalloc(&h->d_keep, np));   // + one read-ahead group
-        G_TRY(h, hipMalloc(&h->d_key_b, 8 * np * VOX_BATCH + 64)); G_TRY(h, hipMemset(h->d_key_b, 0, 8 * np * VOX_BATCH + 64)); G_TRY(h, hipMalloc(&h->d_keep_b, np * (VOX_BATCH + 1)));
-        G_TRY(h, hipMalloc(&h->d_counts, sizeof(int) * VOX_BATCH)); G_TRY(h, hipHostMalloc(&h->h_counts, sizeof(int) * VOX_BATCH));
-        G_TRY(h, hipMalloc(&h->d_cs, 8 * (size_t)max_candidates));
-        G_TRY(h, hipMalloc(&h->d_idx, 8 * (np * 1024 + 64)));                // up to 1024 rotated scans of max_points points (+ read-ahead pad)
-        G_TRY(h, hipMemset(h->d_idx, 0, 8 * (np * 1024 + 64)));
-        G_TRY(h, hipMalloc(&h->d_cells, 2 * (size_t)max_cells)); G_TRY(h, hipMalloc(&h->d_cells2, 2 * (size_t)max_cells));
-        G_TRY(h, hipMalloc(&h->d_hit, 2 * 32768)); G_TRY(h, hipMalloc(&h->d_miss, 2 * 32768));
-        G_TRY(h, hipMalloc(&h->d_mis, 8 * np)); G_TRY(h, hipMalloc(&h->d_ends, 8 * (2 * np + 1))); G_TRY(h, hipMalloc(&h->d_bad, sizeof(int)));
-        G_TRY(h, hipMalloc(&h->d_bb, sizeof(BestRec) * 1024));                   // one record per rotated scan
-        G_TRY(h, hipMalloc(&h->d_best, sizeof(BestRec)));
-        G_TRY(h, hipMalloc(&h->d_count, sizeof(int)));
-        G_TRY(h, hipHostMalloc(&h->h_pts, 8 * np)); G_TRY(h, hipHostMalloc(&h->h_count, sizeof(int)));
-        G_TRY(h, hipHostMalloc(&h->h_best, sizeof(BestRec)));
-        G_TRY(h, hipMalloc(&h->d_box, 4 * sizeof(int))); G_TRY(h, hipHostMalloc(&h->h_box, 4 * sizeof(int)));
-        G_TRY(h, hipMalloc(&h->d_refine, sizeof(RefineOut))); G_TRY(h, hipHostMalloc(&h->h_refine, sizeof(RefineOut)));
+        G_TRY(h, h->d_in.alloc(2 * np)); G_TRY(h, h->d_a.alloc(2 * np)); G_TRY(h, h->d_b.alloc(2 * np));
+        G_TRY(h, h->d_key.alloc(np + 8)); G_TRY(h, hipMemset(h->d_key.d, 0, 8 * np + 64)); G_TRY(h, h->d_keep.alloc(np));   // + one read-ahead group (64 bytes)
+        G_TRY(h, h->d_key_b.alloc(np * VOX_BATCH + 8)); G_TRY(h, hipMemset(h->d_key_b.d, 0, 8 * np * VOX_BATCH + 64)); G_TRY(h, h->d_keep_b.alloc(np * (VOX_BATCH + 1)));
+        G_TRY(h, h->d_counts.alloc(VOX_BATCH)); G_TRY(h, h->h_counts.alloc(VOX_BATCH));
+        G_TRY(h, h->d_cs.alloc(2 * (size_t)max_candidates));
+        G_TRY(h, h->d_idx.alloc(np * 1024 + 64));                                // up to 1024 rotated scans of max_points points (+ read-ahead pad)
+        G_TRY(h, hipMemset(h->d_idx.d, 0, 8 * (np * 1024 + 64)));
+        G_TRY(h, h->d_cells.alloc((size_t)max_cells)); G_TRY(h, h->d_cells2.alloc((size_t)max_cells));
+        G_TRY(h, h->d_hit.alloc(32768)); G_TRY(h, h->d_miss.alloc(32768));
+        G_TRY(h, h->d_mis.alloc(2 * np)); G_TRY(h, h->d_ends.alloc(2 * np + 1)); G_TRY(h, h->d_bad.alloc(1));
+        G_TRY(h, h->d_bb.alloc(1024));                                           // one record per rotated scan
+        G_TRY(h, h->d_best.alloc(1)); G_TRY(h, h->d_count.alloc(1));
+        G_TRY(h, h->h_pts.alloc(2 * np)); G_TRY(h, h->h_count.alloc(1)); G_TRY(h, h->h_best.alloc(1));
+        G_TRY(h, h->d_box.alloc(4)); G_TRY(h, h->h_box.alloc(4));
+        G_TRY(h, h->d_refine.alloc(1)); G_TRY(h, h->h_refine.alloc(1));
         return RGRID_OK;
     }();
     if (rc != RGRID_OK) { std::fprintf(stderr, "rgrid_create: %s\n", h->hip_error.c_str()); rgrid_destroy(h); return rc; }
@@ -737,15 +714,9 @@ void rgrid_destroy(rgrid_t *h)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void *ptrs[] = {h->d_in, h->d_a, h->d_b, h->d_cs, h->d_key, h->d_idx, h->d_keep, h->d_cells, h->d_bb, h->d_best, h->d_count,
-                    h->d_hit, h->d_miss, h->d_mis, h->d_ends, h->d_bad, h->d_cells2, h->d_refine, h->d_tex, h->d_box, h->d_occ_tables, h->d_occ, h->d_key_b, h->d_keep_b, h->d_counts};
-    for (void *p : ptrs) (void)hipFree(p);
-    if (h->h_pts) (void)hipHostFree(h->h_pts);
-    if (h->h_count) (void)hipHostFree(h->h_count);
-    if (h->h_best) (void)hipHostFree(h->h_best);
-    if (h->h_refine) (void)hipHostFree(h->h_refine);
-    if (h->h_box) (void)hipHostFree(h->h_box);
-    if (h->h_counts) (void)hipHostFree(h->h_counts);
+    batch_host::release_all(h->d_in, h->d_a, h->d_b, h->d_cs, h->d_mis, h->h_pts, h->d_key, h->d_idx, h->d_ends, h->d_key_b, h->d_keep, h->d_keep_b, h->d_counts,
+                            h->d_count, h->d_bad, h->d_box, h->h_counts, h->h_count, h->h_box, h->d_cells, h->d_hit, h->d_miss, h->d_cells2, h->d_tex,
+                            h->d_occ_tables, h->d_occ, h->d_bb, h->d_best, h->h_best, h->d_refine, h->h_refine);   // the struct's members, in its order
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -760,9 +731,9 @@ int rgrid_voxel_filter(rgrid_t *h, const float *xy, int n, float resolution, flo
     int rc = upload_points(h, xy, n);
     if (rc != RGRID_OK) return rc;
     int cnt = 0;
-    rc = voxel_pass(h, h->d_in, n, resolution, h->d_a, &cnt);
+    rc = voxel_pass(h, h->d_in.d, n, resolution, h->d_a.d, &cnt);
     if (rc != RGRID_OK) return rc;
-    rc = download_points(h, h->d_a, cnt, out_xy, out_cap);
+    rc = download_points(h, h->d_a.d, cnt, out_xy, out_cap);
     if (rc != RGRID_OK) return rc;
     *m = cnt;
     return RGRID_OK;
@@ -779,12 +750,12 @@ int rgrid_adaptive_voxel_filter(rgrid_t *h, const float *xy, int n, double max_l
     int rc = upload_points(h, xy, n);
     if (rc != RGRID_OK) return rc;
     // FilterByMaxRange (voxel_filter.cc:15-27) -> d_key is free here, the gated cloud goes to d_in's twin: reuse d_b as "in"
-    hipLaunchKernelGGL(kg_range_gate, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_in, n, (float)max_range, h->d_keep);
-    hipLaunchKernelGGL(kg_compact, dim3(1), dim3(1024), 0, h->stream, h->d_in, h->d_keep, n, h->d_b, h->d_count);
-    G_TRY(h, hipMemcpyAsync(h->h_count, h->d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    hipLaunchKernelGGL(kg_range_gate, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_in.d, n, (float)max_range, h->d_keep.d);
+    hipLaunchKernelGGL(kg_compact, dim3(1), dim3(1024), 0, h->stream, h->d_in.d, h->d_keep.d, n, h->d_b.d, h->d_count.d);
+    G_TRY(h, hipMemcpyAsync(h->h_count.h, h->d_count.d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
-    const int ni = *h->h_count;
-    const float *src = h->d_b;                 // the gated cloud
+    const int ni = *h->h_count.h;
+    const float *src = h->d_b.d;                 // the gated cloud
     int cnt = ni;
     const float *final_buf = src;
     // AdaptivelyVoxelFiltered (voxel_filter.cc:29-76).  Its decisions only need the survivor COUNT of a voxel size, and
@@ -809,7 +780,7 @@ int rgrid_adaptive_voxel_filter(rgrid_t *h, const float *xy, int n, double max_l
             if (k < R) {
                 slot = k;
                 float low = ladder[k], high = (k == 1) ? maxl : ladder[k - 1];     // high of that iteration = the previous low
-                unsigned char *park = h->d_keep_b + (size_t)VOX_BATCH * ni;        // `result` while later batches reuse the slices
+                unsigned char *park = h->d_keep_b.d + (size_t)VOX_BATCH * ni;        // `result` while later batches reuse the slices
                 bool parked = false;
                 const int depth = ni <= 4096 ? 5 : (ni <= 8192 ? 3 : 2);
                 while ((high - low) / low > 1e-1f) {                               // :57
@@ -834,7 +805,7 @@ int rgrid_adaptive_voxel_filter(rgrid_t *h, const float *xy, int n, double max_l
                     float mids[VOX_BATCH];
                     for (int q = 0; q < nn; ++q) mids[q] = nodes[q].mid;
                     if (!parked) {                                                 // `result` lives in a slice the batch overwrites
-                        G_TRY(h, hipMemcpyAsync(park, h->d_keep_b + (size_t)slot * ni, (size_t)ni, hipMemcpyDeviceToDevice, h->stream));
+                        G_TRY(h, hipMemcpyAsync(park, h->d_keep_b.d + (size_t)slot * ni, (size_t)ni, hipMemcpyDeviceToDevice, h->stream));
                         parked = true;
                     }
                     rc = voxel_counts(h, src, ni, mids, nn, counts);
@@ -852,11 +823,11 @@ int rgrid_adaptive_voxel_filter(rgrid_t *h, const float *xy, int n, double max_l
                 if (parked) slot = VOX_BATCH;
             }
         }
-        hipLaunchKernelGGL(kg_compact, dim3(1), dim3(1024), 0, h->stream, src, h->d_keep_b + (size_t)slot * ni, ni, h->d_a, h->d_count);
-        G_TRY(h, hipMemcpyAsync(h->h_count, h->d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        hipLaunchKernelGGL(kg_compact, dim3(1), dim3(1024), 0, h->stream, src, h->d_keep_b.d + (size_t)slot * ni, ni, h->d_a.d, h->d_count.d);
+        G_TRY(h, hipMemcpyAsync(h->h_count.h, h->d_count.d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         G_TRY(h, hipStreamSynchronize(h->stream));
-        cnt = *h->h_count;
-        final_buf = h->d_a;
+        cnt = *h->h_count.h;
+        final_buf = h->d_a.d;
     }
     rc = download_points(h, final_buf, cnt, out_xy, out_cap);
     if (rc != RGRID_OK) return rc;
@@ -870,7 +841,7 @@ int rgrid_set_grid(rgrid_t *h, const uint16_t *cells, int num_x_cells, int num_y
     if (!h || !cells || num_x_cells < 1 || num_y_cells < 1 || !(resolution > 0.)) return RGRID_ERR_INVALID;
     if ((long long)num_x_cells * num_y_cells > h->max_cells) return RGRID_ERR_CAPACITY;
     G_TRY(h, hipSetDevice(h->device));
-    G_TRY(h, hipMemcpyAsync(h->d_cells, cells, sizeof(uint16_t) * (size_t)num_x_cells * num_y_cells, hipMemcpyHostToDevice, h->stream));
+    G_TRY(h, hipMemcpyAsync(h->d_cells.d, cells, sizeof(uint16_t) * (size_t)num_x_cells * num_y_cells, hipMemcpyHostToDevice, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
     h->nx = num_x_cells; h->ny = num_y_cells; h->resolution = resolution; h->max_x = max_x; h->max_y = max_y;
     h->have_grid = true;
@@ -880,53 +851,41 @@ int rgrid_set_grid(rgrid_t *h, const uint16_t *cells, int num_x_cells, int num_y
 int rgrid_insert(rgrid_t *h, const float origin_xy[2], const float *returns_xy, int n_returns, const float *misses_xy,
                  int n_misses, float hit_probability, float miss_probability, int insert_free_space)
 {
-    if (!h || !origin_xy || n_returns < 0 || n_misses < 0 || (n_returns > 0 && !returns_xy) || (n_misses > 0 && !misses_xy))
-        return RGRID_ERR_INVALID;
-    if (!h->have_grid || !(hit_probability > 0.f && hit_probability < 1.f) || !(miss_probability > 0.f && miss_probability < 1.f))
-        return RGRID_ERR_INVALID;
+    if (!h || !origin_xy || !two_clouds_ok(returns_xy, n_returns, misses_xy, n_misses)) return RGRID_ERR_INVALID;
+    if (!h->have_grid || !insert_options_ok(hit_probability, miss_probability)) return RGRID_ERR_INVALID;
     if (n_returns > h->max_points || n_misses > h->max_points) return RGRID_ERR_CAPACITY;
     G_TRY(h, hipSetDevice(h->device));
-    if (hit_probability != h->tab_hit_p || miss_probability != h->tab_miss_p) {      // the tables only depend on the two options
-        std::vector<unsigned short> t(32768);
-        lookup_table(hit_probability, t.data());
-        G_TRY(h, hipMemcpy(h->d_hit, t.data(), 2 * 32768, hipMemcpyHostToDevice));
-        lookup_table(miss_probability, t.data());
-        G_TRY(h, hipMemcpy(h->d_miss, t.data(), 2 * 32768, hipMemcpyHostToDevice));
-        h->tab_hit_p = hit_probability; h->tab_miss_p = miss_probability;
-    }
+    G_TRY(h, insert_tables(hit_probability, miss_probability, h->d_hit.d, h->d_miss.d, h->tab_hit_p, h->tab_miss_p));
     if (n_returns > 0) {
-        std::memcpy(h->h_pts, returns_xy, sizeof(float) * 2 * (size_t)n_returns);
-        G_TRY(h, hipMemcpyAsync(h->d_in, h->h_pts, sizeof(float) * 2 * (size_t)n_returns, hipMemcpyHostToDevice, h->stream));
+        if (upload_points(h, returns_xy, n_returns) != RGRID_OK) return RGRID_ERR_HIP;
         G_TRY(h, hipStreamSynchronize(h->stream));                                   // h_pts is reused for the misses below
     }
     if (n_misses > 0) {
-        std::memcpy(h->h_pts, misses_xy, sizeof(float) * 2 * (size_t)n_misses);
-        G_TRY(h, hipMemcpyAsync(h->d_mis, h->h_pts, sizeof(float) * 2 * (size_t)n_misses, hipMemcpyHostToDevice, h->stream));
+        std::memcpy(h->h_pts.h, misses_xy, sizeof(float) * 2 * (size_t)n_misses);
+        G_TRY(h, hipMemcpyAsync(h->d_mis.d, h->h_pts.h, sizeof(float) * 2 * (size_t)n_misses, hipMemcpyHostToDevice, h->stream));
     }
-    G_TRY(h, hipMemsetAsync(h->d_bad, 0, sizeof(int), h->stream));
+    G_TRY(h, hipMemsetAsync(h->d_bad.d, 0, sizeof(int), h->stream));
     InsertArgs A;
     A.nx = h->nx; A.ny = h->ny; A.n_ret = n_returns; A.n_miss = n_misses;
     A.max_x = h->max_x; A.max_y = h->max_y; A.rs = h->resolution / SUBPX;
     A.ox = origin_xy[0]; A.oy = origin_xy[1];
     const int n = n_returns + n_misses;
-    hipLaunchKernelGGL(kg_ends, dim3((n + 1 + 255) / 256), dim3(256), 0, h->stream, A, h->d_in, h->d_mis, h->d_ends, h->d_bad);
+    hipLaunchKernelGGL(kg_ends, dim3((n + 1 + 255) / 256), dim3(256), 0, h->stream, A, h->d_in.d, h->d_mis.d, h->d_ends.d, h->d_bad.d);
     if (n_returns > 0)
-        hipLaunchKernelGGL(kg_hits, dim3((n_returns + 255) / 256), dim3(256), 0, h->stream, A, h->d_ends, h->d_bad, h->d_cells, h->d_hit);
+        hipLaunchKernelGGL(kg_hits, dim3((n_returns + 255) / 256), dim3(256), 0, h->stream, A, h->d_ends.d, h->d_bad.d, h->d_cells.d, h->d_hit.d);
     if (insert_free_space && n > 0)
-        hipLaunchKernelGGL(kg_rays, dim3((n + 3) / 4), dim3(256), 0, h->stream, A, h->d_ends, h->d_bad, h->d_cells, h->d_miss);
+        hipLaunchKernelGGL(kg_rays, dim3((n + 3) / 4), dim3(256), 0, h->stream, A, h->d_ends.d, h->d_bad.d, h->d_cells.d, h->d_miss.d);
     const long long ncells = (long long)h->nx * h->ny;
-    hipLaunchKernelGGL(kg_finish, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, h->stream, h->d_cells, ncells, h->d_bad);
-    G_TRY(h, hipMemcpyAsync(h->h_count, h->d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    hipLaunchKernelGGL(kg_finish, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, h->stream, h->d_cells.d, ncells, h->d_bad.d);
+    G_TRY(h, hipMemcpyAsync(h->h_count.h, h->d_bad.d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
-    return *h->h_count ? RGRID_ERR_CAPACITY : RGRID_OK;
+    return *h->h_count.h ? RGRID_ERR_CAPACITY : RGRID_OK;
 }
 
 int rgrid_grow_as_needed(rgrid_t *h, const float origin_xy[2], const float *returns_xy, int n_returns, const float *misses_xy,
                          int n_misses)
 {
-    if (!h || !origin_xy || n_returns < 0 || n_misses < 0 || (n_returns > 0 && !returns_xy) || (n_misses > 0 && !misses_xy))
-        return RGRID_ERR_INVALID;
-    if (!h->have_grid) return RGRID_ERR_INVALID;
+    if (!h || !origin_xy || !two_clouds_ok(returns_xy, n_returns, misses_xy, n_misses) || !h->have_grid) return RGRID_ERR_INVALID;
     // the bounding box and Grid2D::GrowLimits for its corners, on the limits only (plan_growth of rgrid_dev.h)
     int nx = h->nx, ny = h->ny, off_x = 0, off_y = 0;
     double max_x = h->max_x, max_y = h->max_y;
@@ -934,10 +893,10 @@ int rgrid_grow_as_needed(rgrid_t *h, const float origin_xy[2], const float *retu
     if (rc != RGRID_OK) return rc;
     if (nx == h->nx && ny == h->ny) return RGRID_OK;
     G_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(kg_grow, dim3((nx + 255) / 256, ny), dim3(256), 0, h->stream, h->d_cells, h->nx, h->ny, h->d_cells2, nx, ny, off_x, off_y);
+    hipLaunchKernelGGL(kg_grow, dim3((nx + 255) / 256, ny), dim3(256), 0, h->stream, h->d_cells.d, h->nx, h->ny, h->d_cells2.d, nx, ny, off_x, off_y);
     G_TRY(h, hipGetLastError());
     G_TRY(h, hipStreamSynchronize(h->stream));
-    std::swap(h->d_cells, h->d_cells2);
+    std::swap(h->d_cells.d, h->d_cells2.d);
     h->nx = nx; h->ny = ny; h->max_x = max_x; h->max_y = max_y;
     return RGRID_OK;
 }
@@ -959,7 +918,7 @@ int rgrid_get_grid(rgrid_t *h, uint16_t *cells, long cap)
     const long long ncells = (long long)h->nx * h->ny;
     if (cap < ncells) return RGRID_ERR_BUFFER;
     G_TRY(h, hipSetDevice(h->device));
-    G_TRY(h, hipMemcpyAsync(cells, h->d_cells, sizeof(uint16_t) * (size_t)ncells, hipMemcpyDeviceToHost, h->stream));
+    G_TRY(h, hipMemcpyAsync(cells, h->d_cells.d, sizeof(uint16_t) * (size_t)ncells, hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));
     return RGRID_OK;
 }
@@ -974,12 +933,12 @@ int rgrid_match(rgrid_t *h, const rgrid_match_options *opt, const double initial
     if (n > h->max_points) return RGRID_ERR_CAPACITY;
     G_TRY(h, hipSetDevice(h->device));
     MatchPlan P;
-    if (plan_match(opt, h->resolution, initial_pose, points_xy, n, h->h_pts, &P) != RGRID_OK || P.num_scans > 1024 || P.ncand > h->max_candidates)
+    if (plan_match(opt, h->resolution, initial_pose, points_xy, n, h->h_pts.h, &P) != RGRID_OK || P.num_scans > 1024 || P.ncand > h->max_candidates)
         return RGRID_ERR_CAPACITY;
     std::vector<float> cs(2 * (size_t)P.num_scans);
     rotation_table(P, cs.data());
-    G_TRY(h, hipMemcpyAsync(h->d_in, h->h_pts, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    G_TRY(h, hipMemcpyAsync(h->d_cs, cs.data(), sizeof(float) * cs.size(), hipMemcpyHostToDevice, h->stream));
+    G_TRY(h, hipMemcpyAsync(h->d_in.d, h->h_pts.h, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    G_TRY(h, hipMemcpyAsync(h->d_cs.d, cs.data(), sizeof(float) * cs.size(), hipMemcpyHostToDevice, h->stream));
     MatchArgs A;
     A.n = n; A.num_scans = P.num_scans; A.num_linear = P.num_linear; A.nx = h->nx; A.ny = h->ny;
     A.tx = (float)initial_pose[0]; A.ty = (float)initial_pose[1];
@@ -987,39 +946,35 @@ int rgrid_match(rgrid_t *h, const rgrid_match_options *opt, const double initial
     A.num_angular_d = (double)P.num_angular; A.step = P.step;
     A.wt = opt->translation_delta_cost_weight; A.wr = opt->rotation_delta_cost_weight;
     const int nb_d = (P.num_scans * n + 255) / 256, nb_s = P.num_scans;
-    hipLaunchKernelGGL(kg_discretize, dim3(nb_d), dim3(256), 0, h->stream, A, h->d_in, h->d_cs, h->d_idx);
-    hipLaunchKernelGGL(kg_score, dim3(nb_s), dim3(128), 0, h->stream, A, h->d_idx, h->d_cells, h->d_bb);
-    hipLaunchKernelGGL(kg_best, dim3(1), dim3(256), 0, h->stream, h->d_bb, nb_s, h->d_best);
-    G_TRY(h, hipMemcpyAsync(h->h_best, h->d_best, sizeof(BestRec), hipMemcpyDeviceToHost, h->stream));
+    hipLaunchKernelGGL(kg_discretize, dim3(nb_d), dim3(256), 0, h->stream, A, h->d_in.d, h->d_cs.d, h->d_idx.d);
+    hipLaunchKernelGGL(kg_score, dim3(nb_s), dim3(128), 0, h->stream, A, h->d_idx.d, h->d_cells.d, h->d_bb.d);
+    hipLaunchKernelGGL(kg_best, dim3(1), dim3(256), 0, h->stream, h->d_bb.d, nb_s, h->d_best.d);
+    G_TRY(h, hipMemcpyAsync(h->h_best.h, h->d_best.d, sizeof(BestRec), hipMemcpyDeviceToHost, h->stream));
     G_TRY(h, hipStreamSynchronize(h->stream));                                            // cs stays alive until here
-    decode_best(P, initial_pose, *h->h_best, pose_estimate, score, best3, info3);
+    decode_best(P, initial_pose, *h->h_best.h, pose_estimate, score, best3, info3);
     return RGRID_OK;
 }
 
 // ---- mapping::MapBuilder::AddRangeData (src/mapping/map_builder.cc:57-108) as one call ------------------------------
 // Host side = what the reference's host does between the steps: a few rigid transforms (its float32 round trips
 // through Eigen quaternions restated operation by operation, as in reflector_ekf_slam_amd/map_builder.py) and the
-// decisions; every per-point / per-cell step is one of the entry points above.  The transforms themselves (yaw_of_quaternion_f32 /
-// _f64, rigid2f_apply) are rgrid_dev.h's: rgrid_batch_add_range_data composes its poses with the same text.
+// decisions; every per-point / per-cell step is one of the entry points above.  The transforms and compositions themselves are
+// rgrid_dev.h's, shared with rgrid_batch_add_range_data.
 int rgrid_add_range_data(rgrid_t *h, const rgrid_map_builder_options *opt, const float origin_xy[2], const float *returns_xy,
                          int n_returns, const float *misses_xy, int n_misses, const double ekf_pose[3], double local_pose[3],
                          float *returns_in_local, int *status)
 {
 #pragma clang fp contract(off)
-    if (!h || !opt || !origin_xy || !ekf_pose || !local_pose || n_returns < 0 || n_misses < 0 || (n_returns > 0 && !returns_xy) ||
-        (n_misses > 0 && !misses_xy))
-        return RGRID_ERR_INVALID;
+    if (!h || !opt || !origin_xy || !ekf_pose || !local_pose || !two_clouds_ok(returns_xy, n_returns, misses_xy, n_misses)) return RGRID_ERR_INVALID;
     if (status) *status = RGRID_SCAN_DROPPED_EMPTY;
     if (n_returns == 0) return RGRID_OK;                                          // "Dropped empty horizontal range data." (:63-67)
     if (n_returns > h->max_points || n_misses > h->max_points) return RGRID_ERR_CAPACITY;
-    const double x = ekf_pose[0], y = ekf_pose[1], theta = ekf_pose[2];
-    const double qw = std::cos(theta / 2), qz = std::sin(theta / 2);             // the caller's quaternion (src/ros_node.cc:548)
     // TransformToGravityAlignedFrameAndFilter (:20-32): Rotation(q).cast<float>() -> Project2D -> Rigid2f(0, GetYaw)
-    const float yaw_g = yaw_of_quaternion_f32((float)qw, (float)qz);
+    double qw, qz;
+    float yaw_g;
+    gravity_alignment(ekf_pose[2], qw, qz, yaw_g);
     std::vector<float> ret((size_t)2 * n_returns), mis((size_t)2 * (n_misses > 0 ? n_misses : 1)), fr((size_t)2 * n_returns),
         fm((size_t)2 * (n_misses > 0 ? n_misses : 1)), av((size_t)2 * n_returns);
-    float org[2];
-    rigid2f_apply(0.f, 0.f, yaw_g, origin_xy, 1, org);
     rigid2f_apply(0.f, 0.f, yaw_g, returns_xy, n_returns, ret.data());
     if (n_misses > 0) rigid2f_apply(0.f, 0.f, yaw_g, misses_xy, n_misses, mis.data());
     int nfr = 0, nfm = 0, nav = 0;
@@ -1027,7 +982,7 @@ int rgrid_add_range_data(rgrid_t *h, const rgrid_map_builder_options *opt, const
     if (rc != RGRID_OK) return rc;
     if (n_misses > 0) { rc = rgrid_voxel_filter(h, mis.data(), n_misses, opt->voxel_filter_size, fm.data(), n_misses, &nfm); if (rc != RGRID_OK) return rc; }
     // pose_prediction = Project2D(ekf_pose * gravity_alignment.inverse()): the rotations cancel (:70-71)
-    const double prediction[3] = {x, y, 0.0};
+    const double prediction[3] = {ekf_pose[0], ekf_pose[1], 0.0};
     rc = rgrid_adaptive_voxel_filter(h, fr.data(), nfr, opt->adaptive_max_length, opt->adaptive_min_num_points, opt->adaptive_max_range,
                                      av.data(), n_returns, &nav);
     if (rc != RGRID_OK) return rc;
@@ -1041,28 +996,22 @@ int rgrid_add_range_data(rgrid_t *h, const rgrid_map_builder_options *opt, const
         rc = rgrid_refine_match(h, &opt->refine, prediction, coarse, av.data(), nav, est, nullptr);
         if (rc != RGRID_OK) return rc;
     }
-    // pose_estimate = Embed3D(pose_estimate_2d) * gravity_alignment: quaternion product about z, in double (:86-87)
-    const double aw = std::cos(0.5 * est[2]), az = std::sin(0.5 * est[2]);
-    const double pw = aw * qw - az * qz, pz = aw * qz + az * qw;
-    local_pose[0] = est[0]; local_pose[1] = est[1]; local_pose[2] = yaw_of_quaternion_f64(pw, pz);
-    if (returns_in_local)                                                         // range_data_in_local (:89-90), the raw returns
-        rigid2f_apply((float)est[0], (float)est[1], yaw_of_quaternion_f32((float)pw, (float)pz), returns_xy, n_returns, returns_in_local);
-    // range_data_in_local2 = TransformRangeData(gravity-aligned filtered data, Embed3D(pose_estimate_2d.cast<float>())) (:92-94)
-    const float af = (float)est[2], ha = 0.5f * af;
-    const float yaw2 = yaw_of_quaternion_f32((float)std::cos((double)ha), (float)std::sin((double)ha));
-    float org2[2];
-    rigid2f_apply((float)est[0], (float)est[1], yaw2, org, 1, org2);
+    // pose_estimate = Embed3D(pose_estimate_2d) * gravity_alignment (:86-87): the raw returns move by it (:89-90), the filtered data by yaw2 (:92-94)
+    float yaw_f32, yaw2, org2[2];
+    compose_pose_estimate(est, qw, qz, local_pose, yaw_f32, yaw2);
+    if (returns_in_local) rigid2f_apply((float)est[0], (float)est[1], yaw_f32, returns_xy, n_returns, returns_in_local);
+    origin_in_local(origin_xy, yaw_g, est, yaw2, org2);
     rigid2f_apply((float)est[0], (float)est[1], yaw2, fr.data(), nfr, ret.data());
     if (nfm > 0) rigid2f_apply((float)est[0], (float)est[1], yaw2, fm.data(), nfm, mis.data());
     if (!h->have_grid) {                                                          // InsertIntoSubmap / CreateGrid (:110-126)
-        const int n0 = 100;                                                      // kInitialSubmapSize
-        if ((long long)n0 * n0 > h->max_cells) return RGRID_ERR_CAPACITY;
-        const double resolution = (double)opt->resolution;                       // `float resolution = options_.resolution`
-        const double half = 0.5 * n0 * resolution;
+        int nx, ny;
+        double resolution, max_x, max_y;
+        rc = initial_submap_limits(opt->resolution, org2, h->max_cells, nx, ny, resolution, max_x, max_y);
+        if (rc != RGRID_OK) return rc;
         G_TRY(h, hipSetDevice(h->device));
-        G_TRY(h, hipMemsetAsync(h->d_cells, 0, sizeof(uint16_t) * (size_t)n0 * n0, h->stream));
+        G_TRY(h, hipMemsetAsync(h->d_cells.d, 0, sizeof(uint16_t) * (size_t)nx * ny, h->stream));
         G_TRY(h, hipStreamSynchronize(h->stream));
-        h->nx = n0; h->ny = n0; h->resolution = resolution; h->max_x = (double)org2[0] + half; h->max_y = (double)org2[1] + half;
+        h->nx = nx; h->ny = ny; h->resolution = resolution; h->max_x = max_x; h->max_y = max_y;
         h->have_grid = true;
     }
     rc = rgrid_grow_as_needed(h, org2, ret.data(), nfr, nfm > 0 ? mis.data() : nullptr, nfm);

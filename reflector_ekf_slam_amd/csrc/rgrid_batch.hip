@@ -25,7 +25,8 @@
 // (kgb_filter<true>, which rotates the raw clouds into the gravity-aligned frame as it loads them), match and refinement, the
 // insert -- in ONE synchronous call, with the host composing the poses between them as rgrid_add_range_data does, and kgb_to_local
 // for the raw returns in the local frame.  It packs, stages and launches through the functions the single-kind
-// submits call; there is one text of each.
+// submits call; there is one text of each, and the host steps it has in common with the single handle (checks, launch shapes, resident
+// tables, slice_max_of, AddRangeData's compositions) are rgrid_dev.h's.
 //
 // Per-call data -- a record per scan, the workgroup -> (record, rotation) map, the rotation tables and the rotated points --
 // is packed into one of two staging segments that the kernel reads in place: fine-grained device memory the host writes
@@ -858,23 +859,6 @@ struct OccupancyPending { int grid; long long out_off; double submap_origin[2]; 
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// what rgrid_refine_match refuses (the reference CHECK_GTs the weights, ceres_scan_matcher_2d.cc:37,47,52)
-bool refine_options_ok(const rgrid_refine_options *o)
-{
-    return o->occupied_space_weight > 0. && o->translation_weight > 0. && o->rotation_weight > 0. && o->max_num_iterations >= 0;
-}
-
-// RefineArgs as rgrid_refine_match fills them, without the poses
-void refine_args(RefineArgs &A, const GridSlot &g, const rgrid_refine_options *opt, int n)
-{
-    std::memset(&A, 0, sizeof(A));
-    A.nx = g.nx; A.ny = g.ny; A.n = n; A.max_iter = opt->max_num_iterations; A.max_nonmono = opt->use_nonmonotonic_steps ? 5 : 0;
-    A.res = g.resolution; A.max_x = g.max_x; A.max_y = g.max_y;
-    A.w_occ = opt->occupied_space_weight; A.w_t = opt->translation_weight; A.w_r = opt->rotation_weight;
-}
-
-int refine_threads(int n) { const int t = ((n + 63) / 64) * 64; return t < 1024 ? t : 1024; }   // = rgrid_refine_match's
-
 }  // namespace
 
 struct rgrid_batch {
@@ -890,18 +874,18 @@ struct rgrid_batch {
         std::vector<unsigned char> pack;
         unsigned long long n_taken = 0;
     } seg;
-    unsigned short *d_cells = nullptr;     // grid pool
+    batch_host::Device<unsigned short> cells;   // grid pool
     std::vector<GridSlot> grids;
     // the matcher and the refinement: a result slot per scan
     struct {
-        unsigned long long *d_bb = nullptr;
-        int *d_arrived = nullptr;
+        batch_host::Device<unsigned long long> bb;   // [max_scans][max_rotations] block bests
+        batch_host::Device<int> arrived;             // [max_scans] arrival counters
         batch_host::Pinned<BestRec> best;
         batch_host::Pinned<RefineOut> fine;
     } res;
     // the inserter: the two lookup tables (uint16[32768] each) and the probabilities they were built for, a flag per record
     struct {
-        unsigned short *d_hit = nullptr, *d_miss = nullptr;
+        batch_host::Device<unsigned short> hit, miss;
         float tab_hit_p = -1.f, tab_miss_p = -1.f;
         batch_host::Pinned<int> bad;
         std::vector<unsigned long long> slot_call;   // the insert submit that named a slot last (a call names a slot once)
@@ -932,7 +916,7 @@ struct rgrid_batch {
     // the texture (texture_staging): the (value, alpha) table (uint16[32768]) on the device, uploaded by the first texture submit;
     // the output area and the box records, allocated by the first texture submit, the area grown only when a call needs more
     struct {
-        unsigned short *d_table = nullptr;
+        batch_host::Device<unsigned short> table;
         batch_host::Pinned<unsigned short> out;
         size_t out_pairs = 0;
         batch_host::Pinned<int> box;
@@ -941,7 +925,7 @@ struct rgrid_batch {
     // the occupancy grid (occupancy_staging): the two byte tables (occupancy, then red: 2 * 32768 bytes) on the device, uploaded by
     // the first occupancy submit; the output area and the box records, allocated by it too, the area grown only when a call needs more
     struct {
-        unsigned char *d_tables = nullptr;
+        batch_host::Device<unsigned char> tables;
         batch_host::Pinned<unsigned char> out;
         size_t out_bytes = 0;
         batch_host::Pinned<int> box;
@@ -967,12 +951,6 @@ long long cells_offset(const rgrid_batch_t *b, int grid) { return (long long)gri
 
 // one cloud of a scan of a match or a refine submit, into a set slot
 bool cloud_ok(const rgrid_batch_t *b, int grid, const float *points_xy, int n) { return slot_ok(b, grid) && n >= 0 && (n == 0 || points_xy); }
-
-// the two clouds of a scan of an insert or a filter submit
-bool two_clouds_ok(const float *returns_xy, int n_returns, const float *misses_xy, int n_misses)
-{
-    return n_returns >= 0 && n_misses >= 0 && (n_returns == 0 || returns_xy) && (n_misses == 0 || misses_xy);
-}
 
 // The segments are used in turn, and the turn passes once per launch that reads one.  next_segment is the one that launch will read
 // (a submit may write points straight into it before it knows whether it has anything to launch); take_segment is next_segment for
@@ -1093,7 +1071,7 @@ void launch_match(rgrid_batch_t *b, int k, const MatchWork &W)
 {
     BatchBufs Bf;
     Bf.seg = b->seg.buf[k].dv; Bf.wgmap_off = (int)b->seg.wgmap_off; Bf.f2_off = (int)b->seg.f2_off;
-    Bf.cells = b->d_cells; Bf.bb = b->res.d_bb; Bf.arrived = b->res.d_arrived; Bf.out = b->res.best.dv;
+    Bf.cells = b->cells.d; Bf.bb = b->res.bb.d; Bf.arrived = b->res.arrived.d; Bf.out = b->res.best.dv;
     Bf.max_rotations = b->max_rotations < KGB_MAX_ROT ? b->max_rotations : KGB_MAX_ROT;
     const size_t lds = sizeof(int2) * (size_t)((W.n_max + KGB_PF - 1) / KGB_PF * KGB_PF);
     b->n_launches += b->mode == RGRID_BATCH_REDUCE_ARRIVAL ? 1 : 2;
@@ -1112,7 +1090,8 @@ RefineRec &pack_refine(rgrid_batch_t *b, int k, int rec, const rgrid_refine_opti
 {
     RefineRec &R = reinterpret_cast<RefineRec *>(b->seg.pack.data() + b->seg.rrec_off)[rec];
     std::memset(&R, 0, sizeof(R));
-    refine_args(R.A, b->grids[(size_t)grid], opt, n);
+    const GridSlot &g = b->grids[(size_t)grid];
+    refine_args(R.A, g.nx, g.ny, g.resolution, g.max_x, g.max_y, opt, n);
     R.cells_off = cells_offset(b, grid);
     R.pts_off = nraw;
     std::memcpy(reinterpret_cast<float *>(b->seg.buf[k].h + b->seg.raw_off) + 2 * (size_t)nraw, points_xy, sizeof(float) * 2 * (size_t)n);
@@ -1126,7 +1105,7 @@ void launch_refine(rgrid_batch_t *b, int k, int nrec, int threads)
 {
     RefineBufs Rf;
     Rf.seg = b->seg.buf[k].dv; Rf.rrec_off = (int)b->seg.rrec_off; Rf.raw_off = (int)b->seg.raw_off;
-    Rf.cells = b->d_cells; Rf.best = b->res.best.dv; Rf.out = b->res.fine.dv;
+    Rf.cells = b->cells.d; Rf.best = b->res.best.dv; Rf.out = b->res.fine.dv;
     ++b->n_launches;
     hipLaunchKernelGGL(kgb_refine, dim3((unsigned)nrec), dim3((unsigned)threads), 0, b->stream, Rf);
 }
@@ -1199,14 +1178,7 @@ void pack_insert_scan(rgrid_batch_t *b, InsertWork &W, const rgrid_batch_insert_
 int begin_insert(rgrid_batch_t *b, const rgrid_insert_options *opt, InsertWork &W)
 {
     G_TRY(b, hipSetDevice(b->device));
-    if (opt->hit_probability != b->ins.tab_hit_p || opt->miss_probability != b->ins.tab_miss_p) {
-        std::vector<unsigned short> t(32768);
-        lookup_table(opt->hit_probability, t.data());
-        G_TRY(b, hipMemcpy(b->ins.d_hit, t.data(), 2 * 32768, hipMemcpyHostToDevice));
-        lookup_table(opt->miss_probability, t.data());
-        G_TRY(b, hipMemcpy(b->ins.d_miss, t.data(), 2 * 32768, hipMemcpyHostToDevice));
-        b->ins.tab_hit_p = opt->hit_probability; b->ins.tab_miss_p = opt->miss_probability;
-    }
+    G_TRY(b, insert_tables(opt->hit_probability, opt->miss_probability, b->ins.hit.d, b->ins.miss.d, b->ins.tab_hit_p, b->ins.tab_miss_p));
     W = InsertWork{next_segment(b), 0, 0, 0};
     return RGRID_OK;
 }
@@ -1223,14 +1195,9 @@ void launch_insert(rgrid_batch_t *b, const rgrid_insert_options *opt, const Inse
 {
     InsertBufs If;
     If.seg = b->seg.buf[W.k].dv; If.f2_off = (int)b->seg.f2_off; If.raw_off = (int)b->seg.raw_off;
-    If.cells = b->d_cells; If.hit = b->ins.d_hit; If.miss = b->ins.d_miss; If.bad = b->ins.bad.dv; If.free_space = opt->insert_free_space ? 1 : 0;
+    If.cells = b->cells.d; If.hit = b->ins.hit.d; If.miss = b->ins.miss.d; If.bad = b->ins.bad.dv; If.free_space = opt->insert_free_space ? 1 : 0;
     ++b->n_launches;
     hipLaunchKernelGGL(kgb_insert, dim3((unsigned)W.nrec), dim3(KGI_THREADS), 0, b->stream, If);
-}
-
-bool insert_options_ok(const rgrid_insert_options *o)
-{
-    return o->hit_probability > 0.f && o->hit_probability < 1.f && o->miss_probability > 0.f && o->miss_probability < 1.f;
 }
 
 // A slot at most once per call: two insertions into one grid in one launch have no reference meaning (FinishUpdate lies between).
@@ -1291,8 +1258,6 @@ int filter_staging(rgrid_batch_t *b)
     return RGRID_OK;
 }
 
-bool filter_options_ok(const rgrid_filter_options *o) { return o->voxel_filter_size > 0.f && o->adaptive_max_length > 0.; }
-
 // how far a filter's packing has come: records, input points, output points, the largest cloud
 struct FilterWork { int nrec, nin, nout, n_max; };
 
@@ -1352,53 +1317,17 @@ void launch_filter(rgrid_batch_t *b, const rgrid_filter_options *opt, const Filt
     hipLaunchKernelGGL(kgb_filter<ROT>, dim3((unsigned)W.nrec), dim3(KGF_THREADS), lds, b->stream, Ff, rot);
 }
 
-// the texture's staging for a call that writes `pairs` pairs: the table and the box records once, the output area when it is too small
-int texture_staging(rgrid_batch_t *b, size_t pairs)
+// The staging of a texture or an occupancy call that writes `need` elements: the box records once, the output area when it is too small
+template <typename T>
+int export_staging(rgrid_batch_t *b, batch_host::Pinned<int> &box, batch_host::Pinned<T> &out, size_t &have, size_t need)
 {
-    if (!b->tex.d_table) {
-        std::vector<unsigned short> t(32768);
-        texture_table(t.data());
-        unsigned short *d = nullptr;
-        G_TRY(b, hipMalloc((void **)&d, 2 * 32768));
-        if (hipMemcpy(d, t.data(), 2 * 32768, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); b->hip_error = "texture table: upload failed"; return RGRID_ERR_HIP; }
-        b->tex.d_table = d;
-    }
-    if (!b->tex.box.h) {
-        b->tex.sub.resize((size_t)b->max_scans);
-        G_TRY(b, b->tex.box.alloc(4 * (size_t)b->max_scans));
-    }
-    if (pairs > b->tex.out_pairs) {                                                // it never shrinks
+    if (!box.h) G_TRY(b, box.alloc(4 * (size_t)b->max_scans));
+    if (need > have) {                                                             // it never shrinks
         G_TRY(b, hipStreamSynchronize(b->stream));                                 // (nothing is pending: the area is idle)
-        b->tex.out.release();
-        b->tex.out_pairs = 0;
-        G_TRY(b, b->tex.out.alloc(pairs));
-        b->tex.out_pairs = pairs;
-    }
-    return RGRID_OK;
-}
-
-// the occupancy grid's staging for a call that writes `bytes` bytes: the tables and the box records once, the output area when it is too small
-int occupancy_staging(rgrid_batch_t *b, size_t bytes)
-{
-    if (!b->occ.d_tables) {
-        std::vector<unsigned char> t(2 * 32768);
-        occupancy_tables(reinterpret_cast<signed char *>(t.data()), t.data() + 32768);
-        unsigned char *d = nullptr;
-        G_TRY(b, hipMalloc((void **)&d, 2 * 32768));
-        if (hipMemcpy(d, t.data(), 2 * 32768, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); b->hip_error = "occupancy tables: upload failed"; return RGRID_ERR_HIP; }
-        b->occ.d_tables = d;
-    }
-    if (!b->occ.box.h) {
-        b->occ.sub.resize((size_t)b->max_scans);
-        b->occ.frame.resize((size_t)b->max_scans);
-        G_TRY(b, b->occ.box.alloc(4 * (size_t)b->max_scans));
-    }
-    if (bytes > b->occ.out_bytes) {                                                // it never shrinks
-        G_TRY(b, hipStreamSynchronize(b->stream));                                 // (nothing is pending: the area is idle)
-        b->occ.out.release();
-        b->occ.out_bytes = 0;
-        G_TRY(b, b->occ.out.alloc(bytes));
-        b->occ.out_bytes = bytes;
+        out.release();
+        have = 0;
+        G_TRY(b, out.alloc(need));
+        have = need;
     }
     return RGRID_OK;
 }
@@ -1459,14 +1388,6 @@ void launch_to_local(rgrid_batch_t *b, int nwg)
     hipLaunchKernelGGL(kgb_to_local, dim3((unsigned)nwg), dim3(KGL_THREADS), 0, b->stream, Lf);
 }
 
-// the caller's quaternion of an EKF yaw (src/ros_node.cc:548) and the gravity alignment's yaw (map_builder.cc:20-28): Rotation(q)
-// .cast<float>() -> Project2D -> GetYaw
-void gravity_alignment(double theta, double &qw, double &qz, float &yaw_g)
-{
-    qw = std::cos(theta / 2); qz = std::sin(theta / 2);
-    yaw_g = yaw_of_quaternion_f32((float)qw, (float)qz);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1515,11 +1436,11 @@ int rgrid_batch_create(int max_scans, int max_points, int num_grids, long max_ce
         std::memset(b->res.fine.h, 0, sizeof(RefineOut) * nS);
         G_TRY(b, b->ins.bad.alloc(nS));
         std::memset(b->ins.bad.h, 0, sizeof(int) * nS);
-        G_TRY(b, hipMalloc((void **)&b->ins.d_hit, 2 * 32768)); G_TRY(b, hipMalloc((void **)&b->ins.d_miss, 2 * 32768));
-        G_TRY(b, hipMalloc((void **)&b->d_cells, sizeof(unsigned short) * (size_t)num_grids * (size_t)max_cells));
-        G_TRY(b, hipMalloc((void **)&b->res.d_bb, sizeof(unsigned long long) * nS * nR));
-        G_TRY(b, hipMalloc((void **)&b->res.d_arrived, sizeof(int) * nS));
-        G_TRY(b, hipMemsetAsync(b->res.d_arrived, 0, sizeof(int) * nS, b->stream));
+        G_TRY(b, b->ins.hit.alloc(32768)); G_TRY(b, b->ins.miss.alloc(32768));
+        G_TRY(b, b->cells.alloc((size_t)num_grids * (size_t)max_cells));
+        G_TRY(b, b->res.bb.alloc(nS * nR));
+        G_TRY(b, b->res.arrived.alloc(nS));
+        G_TRY(b, hipMemsetAsync(b->res.arrived.d, 0, sizeof(int) * nS, b->stream));
         // the rotated scan's indices in LDS: 8 B per point, 64 KB at 8192 points
         const int lds_max = (int)(sizeof(int2) * (nP + KGB_PF));
         G_TRY(b, hipFuncSetAttribute((const void *)kgb_match<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
@@ -1536,14 +1457,9 @@ void rgrid_batch_destroy(rgrid_batch_t *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    (void)hipFree(b->d_cells); (void)hipFree(b->res.d_bb); (void)hipFree(b->res.d_arrived);
-    (void)hipFree(b->ins.d_hit); (void)hipFree(b->ins.d_miss); (void)hipFree(b->tex.d_table); (void)hipFree(b->occ.d_tables);
-    for (auto &s : b->seg.buf) s.release();
-    b->res.best.release(); b->res.fine.release(); b->ins.bad.release();
-    b->fil.in.release(); b->fil.out.release(); b->fil.cnt.release();
-    b->ard.tab.release(); b->ard.out.release();
-    b->tex.out.release(); b->tex.box.release();
-    b->occ.out.release(); b->occ.box.release();
+    batch_host::release_all(b->cells, b->res.bb, b->res.arrived, b->ins.hit, b->ins.miss, b->tex.table, b->occ.tables, b->seg.buf[0], b->seg.buf[1],
+                            b->res.best, b->res.fine, b->ins.bad, b->fil.in, b->fil.out, b->fil.cnt, b->ard.tab, b->ard.out, b->tex.out, b->tex.box,
+                            b->occ.out, b->occ.box);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -1562,7 +1478,7 @@ int rgrid_batch_set_grid(rgrid_batch_t *b, int grid, const uint16_t *cells, int 
         return RGRID_ERR_INVALID;
     if ((long long)num_x_cells * num_y_cells > (long long)b->max_cells) return RGRID_ERR_CAPACITY;
     G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipMemcpyAsync(b->d_cells + cells_offset(b, grid), cells, sizeof(uint16_t) * (size_t)num_x_cells * num_y_cells,
+    G_TRY(b, hipMemcpyAsync(b->cells.d + cells_offset(b, grid), cells, sizeof(uint16_t) * (size_t)num_x_cells * num_y_cells,
                             hipMemcpyHostToDevice, b->stream));
     G_TRY(b, hipStreamSynchronize(b->stream));
     GridSlot &g = b->grids[(size_t)grid];
@@ -1679,7 +1595,7 @@ int rgrid_batch_get_grid(rgrid_batch_t *b, int grid, uint16_t *cells, long cap)
     const long long ncells = (long long)g.nx * g.ny;
     if (cap < ncells) return RGRID_ERR_BUFFER;
     G_TRY(b, hipSetDevice(b->device));
-    G_TRY(b, hipMemcpyAsync(cells, b->d_cells + cells_offset(b, grid), sizeof(uint16_t) * (size_t)ncells, hipMemcpyDeviceToHost, b->stream));
+    G_TRY(b, hipMemcpyAsync(cells, b->cells.d + cells_offset(b, grid), sizeof(uint16_t) * (size_t)ncells, hipMemcpyDeviceToHost, b->stream));
     G_TRY(b, hipStreamSynchronize(b->stream));
     return RGRID_OK;
 }
@@ -1688,7 +1604,7 @@ int rgrid_batch_insert_submit(rgrid_batch_t *b, const rgrid_insert_options *opt,
 {
     // (scans == NULL is refused at count == 0 too, unlike the match, the refinement and the texture: callers may rely on it)
     if (!b || !opt || !scans || count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
-    if (!insert_options_ok(opt)) return RGRID_ERR_INVALID;
+    if (!insert_options_ok(opt->hit_probability, opt->miss_probability)) return RGRID_ERR_INVALID;
     for (int j = 0; j < count; ++j) {
         const rgrid_batch_insert_scan &s = scans[j];
         if (!slot_ok(b, s.grid) || !two_clouds_ok(s.returns_xy, s.n_returns, s.misses_xy, s.n_misses)) return RGRID_ERR_INVALID;
@@ -1773,7 +1689,9 @@ int rgrid_batch_texture_submit(rgrid_batch_t *b, const int *grids, int count)
     int k = 0;
     if (count > 0) {                                                               // (a call without a slot allocates nothing and takes no segment)
         G_TRY(b, hipSetDevice(b->device));
-        const int rc = texture_staging(b, pairs);
+        G_TRY(b, resident_texture_table(b->tex.table.d));
+        b->tex.sub.resize((size_t)b->max_scans);
+        const int rc = export_staging(b, b->tex.box, b->tex.out, b->tex.out_pairs, pairs);
         if (rc != RGRID_OK) return rc;
         k = take_segment(b);
         TextureRec *recs = reinterpret_cast<TextureRec *>(b->seg.pack.data());
@@ -1790,7 +1708,7 @@ int rgrid_batch_texture_submit(rgrid_batch_t *b, const int *grids, int count)
     }
     return submit_tail(b, KIND_TEXTURE, count, count, t_begin, [&] {
         TextureBufs Tf;
-        Tf.seg = b->seg.buf[k].dv; Tf.cells = b->d_cells; Tf.table = b->tex.d_table; Tf.out = b->tex.out.dv; Tf.box = b->tex.box.dv;
+        Tf.seg = b->seg.buf[k].dv; Tf.cells = b->cells.d; Tf.table = b->tex.table.d; Tf.out = b->tex.out.dv; Tf.box = b->tex.box.dv;
         hipLaunchKernelGGL(kgb_texture, dim3((unsigned)count), dim3(KGT_THREADS), 0, b->stream, Tf);
     });
 }
@@ -1804,10 +1722,8 @@ int rgrid_batch_texture_collect(rgrid_batch_t *b, int *boxes, double *slice_max,
     for (int j = 0; j < count; ++j) {
         const GridSlot &g = b->grids[(size_t)b->tex.sub[(size_t)j].grid];
         const int *box = b->tex.box.h + 4 * j;
-        const int x0 = box[0], y0 = box[1];
         for (int c = 0; c < 4; ++c) boxes[4 * j + c] = box[c];
-        slice_max[2 * j] = g.max_x - g.resolution * y0;                             // (probability_grid.cc:122-123), rgrid_draw_texture's expressions
-        slice_max[2 * j + 1] = g.max_y - g.resolution * x0;
+        slice_max_of(box, g.resolution, g.max_x, g.max_y, &slice_max[2 * j]);
         offsets[j] = total;
         total += 2l * box[2] * box[3];
     }
@@ -1832,7 +1748,9 @@ int rgrid_batch_occupancy_submit(rgrid_batch_t *b, int mode, const int *grids, c
     int k = 0;
     if (count > 0) {                                                               // (a call without a slot allocates nothing and takes no segment)
         G_TRY(b, hipSetDevice(b->device));
-        const int rc = occupancy_staging(b, bytes);
+        G_TRY(b, resident_occupancy_tables(b->occ.tables.d));
+        b->occ.sub.resize((size_t)b->max_scans); b->occ.frame.resize((size_t)b->max_scans);
+        const int rc = export_staging(b, b->occ.box, b->occ.out, b->occ.out_bytes, bytes);
         if (rc != RGRID_OK) return rc;
         k = take_segment(b);
         OccupancyRec *recs = reinterpret_cast<OccupancyRec *>(b->seg.pack.data());
@@ -1850,7 +1768,7 @@ int rgrid_batch_occupancy_submit(rgrid_batch_t *b, int mode, const int *grids, c
     }
     return submit_tail(b, KIND_OCCUPANCY, count, count, t_begin, [&] {
         OccupancyBufs Of;
-        Of.seg = b->seg.buf[k].dv; Of.cells = b->d_cells; Of.table = b->occ.d_tables + (mode == OCC_MODE_IMAGE ? 32768 : 0);
+        Of.seg = b->seg.buf[k].dv; Of.cells = b->cells.d; Of.table = b->occ.tables.d + (mode == OCC_MODE_IMAGE ? 32768 : 0);
         Of.out = b->occ.out.dv; Of.box = b->occ.box.dv;
         hipLaunchKernelGGL(kgb_occupancy, dim3((unsigned)count), dim3(KGT_THREADS), 0, b->stream, Of);
     });
@@ -1904,7 +1822,7 @@ int rgrid_batch_add_range_data(rgrid_batch_t *b, const rgrid_map_builder_options
     if (count < 0 || count > b->max_scans || b->outstanding) return RGRID_ERR_INVALID;
     const rgrid_filter_options fopt = {opt->voxel_filter_size, opt->adaptive_max_length, opt->adaptive_min_num_points, opt->adaptive_max_range};
     const rgrid_insert_options iopt = {opt->hit_probability, opt->miss_probability, opt->insert_free_space};
-    if (!filter_options_ok(&fopt) || !refine_options_ok(&opt->refine) || !insert_options_ok(&iopt)) return RGRID_ERR_INVALID;
+    if (!filter_options_ok(&fopt) || !refine_options_ok(&opt->refine) || !insert_options_ok(iopt.hit_probability, iopt.miss_probability)) return RGRID_ERR_INVALID;
     long total = 0;
     for (int j = 0; j < count; ++j) {
         const rgrid_batch_range_data &s = scans[j];
@@ -1976,7 +1894,7 @@ int rgrid_batch_add_range_data(rgrid_batch_t *b, const rgrid_map_builder_options
             refine_result(b, P, S.est, nullptr);
         }
     }
-    // ---- 4. the pose compositions (rgrid_add_range_data's lines) and the insert's packing: the filtered clouds moved by
+    // ---- 4. the pose compositions (rgrid_dev.h's, as in rgrid_add_range_data) and the insert's packing: the filtered clouds moved by
     // Embed3D(pose_estimate_2d.cast<float>()) on their way from the filter's output into the insert's segment
     t_begin = std::chrono::steady_clock::now();
     InsertWork I;
@@ -1992,30 +1910,20 @@ int rgrid_batch_add_range_data(rgrid_batch_t *b, const rgrid_map_builder_options
         double qw, qz;
         float yaw_g;
         gravity_alignment(s.ekf_pose[2], qw, qz, yaw_g);
-        // pose_estimate = Embed3D(pose_estimate_2d) * gravity_alignment: quaternion product about z, in double (:86-87)
-        const double aw = std::cos(0.5 * est[2]), az = std::sin(0.5 * est[2]);
-        const double pw = aw * qw - az * qz, pz = aw * qz + az * qw;
-        double *local_pose = &local_poses[3 * j];
-        local_pose[0] = est[0]; local_pose[1] = est[1]; local_pose[2] = yaw_of_quaternion_f64(pw, pz);
-        // range_data_in_local2 = TransformRangeData(gravity-aligned filtered data, Embed3D(pose_estimate_2d.cast<float>())) (:92-94)
-        const float af = (float)est[2], ha = 0.5f * af;
-        const float yaw2 = yaw_of_quaternion_f32((float)std::cos((double)ha), (float)std::sin((double)ha));
-        float org[2], org2[2];
-        rigid2f_apply(0.f, 0.f, yaw_g, s.origin_xy, 1, org);
-        rigid2f_apply((float)est[0], (float)est[1], yaw2, org, 1, org2);
+        // pose_estimate = Embed3D(pose_estimate_2d) * gravity_alignment (:86-87); the filtered data moves by yaw2 (:92-94)
+        float yaw_f32, yaw2, org2[2];
+        compose_pose_estimate(est, qw, qz, &local_poses[3 * j], yaw_f32, yaw2);
+        origin_in_local(s.origin_xy, yaw_g, est, yaw2, org2);
         origins_in_local[2 * j] = org2[0]; origins_in_local[2 * j + 1] = org2[1];
         const float *fr = reinterpret_cast<const float *>(b->fil.out.h + S.out_off), *fm = fr + 2 * (size_t)s.n_returns;
         rigid2f_apply((float)est[0], (float)est[1], yaw2, fr, S.n_fr, b->ard.ret.data());
         if (S.n_fm > 0) rigid2f_apply((float)est[0], (float)est[1], yaw2, fm, S.n_fm, b->ard.mis.data());
         GridSlot &g = b->grids[(size_t)s.grid];
         if (!g.set) {                                                            // InsertIntoSubmap / CreateGrid (:110-126)
-            const int n0 = 100;                                                  // kInitialSubmapSize
-            if ((long long)n0 * n0 > (long long)b->max_cells) { codes[j] = RGRID_ERR_CAPACITY; continue; }
-            const double resolution = (double)opt->resolution;                   // `float resolution = options_.resolution`
-            if (!(resolution > 0.)) { codes[j] = RGRID_ERR_INVALID; continue; }
-            const double half = 0.5 * n0 * resolution;
-            G_TRY(b, hipMemsetAsync(b->d_cells + cells_offset(b, s.grid), 0, sizeof(uint16_t) * (size_t)n0 * n0, b->stream));
-            g.set = true; g.nx = n0; g.ny = n0; g.resolution = resolution; g.max_x = (double)org2[0] + half; g.max_y = (double)org2[1] + half;
+            codes[j] = initial_submap_limits(opt->resolution, org2, (long long)b->max_cells, g.nx, g.ny, g.resolution, g.max_x, g.max_y);
+            if (codes[j] != RGRID_OK) continue;                                  // the slot stays unset
+            G_TRY(b, hipMemsetAsync(b->cells.d + cells_offset(b, s.grid), 0, sizeof(uint16_t) * (size_t)g.nx * g.ny, b->stream));
+            g.set = true;
         }
         rgrid_batch_insert_scan is;
         is.grid = s.grid; is.n_returns = S.n_fr; is.n_misses = S.n_fm;
@@ -2029,7 +1937,7 @@ int rgrid_batch_add_range_data(rgrid_batch_t *b, const rgrid_map_builder_options
         // range_data_in_local.returns = the RAW returns through pose_estimate.cast<float>() (:89-90): kgb_to_local's record
         ToLocalRec L;
         L.src_off = S.src_off; L.dst_off = S.dst_off = ndst; L.n = s.n_returns; L.pad = 0;
-        rigid2f_cs(yaw_of_quaternion_f32((float)pw, (float)pz), &L.c, &L.s);
+        rigid2f_cs(yaw_f32, &L.c, &L.s);
         L.tx = (float)est[0]; L.ty = (float)est[1];
         lrecs[nl] = L;
         for (int t = 0; t * KGL_THREADS < s.n_returns; ++t) wgmap[nwg++] = make_int2(nl, t);

@@ -7,9 +7,16 @@
 // discretisation's index formula and the first-maximum comparison are written out inside kg_discretize / kg_score / kg_best --
 // calling them through the two functions below changed kg_score's instruction schedule -- and cell_index_of / best_before restate
 // them for rgrid_batch.hip.  tests/test_fleet_match_gpu.py holds the two matchers together bit for bit.
-// The two range-data inserters (rgrid_insert / rgrid_grow_as_needed and kgb_insert) share the text at the end of this file.
+// The two range-data inserters (rgrid_insert / rgrid_grow_as_needed and kgb_insert) share the text further down.
+//
+// The host steps AROUND the kernels are one text too, called by both handles: the checks and the refinement's launch shape (below
+// G_TRY), insert_tables, the tables built on first use (resident_*), box_of_known / slice_max_of, and AddRangeData's compositions and
+// CreateGrid's limits at the end of this file (tests/cpp/range_data_host.cpp drives them without a GPU).  rgrid.hip's voxel filter, by the
+// same measurement as kg_score above: kg_keys and kg_keys_b call one body (voxel_keys: their instructions did not change), kg_first and
+// kg_first_b stay two texts -- through a common body, with or without __restrict__, both came out with an operand pair swapped.
 #pragma once
 #include "../../include/rgrid.h"
+#include "rgrid_refine_dev.h"
 
 #include <hip/hip_runtime.h>
 
@@ -29,6 +36,21 @@
     } while (0)
 
 namespace {
+
+// ---- what both handles refuse, ONE text (inline: a handle need not call every one); every comparison refuses a NaN option
+inline bool two_clouds_ok(const float *ret, int n_ret, const float *mis, int n_mis) { return n_ret >= 0 && n_mis >= 0 && (n_ret == 0 || ret) && (n_mis == 0 || mis); }
+inline bool refine_options_ok(const rgrid_refine_options *o) { return o->occupied_space_weight > 0. && o->translation_weight > 0. && o->rotation_weight > 0. && o->max_num_iterations >= 0; }
+inline bool insert_options_ok(float hit, float miss) { return hit > 0.f && hit < 1.f && miss > 0.f && miss < 1.f; }
+inline bool filter_options_ok(const rgrid_filter_options *o) { return o->voxel_filter_size > 0.f && o->adaptive_max_length > 0.; }
+// ---- the refinement's launch shape: RefineArgs without the poses, and the thread count: no idle waves in the barriers and the sums
+void refine_args(RefineArgs &A, int nx, int ny, double resolution, double max_x, double max_y, const rgrid_refine_options *opt, int n)
+{
+    std::memset(&A, 0, sizeof(A));
+    A.nx = nx; A.ny = ny; A.n = n; A.max_iter = opt->max_num_iterations; A.max_nonmono = opt->use_nonmonotonic_steps ? 5 : 0;
+    A.res = resolution; A.max_x = max_x; A.max_y = max_y;
+    A.w_occ = opt->occupied_space_weight; A.w_t = opt->translation_weight; A.w_r = opt->rotation_weight;
+}
+int refine_threads(int n) { const int t = ((n + 63) / 64) * 64; return t < 1024 ? t : 1024; }
 
 struct BestRec { float score; int id; };
 
@@ -208,6 +230,31 @@ void lookup_table(float probability, unsigned short *table)
     }
 }
 
+// A table on the device from the host's: allocates when d_table is null, uploads, and only then publishes the pointer -- a failed upload
+// frees what it allocated, so a table that is built on first use is built again by the next call
+template <typename T>
+hipError_t upload_table(T *&d_table, const T *table, size_t n)
+{
+    T *d = d_table;
+    hipError_t e = d ? hipSuccess : hipMalloc((void **)&d, sizeof(T) * n);
+    if (e == hipSuccess && (e = hipMemcpy(d, table, sizeof(T) * n, hipMemcpyHostToDevice)) == hipSuccess) d_table = d;
+    else if (d != d_table) (void)hipFree(d);
+    return e;
+}
+// The inserter's two resident tables (uint16[32768] each, allocated with the handle) for a (hit, miss) pair.  They only depend on the two
+// options: tab_hit_p / tab_miss_p remember the pair they hold and change only after BOTH uploads succeeded.
+hipError_t insert_tables(float hit, float miss, unsigned short *d_hit, unsigned short *d_miss, float &tab_hit_p, float &tab_miss_p)
+{
+    if (!(hit != tab_hit_p || miss != tab_miss_p)) return hipSuccess;
+    std::vector<unsigned short> t(32768);
+    lookup_table(hit, t.data());
+    hipError_t e = upload_table(d_hit, t.data(), t.size());
+    if (e != hipSuccess) return e;
+    lookup_table(miss, t.data());
+    if ((e = upload_table(d_miss, t.data(), t.size())) == hipSuccess) { tab_hit_p = hit; tab_miss_p = miss; }
+    return e;
+}
+
 // (value, alpha) of every cell value: 128 - ProbabilityToLogOddsInteger(GetProbability) (probability_grid.cc:97-114,
 // submaps.h:22-41), host float32 with the same libm a CPU build uses; entry = value | alpha << 8
 void texture_table(unsigned short *table)
@@ -226,6 +273,13 @@ void texture_table(unsigned short *table)
         const unsigned alpha = (unsigned)(delta > 0 ? 0 : -delta) & 255u, value = (unsigned)(delta > 0 ? delta : 0) & 255u;
         table[v] = (unsigned short)(value | ((value || alpha) ? alpha : 1u) << 8);
     }
+}
+hipError_t resident_texture_table(unsigned short *&d_table)
+{
+    if (d_table) return hipSuccess;
+    std::vector<unsigned short> t(32768);
+    texture_table(t.data());
+    return upload_table(d_table, t.data(), t.size());
 }
 
 // ---- occupancy grid and saved map: what rgrid_occupancy_grid (rgrid.hip) and rgrid_batch_occupancy_* (rgrid_batch.hip) share.
@@ -251,6 +305,27 @@ void occupancy_tables(signed char *occupancy, unsigned char *red)
         red[v] = (unsigned char)(over > 255u ? 255u : over);
         occupancy[v] = (value == 0u && alpha == 0u) ? (signed char)-1 : (signed char)std::lround((1. - red[v] / 255.) * 100.);
     }
+}
+hipError_t resident_occupancy_tables(unsigned char *&d_tables)                     // occupancy, then red: 2 * 32768 bytes
+{
+    if (d_tables) return hipSuccess;
+    std::vector<unsigned char> t(2 * 32768);
+    occupancy_tables(reinterpret_cast<signed char *>(t.data()), t.data() + 32768);
+    return upload_table(d_tables, t.data(), t.size());
+}
+
+// Grid2D::ComputeCroppedLimits' box (offset_x, offset_y, width, height) (grid_2d.cc:36-48) from the known cells' (min x, min y, max x,
+// max y) as kg_known_box leaves them; nothing known (max x < 0): offset 0, CellLimits(1, 1) (:39-44)
+inline void box_of_known(const int known[4], int box[4])
+{
+    const bool any = known[2] >= 0;
+    box[0] = any ? known[0] : 0; box[1] = any ? known[1] : 0; box[2] = any ? known[2] - known[0] + 1 : 1; box[3] = any ? known[3] - known[1] + 1 : 1;
+}
+// limits.max - resolution * (offset_y, offset_x): the translation of SubmapTexture::slice_pose (probability_grid.cc:122-123)
+inline void slice_max_of(const int box[4], double resolution, double max_x, double max_y, double slice_max[2])
+{
+#pragma clang fp contract(off)
+    slice_max[0] = max_x - resolution * box[1]; slice_max[1] = max_y - resolution * box[0];
 }
 
 // cairo_matrix_t and cairo_matrix_multiply(r, a, b) as cairo 1.16 writes them out: every cairo_scale / cairo_transform call
@@ -286,7 +361,8 @@ int occupancy_frame(const int box[4], double resolution, double max_x, double ma
 #pragma clang fp contract(off)
     const double r = resolution;
     // slice_pose = local_pose^-1 * Translation(slice_max) (probability_grid.cc:122-126), submap.pose * submap.slice_pose puts it back
-    const double slice_max[2] = {max_x - r * box[1], max_y - r * box[0]};
+    double slice_max[2];
+    slice_max_of(box, r, max_x, max_y, slice_max);
     const double t[2] = {(slice_max[0] - submap_origin[0]) + submap_origin[0], (slice_max[1] - submap_origin[1]) + submap_origin[1]};
     if (!(std::fabs(t[0] / r) < 16384.) || !(std::fabs(t[1] / r) < 16384.)) return RGRID_ERR_CAPACITY;
     CairoMatrix ctm = {1., 0., 0., 1., 0., 0.};
@@ -509,6 +585,48 @@ void rigid2f_apply(float tx, float ty, float yaw, const float *in, int n, float 
     float c, s;
     rigid2f_cs(yaw, &c, &s);
     for (int i = 0; i < n; ++i) rigid2f_point(c, s, tx, ty, in[2 * i], in[2 * i + 1], out[2 * i], out[2 * i + 1]);
+}
+
+// the caller's quaternion of an EKF yaw (src/ros_node.cc:548) and the gravity alignment's yaw (map_builder.cc:20-28): Rotation(q)
+// .cast<float>() -> Project2D -> GetYaw
+void gravity_alignment(double theta, double &qw, double &qz, float &yaw_g)
+{
+    qw = std::cos(theta / 2); qz = std::sin(theta / 2);
+    yaw_g = yaw_of_quaternion_f32((float)qw, (float)qz);
+}
+// What AddRangeData makes of ScanMatch's answer est (map_builder.cc:86-94).  pose_estimate = Embed3D(est) * gravity_alignment, a
+// quaternion product about z in double: local_pose is its projection, yaw_f32 the yaw of pose_estimate.cast<float>() (the raw returns);
+// yaw2 is the yaw of Embed3D(est.cast<float>()) (the filtered data): AngleAxisf -> Quaternionf, cos / sin of the float32 half angle.
+void compose_pose_estimate(const double est[3], double qw, double qz, double local_pose[3], float &yaw_f32, float &yaw2)
+{
+#pragma clang fp contract(off)
+    const double aw = std::cos(0.5 * est[2]), az = std::sin(0.5 * est[2]);
+    const double pw = aw * qw - az * qz, pz = aw * qz + az * qw;
+    local_pose[0] = est[0]; local_pose[1] = est[1]; local_pose[2] = yaw_of_quaternion_f64(pw, pz);
+    yaw_f32 = yaw_of_quaternion_f32((float)pw, (float)pz);
+    const float af = (float)est[2], ha = 0.5f * af;
+    yaw2 = yaw_of_quaternion_f32((float)std::cos((double)ha), (float)std::sin((double)ha));
+}
+// the scan's origin (tracking frame) in the local frame: through the gravity alignment, then through Embed3D(est.cast<float>())
+void origin_in_local(const float origin_xy[2], float yaw_g, const double est[3], float yaw2, float out[2])
+{
+    float org[2];
+    rigid2f_apply(0.f, 0.f, yaw_g, origin_xy, 1, org);
+    rigid2f_apply((float)est[0], (float)est[1], yaw2, org, 1, out);
+}
+// MapBuilder::CreateGrid (map_builder.cc:112-126): the limits of the submap the first inserted scan creates, kInitialSubmapSize = 100
+// cells a side around its origin in local; `float resolution = options_.resolution`.  RGRID_ERR_CAPACITY when the handle holds fewer
+// cells, RGRID_ERR_INVALID for a resolution that is not > 0 (NaN included); the outputs are untouched then.
+int initial_submap_limits(float options_resolution, const float origin_local[2], long long max_cells, int &nx, int &ny, double &resolution,
+                          double &max_x, double &max_y)
+{
+#pragma clang fp contract(off)
+    const int n0 = 100;
+    const double r = (double)options_resolution, half = 0.5 * n0 * r;
+    if ((long long)n0 * n0 > max_cells) return RGRID_ERR_CAPACITY;
+    if (!(r > 0.)) return RGRID_ERR_INVALID;
+    nx = n0; ny = n0; resolution = r; max_x = (double)origin_local[0] + half; max_y = (double)origin_local[1] + half;
+    return RGRID_OK;
 }
 
 }  // namespace

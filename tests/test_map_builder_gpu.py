@@ -86,3 +86,21 @@ def test_add_range_data_c_entry_point_equals_the_python_mirror():
         ga, la = mb.grid()
         assert fe.GetLimits() == la and np.array_equal(fe.GetGrid(), ga)
     fe.close()
+
+
+def test_a_resolution_that_is_not_positive_creates_no_submap():
+    """CreateGrid with options.resolution = 0 is refused with RGRID_ERR_INVALID, as the fleet handle refuses it, and leaves the handle
+    without a grid; the same scan with 0.05 then creates the 100 x 100 submap and is inserted."""
+    from reflector_ekf_slam_amd.grid import GridFrontEnd, RgridError
+    from reflector_ekf_slam_amd.map_builder import MapBuilderOptions
+    fe = GridFrontEnd(max_points=64, max_cells=10000)
+    ang = 2.0 * math.pi * np.arange(8) / 8
+    returns = np.stack([np.cos(ang), np.sin(ang)], 1).astype(np.float32)             # 8 returns on a 1 m circle, no misses
+    with pytest.raises(RgridError) as e:
+        fe.AddRangeData(MapBuilderOptions(resolution=0.0), np.zeros(2, np.float32), returns, None, (0.0, 0.0, 0.0))
+    assert e.value.code == -1
+    with pytest.raises(RgridError):
+        fe.GetLimits()
+    st, _, _ = fe.AddRangeData(MapBuilderOptions(resolution=0.05), np.zeros(2, np.float32), returns, None, (0.0, 0.0, 0.0))
+    assert st == 0 and fe.GetLimits()[:2] == (100, 100)                              # RGRID_SCAN_INSERTED
+    fe.close()
