@@ -32,6 +32,13 @@
  * SaveReflectorResult's positions and 2 x 2 blocks) is served for any list of members by ONE launch and without a copy of any
  * covariance matrix: rfleet_get_reflectors.
  *
+ * What the node publishes of the pose (src/ros_node.cc:627-660, :517-545: the pose with its 3 x 3 covariance and ekf_path_ after
+ * every odometry message and every scan that saw reflectors; StatePosetoRosPose :796-819) is served by the pose track: with
+ * rfleet_set_tracking on, the ONE launch of an rfleet_submit also leaves a record per message -- the pose, its covariance, n, the
+ * flags and the scan's match counts AFTER that message -- in pinned host memory, and rfleet_take_track hands the records over per
+ * member with one synchronisation and no launch.  A message the filter drops (stale odometry, odometry of a use_imu member) gets a
+ * record of the unchanged pose, as the node publishes it.
+ *
  * Deliberately OUT OF SCOPE (use a rekf handle): a map per member, a map of more than RFLEET_MAX_MAP_POINTS points, scans
  * wider than RFLEET_MAX_OBS, auto-grow, PredictState's landmark part (the full state).
  *
@@ -114,6 +121,43 @@ int rfleet_get_map_size(rfleet_t *f, int *M);
  * (Added without a new RFLEET_ABI_VERSION: a binding looks the call up by name.) */
 int rfleet_get_reflectors(rfleet_t *f, const int *members, int count,   /* members NULL = all B, in order */
                           int *counts /*[count]*/, double *ellipses5, double *xy2, double *cov4, long cap_rows);
+/* The pose track.  One record per message of a tracked rfleet_submit: the member's pose, pose covariance (column-major, as
+ * rfleet_get_poses), state dimension and sticky flags AFTER that message, and for a scan its match counts (zero otherwise).  The
+ * record of a member's last message of a call is what rfleet_get_poses reads behind that call, bit for bit.  dropped = 1: a message
+ * the filter ignores (odometry with t < state time, odometry of a use_imu member); its record repeats the state before it, and the
+ * member's state, time and last velocity stay untouched, as without tracking. */
+typedef struct rfleet_track_rec {
+    double t;            /* the message's stamp */
+    double mu3[3];
+    double sigma3x3[9];  /* column-major */
+    int member;
+    int kind;            /* RFLEET_EV_* */
+    int K;               /* SCAN: observations of the message */
+    int dropped;
+    int n;
+    int flags;
+    int n_state, n_map, n_new;
+    int pad_;
+} rfleet_track_rec;
+
+/* on != 0: every later rfleet_submit is tracked (ONE launch, as before; its ring segment holds 128 more bytes per message, and a call
+ * whose every message is dropped still launches, for the records).  Off at rfleet_create.  max_records bounds the HOST-side log per
+ * member: when a member's log is full the oldest record is discarded and counted; 0 = the default of 1024; a smaller bound than
+ * before trims at once.  Switching off keeps what is logged, records of calls already submitted included.  rfleet_set_state logs
+ * nothing.  REKF_ERR_INVALID for a null handle or max_records < 0; no HIP call, no synchronisation.
+ * (Added without a new RFLEET_ABI_VERSION: a binding looks the three calls up by name.) */
+int rfleet_set_tracking(rfleet_t *f, int on, long max_records);
+/* The records of the listed members, compact and in the order listed, each member's oldest first; they leave the log.  members NULL =
+ * all B members in order (count must be B).  Synchronises once, launches nothing.  counts[g] is written on success AND with
+ * REKF_ERR_BUFFER (the records do not fit cap_rows: out is not touched, nothing leaves the log, counts sizes the second call).
+ * out NULL: the call that asks for the counts (nothing leaves the log).  lost (nullable): lost[g] = records of members[g] discarded
+ * since the previous take that handed records over.  With tracking never switched on every count is zero.
+ * REKF_ERR_INVALID as rfleet_get_reflectors: a null handle, count < 0, count > 0 with null counts, cap_rows < 0, a member outside
+ * 0 .. B-1, a member listed twice, members NULL with count != B.  count == 0 with a list is REKF_OK and does nothing. */
+int rfleet_take_track(rfleet_t *f, const int *members, int count, int *counts /*[count]*/, rfleet_track_rec *out, long cap_rows,
+                      long *lost /*[count], nullable*/);
+/* sizeof(rfleet_track_rec) as the library was compiled */
+int rfleet_sizeof_track_rec(void);
 /* Wait for all enqueued work.  REKF_ERR_HIP when the device reported an error. */
 int rfleet_sync(rfleet_t *f);
 int rfleet_size(rfleet_t *f, int *B, int *max_landmarks);

@@ -13,4 +13,4 @@ from .grid import OccupancyGrid  # noqa: F401
 from .fleet_match import (FleetFilterResult, FleetOccupancyGrid, FleetRangeDataResult, FleetRefineResult, FleetScanMatchResult, FleetTexture,  # noqa: F401
                           RgridBatchFilterScan, RgridBatchInsertScan, RgridBatchRangeData, ScanMatchFleet, gravity_aligned_scans, pose_fixes)
 from .map_builder import FleetMapBuilder  # noqa: F401
-from .node_replay import FleetBackend, FleetNode  # noqa: F401
+from .node_replay import FleetBackend, FleetNode, pose_with_covariance  # noqa: F401

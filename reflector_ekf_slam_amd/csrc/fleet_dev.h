@@ -25,7 +25,7 @@
 struct FleetEvent {          // one Predict (+ scan) of one member, as the host packs it into the staging ring
     double dt;               // t - state time
     double vt[3];            // vt_ this Predict uses
-    int kind;                // 0 odometry (Predict only), 1 scan
+    int kind;                // 0 odometry (Predict only), 1 scan, 2 (tracked launches only) a message the host dropped: no Predict, a record
     int K;                   // observations (scan)
     int obs_off;             // index of the scan's first float in FleetLaunch::obs
     int fix_off;             // index of the scan's pose fix (x, y, yaw) in FleetLaunch::fix, -1: the scan has none
@@ -46,6 +46,16 @@ struct FleetMemberOpt { double lin_cov, ang_cov, obs_cov; int model; int pad_; }
 
 // what a launch leaves for the host in pinned memory, per member: read after a stream synchronisation, no copy of the state
 struct FleetPoseSlot { double mu3[3]; double C9[9]; int n; int flags; double pad_[3]; };
+
+// what a TRACKED launch leaves per packed event, in the launch's own ring segment (pinned host memory): the slot's content as it
+// would be if the launch ended behind that event, and the scan's match counts (zero for odometry).  One 128-byte line per event.
+struct alignas(128) FleetTrackRec {
+    double mu3[3]; double C9[9];
+    int n, flags;
+    int n_state, n_new, n_map;
+    int pad_[3];
+};
+static_assert(sizeof(FleetTrackRec) == 128, "one record is one 128-byte line");
 
 struct FleetDev {
     double *mu;              // [B][ld]
@@ -69,6 +79,8 @@ struct FleetLaunch {         // one rfleet_submit: G members with events, member
     const double *map_cov;   // [M_map][4], row-major 2 x 2
     const unsigned char *map_use;   // [B]: non-zero = the member matches against the map
     int M_map, pad2_;        // M_map > 0 selects k_fleet_step_map
+    // the pose track (k_fleet_step_track only; appended the same way)
+    FleetTrackRec *track;    // [events of the call]: event e writes track[e]; non-NULL selects k_fleet_step_track
 };
 
 hipError_t rfleet_launch_step(const FleetDev &d, const FleetLaunch &l, hipStream_t s);

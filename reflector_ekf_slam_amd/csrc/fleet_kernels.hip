@@ -115,6 +115,8 @@
 //   P  the scan's pose fix, if it has one and matched a reflector (gps.cc:305-340): a rank-3 step on what C-F left, see below
 //   G  augmentation rows and means (cc:311-364)
 // and, once per launch, the pose, pose block, n and flags into the member's slot in pinned host memory.
+// k_fleet_step_track (a handle that tracks, rfleet_set_tracking) also leaves ONE FleetTrackRec per event, at the end of every pass of
+// the event loop: what the slot would hold if the launch ended there, see fleet_track_write.
 //
 // FP64 MFMA operand layout (16x16x4): lane l supplies A[l & 15][l >> 4] and B[l >> 4][l & 15]; result register r of lane l is
 // D[(l >> 4) + 4 r][l & 15].  Phases E and F compute the TRANSPOSED tile (D = B-side rows along the lanes) so that the 16 lanes of
@@ -157,7 +159,27 @@ __device__ static inline double fleet_yaw_innovation(double delta_theta)
     return scale * z;
 }
 
-// The kernel's body stands once, below the `#else`, and is compiled three times by this file including itself: k_fleet_step for a
+// One event's record of a tracked launch: the pose, the pose block of the lower triangle, n, the flags and the scan's match counts,
+// staged in LDS and stored by lanes 0-15 of wave 0, 8 bytes each: ONE 128-byte line of the launch's ring segment in pinned host
+// memory.  The host sized the area for one record per packed event, so nothing counts and nothing can overflow.  The leading barrier
+// orders the reads behind the event's last write to s_mu, s_flags and P's corner (whichever phase that was); the next pass has
+// barriers of its own before anything here is staged again.
+__device__ static inline void fleet_track_write(FleetTrackRec *rec, double *s_trk, const double *s_mu, const double *P, int ld, int n,
+                                                const int *s_flags, int n_state, int n_new, int n_map)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();
+    if (tid < 3) s_trk[tid] = s_mu[tid];
+    else if (tid < 12) s_trk[tid] = rekf_plower(P, ld, (tid - 3) % 3, (tid - 3) / 3);
+    else if (tid == 12) {
+        int *q = (int *)(s_trk + 12);                       // FleetTrackRec's integers, in its order
+        q[0] = n; q[1] = *s_flags; q[2] = n_state; q[3] = n_new; q[4] = n_map; q[5] = 0; q[6] = 0; q[7] = 0;
+    }
+    __syncthreads();
+    if (tid < 16) ((double *)rec)[tid] = s_trk[tid];
+}
+
+// The kernel's body stands once, below the `#else`, and is compiled four times by this file including itself: k_fleet_step for a
 // launch in which no scan carries a fix (the host knows), k_fleet_step_fix otherwise, and k_fleet_step_map (map branch and phase P)
 // for a launch in which a member with events matches against a non-empty pre-loaded map, with or without fixes.  In the first two
 // every map statement is a discarded one and the map's LDS variables do not exist.  Phase P's statements stand once too, at the
@@ -166,44 +188,63 @@ __device__ static inline double fleet_yaw_innovation(double delta_theta)
 // discarded statements, and as a plain (non-template) kernel of that name it compiles to the code it had before phase P existed
 // (a template's instantiation does not: its LDS variables get other names and another layout, and the common path lost 0.7 %).
 // Both kernels compute a member's plain scans with the same arithmetic (tests/test_fleet_pose_gpu.py: the same bits beside
-// neighbours with and without fixes).
+// neighbours with and without fixes).  k_fleet_step_track is k_fleet_step_map's body plus the records, launched whenever the handle
+// tracks (a member without fix and map computes the same bits under that body: tests/test_fleet_map_gpu.py); in the other three every
+// tracking statement is a discarded one and s_trk does not exist.
 #define FLEET_STEP_KERNEL k_fleet_step
 #define FLEET_STEP_FIX false
 #define FLEET_STEP_MAP false
+#define FLEET_STEP_TRACK false
 #include "fleet_kernels.hip"
 #undef FLEET_STEP_KERNEL
 #undef FLEET_STEP_FIX
 #undef FLEET_STEP_MAP
+#undef FLEET_STEP_TRACK
 #define FLEET_STEP_KERNEL k_fleet_step_fix
 #define FLEET_STEP_FIX true
 #define FLEET_STEP_MAP false
+#define FLEET_STEP_TRACK false
 #include "fleet_kernels.hip"
 #undef FLEET_STEP_KERNEL
 #undef FLEET_STEP_FIX
 #undef FLEET_STEP_MAP
+#undef FLEET_STEP_TRACK
 #define FLEET_STEP_KERNEL k_fleet_step_map
 #define FLEET_STEP_FIX true
 #define FLEET_STEP_MAP true
+#define FLEET_STEP_TRACK false
 #include "fleet_kernels.hip"
 #undef FLEET_STEP_KERNEL
 #undef FLEET_STEP_FIX
 #undef FLEET_STEP_MAP
+#undef FLEET_STEP_TRACK
+#define FLEET_STEP_KERNEL k_fleet_step_track
+#define FLEET_STEP_FIX true
+#define FLEET_STEP_MAP true
+#define FLEET_STEP_TRACK true
+#include "fleet_kernels.hip"
+#undef FLEET_STEP_KERNEL
+#undef FLEET_STEP_FIX
+#undef FLEET_STEP_MAP
+#undef FLEET_STEP_TRACK
 
 hipError_t rfleet_launch_step(const FleetDev &d, const FleetLaunch &l, hipStream_t s)
 {
     if (l.G <= 0) return hipSuccess;
-    if (l.M_map > 0) hipLaunchKernelGGL(k_fleet_step_map, dim3((unsigned)l.G), dim3(RFLEET_THREADS), 0, s, d, l);
+    if (l.track) hipLaunchKernelGGL(k_fleet_step_track, dim3((unsigned)l.G), dim3(RFLEET_THREADS), 0, s, d, l);
+    else if (l.M_map > 0) hipLaunchKernelGGL(k_fleet_step_map, dim3((unsigned)l.G), dim3(RFLEET_THREADS), 0, s, d, l);
     else if (l.fix) hipLaunchKernelGGL(k_fleet_step_fix, dim3((unsigned)l.G), dim3(RFLEET_THREADS), 0, s, d, l);
     else hipLaunchKernelGGL(k_fleet_step, dim3((unsigned)l.G), dim3(RFLEET_THREADS), 0, s, d, l);
     return hipGetLastError();
 }
 
-#else  // ---- the kernel's body: FLEET_STEP_KERNEL, FLEET_STEP_FIX, FLEET_STEP_MAP
+#else  // ---- the kernel's body: FLEET_STEP_KERNEL, FLEET_STEP_FIX, FLEET_STEP_MAP, FLEET_STEP_TRACK
 
 __global__ __launch_bounds__(RFLEET_THREADS) void FLEET_STEP_KERNEL(FleetDev d, FleetLaunch L)
 {
     constexpr bool FIX = FLEET_STEP_FIX;
     constexpr bool MAP = FLEET_STEP_MAP;
+    constexpr bool TRACK = FLEET_STEP_TRACK;
     __shared__ double s_mu[FLEET_LD_MAX];
     __shared__ double s_S[64 * FLEET_SLD];
     __shared__ double s_hv[64][5];
@@ -220,6 +261,7 @@ __global__ __launch_bounds__(RFLEET_THREADS) void FLEET_STEP_KERNEL(FleetDev d, 
     __shared__ double s_cs[2];
     __shared__ double s_Gp[RFLEET_MAX_OBS_DEV][6], s_Sxi[9], s_RQR[4];
     __shared__ double s_p0[3], s_in2[3], s_Si2[9];       // phase P: the linearisation pose, innov2, S2^-1
+    __shared__ double s_trk[16];                          // one FleetTrackRec (k_fleet_step_track; unused and absent elsewhere)
     double *const s_W2 = s_S, *const s_K2 = s_S + 4 * FLEET_LD_MAX;     // phase P: W2, K2 as [4][FLEET_LD_MAX] (S^-1 is dead by then)
     static_assert(8 * FLEET_LD_MAX <= 64 * FLEET_SLD, "W2 and K2 live in S's space");
 
@@ -255,6 +297,12 @@ __global__ __launch_bounds__(RFLEET_THREADS) void FLEET_STEP_KERNEL(FleetDev d, 
         const int kind = s_ev.kind, K = s_ev.K, obs_off = s_ev.obs_off;    // (thread 0 rewrites s_ev at the top of the next event)
         int fix_off = -1;
         if constexpr (FIX) fix_off = s_ev.fix_off;
+        if constexpr (TRACK) {
+            if (kind == 2) {                              // a message the host dropped: nothing moves, the record is the state as it stands
+                fleet_track_write(L.track + e, s_trk, s_mu, P, (int)ld, n, &s_flags, 0, 0, 0);
+                continue;
+            }
+        }
         {
 #pragma clang fp contract(off)
             const double a = s_mo.a, b = s_mo.b;
@@ -277,10 +325,16 @@ __global__ __launch_bounds__(RFLEET_THREADS) void FLEET_STEP_KERNEL(FleetDev d, 
             }
         }
         __syncthreads();
-        if (kind != 1) continue;
+        if (kind != 1) {
+            if constexpr (TRACK) fleet_track_write(L.track + e, s_trk, s_mu, P, (int)ld, n, &s_flags, 0, 0, 0);
+            continue;
+        }
         rec_new = true; recK = K; rec_ns = 0; rec_nn = 0;
         if constexpr (MAP) rec_nm = 0;
-        if (K <= 0) continue;                                                         // cc:235-236: an empty scan is a Predict
+        if (K <= 0) {                                                                 // cc:235-236: an empty scan is a Predict
+            if constexpr (TRACK) fleet_track_write(L.track + e, s_trk, s_mu, P, (int)ld, n, &s_flags, 0, 0, 0);
+            continue;
+        }
 
         // ---- B: ReflectorMatch, state branch (cc:370-455)
         if (tid < 2 * K) s_obs[tid] = L.obs[obs_off + tid];
@@ -589,6 +643,7 @@ __global__ __launch_bounds__(RFLEET_THREADS) void FLEET_STEP_KERNEL(FleetDev d, 
             n += 2 * N2;                                                                      // cc:360-363
             __syncthreads();
         }
+        if constexpr (TRACK) fleet_track_write(L.track + e, s_trk, s_mu, P, (int)ld, n, &s_flags, rec_ns, rec_nn, rec_nm);
     }
 
     // ---- the member's state, record and host slot

@@ -13,10 +13,19 @@
 //
 // rfleet_get_reflectors is one launch of k_fleet_reflectors (fleet_reflectors.hip) behind whatever has been submitted, into a pinned
 // buffer sized at rfleet_create for B x max_landmarks rows, one synchronisation, and a host copy of the rows into the caller's arrays.
+//
+// The pose track (rfleet_set_tracking / rfleet_take_track).  A tracked submit appends one FleetTrackRec per packed event to its ring
+// segment and launches k_fleet_step_track, which fills them; the host keeps beside the segment what it knows of each event (stamp,
+// member, kind, K, dropped).  The messages the untracked path drops before packing (stale odometry, odometry of a use_imu member) are
+// packed as events of kind 2, which move nothing and only write their record.  Records move from a segment into the per-member host
+// log (bounded: the oldest goes, counted) wherever a segment's launch is known to have finished: before the segment is reused and in
+// rfleet_sync, which every getter calls -- oldest segment first, so a member's records stay in order.  The untracked submit keeps its
+// segment layout, its "every event dropped => no launch" and its kernels.
 #include "fleet_dev.h"
 #include "fleet_reflectors.h"
 #include "../../include/rfleet.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -24,6 +33,31 @@
 
 namespace {
 constexpr int kSegs = 8;
+constexpr long kTrackDefault = 1024;        // records per member the host log holds when rfleet_set_tracking is given 0
+
+// One member's host-side log: the records [head, buf.size()) of a vector that is appended to and, when the bound discards from the
+// front, compacted now and then -- no allocation per record.
+struct TrackLog {
+    std::vector<rfleet_track_rec> buf;
+    size_t head = 0;
+    size_t size() const { return buf.size() - head; }
+    void clear() { buf.clear(); head = 0; }
+    long trim(long max_records)             // -> records discarded
+    {
+        long gone = 0;
+        while ((long)size() > max_records) { ++head; ++gone; }
+        if (head >= 256 && head >= buf.size() / 2) {
+            buf.erase(buf.begin(), buf.begin() + (long)head);
+            head = 0;
+        }
+        return gone;
+    }
+};
+
+struct TrackMeta {                          // what the host knows of a packed event of a tracked submit
+    double t;
+    int member, kind, K, dropped;
+};
 
 struct Segment {
     char *host = nullptr;
@@ -31,6 +65,10 @@ struct Segment {
     size_t cap = 0;
     hipEvent_t done = nullptr;
     bool busy = false;
+    // a tracked submit: its records (n_track of them, in the segment at `track`) wait here until the launch is known to have finished
+    int n_track = 0;
+    const FleetTrackRec *track = nullptr;
+    std::vector<TrackMeta> meta;
 };
 }  // namespace
 
@@ -57,6 +95,12 @@ struct rfleet {
     std::vector<int> cnt, pos, order;
     std::vector<double> time_tmp, vt_tmp;
     std::vector<double> stage;
+    // the pose track: the switch, the bound per member, the per-member log and what it has discarded since the last take
+    bool tracking = false;
+    long track_max = kTrackDefault;
+    std::vector<TrackLog> track_log;
+    std::vector<long> track_lost;
+    std::vector<unsigned char> dropped;     // scratch of a tracked rfleet_submit: event i is one the untracked path drops
 };
 
 #define FLEET_HIP(f, call)                                                     \
@@ -69,6 +113,32 @@ struct rfleet {
     } while (0)
 
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+static size_t align128(size_t v) { return (v + 127) & ~(size_t)127; }
+
+static void track_push(rfleet *f, int member, const rfleet_track_rec &r)
+{
+    TrackLog &log = f->track_log[(size_t)member];
+    log.buf.push_back(r);
+    f->track_lost[(size_t)member] += log.trim(f->track_max);
+}
+
+// the records of a segment whose launch has finished, into the members' logs
+static void track_harvest(rfleet *f, Segment &s)
+{
+    for (int e = 0; e < s.n_track; ++e) {
+        const FleetTrackRec &d = s.track[e];
+        const TrackMeta &m = s.meta[(size_t)e];
+        rfleet_track_rec r{};
+        r.t = m.t;
+        memcpy(r.mu3, d.mu3, sizeof(r.mu3));
+        memcpy(r.sigma3x3, d.C9, sizeof(r.sigma3x3));
+        r.member = m.member; r.kind = m.kind; r.K = m.K; r.dropped = m.dropped;
+        r.n = d.n; r.flags = d.flags;
+        r.n_state = d.n_state; r.n_map = d.n_map; r.n_new = d.n_new;
+        track_push(f, m.member, r);
+    }
+    s.n_track = 0;
+}
 
 // the pinned buffer of rfleet_get_reflectors: byte offsets of its parts
 static size_t refl_rows(const rfleet *f) { return (size_t)f->B * (size_t)f->max_landmarks; }
@@ -83,6 +153,8 @@ extern "C" {
 int rfleet_abi_version(void) { return RFLEET_ABI_VERSION; }
 
 int rfleet_sizeof_event(void) { return (int)sizeof(rfleet_event); }
+
+int rfleet_sizeof_track_rec(void) { return (int)sizeof(rfleet_track_rec); }
 
 const char *rfleet_last_hip_error(rfleet_t *f) { return f ? f->hip_error.c_str() : ""; }
 
@@ -179,6 +251,8 @@ int rfleet_create(const rekf_options *opts, int B, int max_landmarks, int device
     f->pos.resize((size_t)B);
     f->map_use.assign((size_t)B, 0);
     f->map_rec.assign((size_t)B, 0);
+    f->track_log.resize((size_t)B);
+    f->track_lost.assign((size_t)B, 0);
     const int rc = fleet_create_body(f, opts);
     if (rc != REKF_OK) {
         rfleet_destroy(f);
@@ -201,7 +275,11 @@ int rfleet_sync(rfleet_t *f)
     if (!f) return REKF_ERR_INVALID;
     FLEET_HIP(f, hipSetDevice(f->device));
     FLEET_HIP(f, hipStreamSynchronize(f->stream));
-    for (Segment &s : f->seg) s.busy = false;
+    for (int i = 0; i < kSegs; ++i) {                                      // (from the oldest segment: a member's records stay in order)
+        Segment &s = f->seg[(f->next_seg + i) % kSegs];
+        s.busy = false;
+        if (s.n_track) track_harvest(f, s);
+    }
     return REKF_OK;
 }
 
@@ -226,6 +304,8 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     if (count == 0) return REKF_OK;
     // ---- which events reach the device (on a copy of the mirror: committed behind the launch)
     const int B = f->B;
+    const bool tracked = f->tracking;
+    if (tracked) f->dropped.assign((size_t)count, 0);
     f->time_tmp = f->time;
     f->vt_tmp = f->vt;
     f->order.clear();
@@ -238,8 +318,14 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
         const rfleet_event &e = ev[i];
         const int b = e.member;
         if (e.kind == RFLEET_EV_ODOM) {
-            if (f->opts[b].use_imu) continue;                              // cc:213-223: odometry is ignored with use_imu
-            if (e.t < f->time_tmp[b]) continue;                            // cc:211-212
+            if (f->opts[b].use_imu || e.t < f->time_tmp[b]) {              // cc:213-223: odometry is ignored with use_imu; cc:211-212
+                if (!tracked) continue;
+                f->dropped[(size_t)i] = 1;                                 // (the node still publishes the unchanged pose: a record, no Predict)
+                for (int k = 0; k < 4; ++k) dts[4 * (size_t)i + k] = 0.0;
+                f->cnt[b]++;
+                f->order.push_back(i);
+                continue;
+            }
             for (int k = 0; k < 3; ++k) f->vt_tmp[3 * b + k] = e.v[k];     // cc:216
         } else {
             n_obs += (size_t)e.K;
@@ -263,13 +349,16 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     // ---- a ring segment: members[G] | ev_begin[G + 1] | events[E] | fix[3 n_fix] | obs[2 n_obs]
     const size_t off_mem = 0, off_beg = align16(off_mem + sizeof(int) * G), off_ev = align16(off_beg + sizeof(int) * (G + 1));
     const size_t off_fix = align16(off_ev + sizeof(FleetEvent) * E), off_obs = align16(off_fix + sizeof(double) * 3 * n_fix);
-    const size_t need = align16(off_obs + sizeof(float) * 2 * n_obs + 16);
+    size_t need = align16(off_obs + sizeof(float) * 2 * n_obs + 16);
+    const size_t off_track = align128(need);                               // a tracked submit: | track[E], one 128-byte line each
+    if (tracked) need = off_track + sizeof(FleetTrackRec) * (size_t)E;
     FLEET_HIP(f, hipSetDevice(f->device));
     Segment &s = f->seg[f->next_seg];
     if (s.busy) {
         FLEET_HIP(f, hipEventSynchronize(s.done));
         s.busy = false;
     }
+    if (s.n_track) track_harvest(f, s);                                    // (the oldest segment: every later record comes behind these)
     if (s.cap < need) {
         size_t cap = s.cap ? s.cap : 4096;
         while (cap < need) cap *= 2;
@@ -300,10 +389,20 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     ev_begin[G] = acc;
     size_t obs_at = 0;
     int fix_at = 0;
+    if (tracked) s.meta.resize((size_t)E);
     for (int q = 0; q < E; ++q) {
         const int i = f->order[q];
         const rfleet_event &e = ev[i];
-        FleetEvent &pe = pev[f->pos[e.member]++];
+        const int at = f->pos[e.member]++;
+        FleetEvent &pe = pev[at];
+        if (tracked) {
+            const int dr = f->dropped[(size_t)i];
+            s.meta[(size_t)at] = TrackMeta{e.t, e.member, e.kind, e.kind == RFLEET_EV_SCAN ? e.K : 0, dr};
+            if (dr) {
+                pe = FleetEvent{0.0, {0.0, 0.0, 0.0}, 2, 0, (int)obs_at, -1};
+                continue;
+            }
+        }
         pe.dt = dts[4 * (size_t)i];
         for (int k = 0; k < 3; ++k) pe.vt[k] = dts[4 * (size_t)i + 1 + k];
         pe.kind = (e.kind == RFLEET_EV_SCAN) ? 1 : 0;
@@ -333,8 +432,13 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
         L.map_use = f->map_use_dev;
         L.M_map = f->M_map;
     }
+    if (tracked) L.track = (FleetTrackRec *)(s.dev + off_track);           // (non-NULL selects k_fleet_step_track, the map kernel's body)
     FLEET_HIP(f, rfleet_launch_step(f->dev, L, f->stream));
-    for (int b : f->scanned) f->map_rec[b] = with_map ? 1 : 0;
+    if (tracked) {
+        s.n_track = E;
+        s.track = (const FleetTrackRec *)(s.host + off_track);
+    }
+    for (int b : f->scanned) f->map_rec[b] = (with_map || tracked) ? 1 : 0;
     f->time.swap(f->time_tmp);
     f->vt.swap(f->vt_tmp);
     FLEET_HIP(f, hipEventRecord(s.done, f->stream));
@@ -512,6 +616,51 @@ int rfleet_get_map_size(rfleet_t *f, int *M)
 {
     if (!f || !M) return REKF_ERR_INVALID;
     *M = f->M_map;
+    return REKF_OK;
+}
+
+int rfleet_set_tracking(rfleet_t *f, int on, long max_records)
+{
+    if (!f || max_records < 0) return REKF_ERR_INVALID;
+    f->tracking = on != 0;
+    f->track_max = max_records ? max_records : kTrackDefault;
+    for (int b = 0; b < f->B; ++b) {                                       // a smaller bound holds for what is logged already
+        f->track_lost[(size_t)b] += f->track_log[(size_t)b].trim(f->track_max);
+    }
+    return REKF_OK;
+}
+
+int rfleet_take_track(rfleet_t *f, const int *members, int count, int *counts, rfleet_track_rec *out, long cap_rows, long *lost)
+{
+    if (!f || count < 0 || (count > 0 && !counts) || cap_rows < 0) return REKF_ERR_INVALID;
+    const int B = f->B;
+    if (!members && count != B) return REKF_ERR_INVALID;
+    if (members) {
+        if (count > B) return REKF_ERR_INVALID;                            // (more than B members: one is listed twice)
+        std::fill(f->cnt.begin(), f->cnt.end(), 0);
+        for (int g = 0; g < count; ++g) {
+            if (members[g] < 0 || members[g] >= B || f->cnt[members[g]]++) return REKF_ERR_INVALID;
+        }
+    }
+    if (count == 0) return REKF_OK;
+    const int rc = rfleet_sync(f);                                         // (harvests every outstanding segment)
+    if (rc != REKF_OK) return rc;
+    long rows = 0;
+    for (int g = 0; g < count; ++g) {
+        const int b = members ? members[g] : g;
+        counts[g] = (int)f->track_log[(size_t)b].size();
+        rows += counts[g];
+        if (lost) lost[g] = f->track_lost[(size_t)b];
+    }
+    if (!out) return REKF_OK;                                              // (no output given: the call that asks for the counts)
+    if (rows > cap_rows) return REKF_ERR_BUFFER;
+    for (int g = 0; g < count; ++g) {
+        const int b = members ? members[g] : g;
+        TrackLog &log = f->track_log[(size_t)b];
+        out = std::copy(log.buf.begin() + (long)log.head, log.buf.end(), out);
+        log.clear();
+        f->track_lost[(size_t)b] = 0;
+    }
     return REKF_OK;
 }
 

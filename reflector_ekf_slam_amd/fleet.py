@@ -11,6 +11,10 @@ What the node publishes after a scan comes from ONE more launch (k_fleet_reflect
 ``marker_ellipses()`` (ReflectorToRosMarkers' covariance ellipses), ``landmarks()`` and ``save_map_txt`` (SaveReflectorResult).
 The node's tick: detect -> predict_poses -> match -> fleet.submit -> marker_ellipses.
 
+The pose and path stream (the node publishes the pose with its covariance after every odometry message and every scan that saw
+reflectors) comes out of the step launch itself: after ``track()`` every ``submit`` also leaves one record per message -- the pose
+AFTER that message -- in pinned host memory, and ``take_track()`` reads them with one synchronisation and no launch.
+
 All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -75,6 +79,66 @@ def _declare_reflectors(L):
 
 
 _reflectors_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_get_reflectors",), (), _declare_reflectors)
+
+
+class RfleetTrackRec(C.Structure):
+    """struct rfleet_track_rec (include/rfleet.h)."""
+    _fields_ = [("t", C.c_double), ("mu3", C.c_double * 3), ("sigma3x3", C.c_double * 9), ("member", C.c_int), ("kind", C.c_int),
+                ("K", C.c_int), ("dropped", C.c_int), ("n", C.c_int), ("flags", C.c_int), ("n_state", C.c_int), ("n_map", C.c_int),
+                ("n_new", C.c_int), ("pad_", C.c_int)]
+
+
+TRACK_DTYPE = np.dtype([("t", "<f8"), ("mu3", "<f8", (3,)), ("sigma3x3", "<f8", (9,)), ("member", "<i4"), ("kind", "<i4"), ("K", "<i4"),
+                        ("dropped", "<i4"), ("n", "<i4"), ("flags", "<i4"), ("n_state", "<i4"), ("n_map", "<i4"), ("n_new", "<i4"),
+                        ("pad_", "<i4")])
+assert TRACK_DTYPE.itemsize == C.sizeof(RfleetTrackRec)
+
+
+def _declare_track(L):
+    """``rfleet()`` with the argtypes of the pose track's calls set.  They were added without a new ABI version and are looked up by
+    name: raises LibraryMissing when the built library has none; every other call keeps working then."""
+    L.rfleet_set_tracking.argtypes = [C.c_void_p, C.c_int, C.c_long]
+    L.rfleet_take_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+
+
+_track_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_set_tracking", "rfleet_take_track"), [("rfleet_sizeof_track_rec", RfleetTrackRec)],
+                          _declare_track)
+
+
+_TRACK_FIELDS = ("t", "kind", "K", "dropped", "mu", "sigma", "n", "flags", "n_state", "n_map", "n_new")
+
+
+class MemberTrack:
+    """One member's part of ``take_track``: R records, oldest first, each the member's state AFTER one message.
+
+        t [R]            the messages' stamps
+        kind [R]         EV_ODOM / EV_SCAN
+        K [R]            observations of a scan message
+        dropped [R]      1: a message the filter ignores (stale or use_imu odometry); the record repeats the state before it
+        mu [R, 3], sigma [R, 3, 3] (oriented as ``poses()`` returns it)
+        n [R], flags [R] state dimension and sticky REKF_FLAGBIT_* after the message
+        n_state, n_map, n_new [R]   the scan's match counts (zero for odometry)
+        lost             records the bounded log discarded since the previous take
+
+    The arrays are views of rows [at, at + R) of one array per field that the members of a take share, made when they are read."""
+    __slots__ = ("_cols", "_at", "_R", "lost")
+
+    def __init__(self, t, kind, K, dropped, mu, sigma, n, flags, n_state, n_map, n_new, lost=0, at=0, rows=None):
+        self._cols = (t, kind, K, dropped, mu, sigma, n, flags, n_state, n_map, n_new)
+        self._at = at
+        self._R = len(t) - at if rows is None else rows
+        self.lost = lost
+
+    def __len__(self):
+        return self._R
+
+
+def _track_field(i):
+    return property(lambda self: self._cols[i][self._at: self._at + self._R])
+
+
+for _i, _name in enumerate(_TRACK_FIELDS):
+    setattr(MemberTrack, _name, _track_field(_i))
 
 
 def odom_event(member, t, vx, vy, wz):
@@ -271,6 +335,45 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
         if self._map is None or (self._map[1] is not None and not self._map[1][int(i)]):
             return None
         return self._map[0]
+
+    # -- the pose track: every member's pose after every message, written by the step launch itself -----------------
+    def track(self, on: bool = True, max_records: int = 0):
+        """Switches the pose track on or off for every later ``submit``: the launch then also leaves one record per message in
+        pinned host memory (no further launch, no synchronisation).  ``max_records`` bounds the host-side log per member (0 = 1024):
+        when it is full the oldest record goes and is counted in ``lost``.  Switching off keeps what is logged."""
+        self._chk(_track_lib().rfleet_set_tracking(self._h, 1 if on else 0, int(max_records)), "rfleet_set_tracking")
+
+    def take_track_code(self, members, counts, out, cap_rows, lost) -> int:
+        """rfleet_take_track as it is (for tests): numpy arrays or None."""
+        mem = None if members is None else np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        count = self.B if mem is None else mem.shape[0]
+        return _track_lib().rfleet_take_track(self._h, None if mem is None else mem.ctypes.data, count,
+                                              None if counts is None else counts.ctypes.data, None if out is None else out.ctypes.data,
+                                              int(cap_rows), None if lost is None else lost.ctypes.data)
+
+    def take_track(self, members=None):
+        """-> a list of ``MemberTrack``, one per listed member (None = all, in order): the records logged since the previous take,
+        oldest first; they leave the log.  One synchronisation and no launch, whatever the number of members and messages."""
+        count = self.B if members is None else len(np.asarray(members).reshape(-1))
+        counts = np.zeros(max(count, 1), np.int32)
+        lost = np.zeros(max(count, 1), np.int64)
+        rc = self.take_track_code(members, counts, None, 0, None)                      # the sizing call
+        if rc != 0:
+            self._chk(rc, "rfleet_take_track")
+        rows = int(counts[:count].sum())
+        out = np.zeros(max(rows, 1), TRACK_DTYPE)
+        rc = self.take_track_code(members, counts, out, rows, lost)
+        if rc != 0:
+            self._chk(rc, "rfleet_take_track")
+        out = out[:rows]
+        cols = [np.ascontiguousarray(out[k]) for k in ("t", "kind", "K", "dropped", "mu3")]      # one copy per field, members are slices
+        cols.append(out["sigma3x3"].reshape(-1, 3, 3).transpose(0, 2, 1).copy())
+        cols += [np.ascontiguousarray(out[k]) for k in ("n", "flags", "n_state", "n_map", "n_new")]
+        res, at = [], 0
+        for k, ls in zip(counts[:count].tolist(), lost[:count].tolist()):
+            res.append(MemberTrack(*cols, ls, at, k))
+            at += k
+        return res
 
     # -- what the node publishes: the reflectors of any list of members in one launch ----------------
     def reflectors(self, members=None, ellipses=True, xy=False, cov=False):

@@ -224,12 +224,24 @@ def replay(dump: Dump, backend: Backend | None = None) -> Node:
     return node
 
 
+def pose_with_covariance(mu3, sigma3):
+    """The fields Node::StatePosetoRosPose (src/ros_node.cc:796-819) fills from a state: -> (position (x, y, 0), orientation
+    (x, y, z, w) = (0, 0, sin(theta / 2), cos(theta / 2)), covariance [36]) with exactly the entries 0, 1, 5, 6, 7, 11, 30, 31, 35 of the
+    row-major 6 x 6 set, from sigma(0..2, 0..2) in that order (:809-817), and zeros elsewhere."""
+    mu3 = np.asarray(mu3, np.float64).reshape(3)
+    sg = np.asarray(sigma3, np.float64).reshape(3, 3)
+    cov = np.zeros(36)
+    cov[[0, 1, 5, 6, 7, 11, 30, 31, 35]] = sg.reshape(-1)
+    return ((float(mu3[0]), float(mu3[1]), 0.0), (0.0, 0.0, math.sin(float(mu3[2]) / 2), math.cos(float(mu3[2]) / 2)), cov)
+
+
 # ------------------------------------------------------------------------------------------------ the node of a fleet
 @dataclass
 class FleetBackend:
     """Factories of the three fleets ``FleetNode`` owns: what ``Backend`` is to ``Node``."""
     make_detector_fleet: object    # ([ReflectorDetectOptions], sensor_to_base_link [B, 3]) -> HandleOdometryData(member, msg) / submit / collect / range_data
     make_filter_fleet: object      # ([EKFOptions]) -> set_state / set_map / submit / poses / n / marker_ellipses / save_map_txt
+                                   # (and track / take_track, for a FleetNode with pose_log=True only)
     make_map_builder: object       # (B) -> AddRangeData(times, range_datas, poses, members) / OccupancyGrids / SaveMap
 
 
@@ -256,6 +268,9 @@ class FleetReplayLog:
     match_results: list = field(default_factory=list)        # the MatchingResult itself (or None)
     mapper_inputs: list = field(default_factory=list)        # (stamp, RangeData, (x, y, yaw)): exactly what the mapper was given
     skipped: list = field(default_factory=list)              # (stamp, detector status) of every scan the detector refused
+    pose_log: list = field(default_factory=list)             # FleetNode(pose_log=True): (stamp, x, y, theta, sigma3x3) after every odometry
+                                                             # message of a member whose filter exists and every scan that saw reflectors,
+                                                             # in message order: ``Node``'s ``log.path`` with the covariance beside it
 
 
 class FleetNode:
@@ -276,12 +291,17 @@ class FleetNode:
     ``skipped`` and left out for that member -- the reference exits there.  A scan with more than ``fleet.MAX_OBS`` centres raises
     ValueError before anything is submitted to the filter: include/rfleet.h puts such scans out of scope.
 
+    ``pose_log=True``: the pose log after every odometry message (``Node`` keeps one in ``log.path``) is opt-in and costs no
+    synchronisation per message: the filter fleet's pose track is switched on (``fleet.track()``), the tick's ONE launch writes a
+    record per message, and ``logs[m].pose_log`` is filled from ``fleet.take_track()`` where the tick synchronises anyway (behind
+    ``poses()``) and once more at the end of ``run`` (``harvest_pose_log``); a tick of odometry only adds no synchronisation.  With
+    ``pose_log=False`` no tracking call reaches the backend.
+
     OUT OF SCOPE: the USE_GPS ordering of ScanCallback (:450-508: predict, match, then the update with the pose fix);
-    PointCloudCallback; a pose log after every odometry message (``Node`` keeps one: a ``poses()`` per message would be a
-    synchronisation per message); a device-to-device route from the detector's returns into rgrid_batch_add_range_data (the range
+    PointCloudCallback; a device-to-device route from the detector's returns into rgrid_batch_add_range_data (the range
     data crosses the host once per tick, DESIGN.md 10.11 "not built")."""
 
-    def __init__(self, metas, backend: FleetBackend | None = None):
+    def __init__(self, metas, backend: FleetBackend | None = None, pose_log: bool = False):
         from .detect import ReflectorDetectOptions
         from .ekf_slam import load_map_txt
         self.metas = [dict(m) for m in metas]
@@ -301,6 +321,9 @@ class FleetNode:
                                    [i for i, m in enumerate(self.metas) if m.get("map_path", "") == paths[0]])
         self.has_filter = [False] * self.B
         self.logs = [FleetReplayLog() for _ in range(self.B)]
+        self.pose_log = bool(pose_log)
+        if self.pose_log:
+            self.fleet.track(True)
 
     @staticmethod
     def _ekf_options(m):
@@ -353,6 +376,8 @@ class FleetNode:
             return []
         members = [m for m, _, _ in kept]
         _, mu, _ = self.fleet.poses()
+        if self.pose_log:
+            self.harvest_pose_log()                                                          # (the tick has synchronised: nothing waits)
         range_datas = self.detector.range_data(members)
         stamps = [float(sc.stamp) for _, sc, _ in kept]
         poses = [(float(mu[m, 0]), float(mu[m, 1]), float(mu[m, 2])) for m in members]
@@ -367,6 +392,15 @@ class FleetNode:
             log.match_poses.append(None if res is None else np.array(res.local_pose))
             log.match_results.append(res)
         return members
+
+    def harvest_pose_log(self):
+        """Moves the filter fleet's pose track into ``logs[m].pose_log``: every odometry record (a dropped one too: the node publishes
+        the unchanged pose, :640-660) and every scan record with reflectors in view (:524).  Synchronises."""
+        for m, tr in enumerate(self.fleet.take_track()):
+            log = self.logs[m].pose_log
+            for r in range(len(tr)):
+                if tr.kind[r] == 0 or tr.K[r] > 0:
+                    log.append((float(tr.t[r]), float(tr.mu[r, 0]), float(tr.mu[r, 1]), float(tr.mu[r, 2]), tr.sigma[r].copy()))
 
     # -- what the node hands out ------------------------------------------------------------------
     def markers(self, members=None):
@@ -409,6 +443,8 @@ class FleetNode:
                 ticks.setdefault(k, ([], []))[0].extend(od)
         for k in sorted(ticks):
             self.tick(*ticks[k])
+        if self.pose_log:
+            self.harvest_pose_log()
         return self.logs
 
 
