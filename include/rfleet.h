@@ -39,8 +39,14 @@
  * member with one synchronisation and no launch.  A message the filter drops (stale odometry, odometry of a use_imu member) gets a
  * record of the unchanged pose, as the node publishes it.
  *
+ * A scan of more than RFLEET_MAX_OBS observations (an open hall, a 360 degree lidar: both fleet detectors hand over up to 256
+ * centres) is served on a fleet that has called rfleet_set_wide_scans, up to RFLEET_MAX_OBS_WIDE: the scan is matched once and its
+ * pairs are applied in exact block steps of 32, which equals the reference's joint update (csrc/fleet_wide.hip).  A submit that
+ * holds such a scan takes one launch of a kernel of its own; every other submit launches what it always did.
+ *
  * Deliberately OUT OF SCOPE (use a rekf handle): a map per member, a map of more than RFLEET_MAX_MAP_POINTS points, scans
- * wider than RFLEET_MAX_OBS, auto-grow, PredictState's landmark part (the full state).
+ * wider than RFLEET_MAX_OBS on a fleet that has not called rfleet_set_wide_scans, wider than RFLEET_MAX_OBS_WIDE on one that has,
+ * auto-grow, PredictState's landmark part (the full state).
  *
  * The covariance of a member lives on the device as its lower triangle; the getters mirror it (as rekf_get_state does).
  */
@@ -56,6 +62,7 @@ extern "C" {
 #define RFLEET_ABI_VERSION 2
 #define RFLEET_MAX_LANDMARKS 128     /* per member: n <= 259 */
 #define RFLEET_MAX_OBS 32            /* per scan: one joint update, m <= 64 innovation rows */
+#define RFLEET_MAX_OBS_WIDE 256      /* per scan on a fleet with rfleet_set_wide_scans on: block steps of RFLEET_MAX_OBS pairs */
 #define RFLEET_MAX_MAP_POINTS 2048   /* the fleet's shared pre-loaded map */
 
 typedef struct rfleet rfleet_t;
@@ -80,8 +87,8 @@ void rfleet_destroy(rfleet_t *f);
 
 /* Any number of events for any subset of members; a member's events are applied in the order given
  * (HandleOdometryMessage / HandleObservationMessage each).  EVERYTHING is validated first: on an error return (a member out
- * of range, an unknown kind, K < 0, K > RFLEET_MAX_OBS = REKF_ERR_TOO_MANY_OBS, K > 0 with a null xy, has_pose_fix on an
- * odometry event, a non-finite component of a fix) no member has moved.
+ * of range, an unknown kind, K < 0, K > RFLEET_MAX_OBS = REKF_ERR_TOO_MANY_OBS (K > RFLEET_MAX_OBS_WIDE with rfleet_set_wide_scans
+ * on), K > 0 with a null xy, has_pose_fix on an odometry event, a non-finite component of a fix) no member has moved.
  * Packs the events into a pinned staging ring, enqueues ONE kernel launch and returns; consecutive calls do not synchronise. */
 int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count);
 
@@ -99,7 +106,8 @@ int rfleet_get_state(rfleet_t *f, int member, double *t, int *n, double *mu, lon
 /* As rekf_set_state: only the lower triangle of sigma is used; vt3 = nullable last odometry velocity. */
 int rfleet_set_state(rfleet_t *f, int member, double t, int n, const double *mu, const double *sigma, const double *vt3);
 /* The member's last scan: pairs are (observation, landmark); buffers hold RFLEET_MAX_OBS entries (pairs: twice that).
- * Any pointer may be NULL.  map_pairs are (observation, map point); *n_map is 0 for a member that does not use the map. */
+ * Any pointer may be NULL.  map_pairs are (observation, map point); *n_map is 0 for a member that does not use the map.
+ * When a count exceeds RFLEET_MAX_OBS (the record of a wide scan): REKF_ERR_BUFFER, the three counts written, no list touched. */
 int rfleet_get_last_match(rfleet_t *f, int member, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new, int *new_ids);
 /* map_ as LoadMapFromTxtFile leaves it, shared by the fleet: M points (float32 xy) and M row-major 2x2 weights, as rekf_set_map.
  * use[b] != 0: member b matches against it (NULL = every member).  M = 0 clears the map.  Synchronises, replaces the device copy;
@@ -156,6 +164,23 @@ int rfleet_set_tracking(rfleet_t *f, int on, long max_records);
  * 0 .. B-1, a member listed twice, members NULL with count != B.  count == 0 with a list is REKF_OK and does nothing. */
 int rfleet_take_track(rfleet_t *f, const int *members, int count, int *counts /*[count]*/, rfleet_track_rec *out, long cap_rows,
                       long *lost /*[count], nullable*/);
+/* Wide scans.  on != 0: every later rfleet_submit accepts scans of up to RFLEET_MAX_OBS_WIDE observations (K beyond that is
+ * REKF_ERR_TOO_MANY_OBS, validated before anything moves).  Off at rfleet_create: K > RFLEET_MAX_OBS is refused as ever.  Switching
+ * on allocates the members' wide match records (once) and launches nothing; switching off keeps the records readable.  A submit
+ * WITHOUT a scan wider than RFLEET_MAX_OBS launches exactly the kernel it launched before, switch on or off; one WITH such a scan is
+ * ONE launch of k_fleet_step_wide, which also carries the call's narrow scans, odometry and fixes, with the same bits for those.
+ * Per member: Predict and ReflectorMatch once over all K observations, the MM pairs in ceil(MM / 32) block steps (rows linearised
+ * at the state behind Predict, the innovation corrected by what the blocks before moved, the heading normalised once), the pose fix
+ * as a step of its own, the augmentation once (the first (n_max - n) / 2 new observations, REKF_FLAGBIT_CAPACITY beyond).
+ * REKF_ERR_INVALID for a null handle, REKF_ERR_HIP (rfleet_last_hip_error) when the records cannot be allocated.
+ * (Added without a new RFLEET_ABI_VERSION: a binding looks the three calls up by name.) */
+int rfleet_set_wide_scans(rfleet_t *f, int on);
+/* rfleet_get_last_match with caller-sized lists: they hold cap entries (pairs: 2 cap).  REKF_ERR_BUFFER when a count exceeds cap:
+ * the three counts are written and no list is touched.  Serves the records of narrow scans too. */
+int rfleet_get_last_match_wide(rfleet_t *f, int member, int cap, int *n_state, int *state_pairs, int *n_map, int *map_pairs,
+                               int *n_new, int *new_ids);
+/* Host counters since rfleet_create: launches of k_fleet_step_wide, scans with K > RFLEET_MAX_OBS submitted.  No HIP call. */
+int rfleet_wide_counts(rfleet_t *f, long *launches, long *scans);
 /* sizeof(rfleet_track_rec) as the library was compiled */
 int rfleet_sizeof_track_rec(void);
 /* Wait for all enqueued work.  REKF_ERR_HIP when the device reported an error. */

@@ -19,6 +19,8 @@
 #include "ekf_dev.h"
 
 #define RFLEET_MAX_OBS_DEV 32
+#define RFLEET_MAX_OBS_WIDE_DEV 256       // k_fleet_step_wide (fleet_wide.hip): observations of a wide scan
+#define RFLEET_MAX_NEW_WIDE_DEV 128       // ... and what it can append at once: (n_max - 3) / 2 at most
 #define RFLEET_PANEL_COLS 64
 #define RFLEET_THREADS 512
 
@@ -40,6 +42,16 @@ struct FleetMemberCtl {
     int state_pairs[2 * RFLEET_MAX_OBS_DEV];
     int new_ids[RFLEET_MAX_OBS_DEV];
     int map_pairs[2 * RFLEET_MAX_OBS_DEV];    // (observation, map point), k_fleet_step_map only
+};
+
+// The match record of a member whose last scan went through a WIDE launch (k_fleet_step_wide), narrow scans of that launch included:
+// a device array of its own [B], allocated by rfleet_set_wide_scans.  FleetMemberCtl keeps its layout; the host remembers per
+// member which kind of launch wrote its last record.
+struct FleetWideRec {
+    int K, n_state, n_map, n_new;
+    int state_pairs[2 * RFLEET_MAX_OBS_WIDE_DEV];
+    int map_pairs[2 * RFLEET_MAX_OBS_WIDE_DEV];
+    int new_ids[RFLEET_MAX_OBS_WIDE_DEV];
 };
 
 struct FleetMemberOpt { double lin_cov, ang_cov, obs_cov; int model; int pad_; };
@@ -84,3 +96,5 @@ struct FleetLaunch {         // one rfleet_submit: G members with events, member
 };
 
 hipError_t rfleet_launch_step(const FleetDev &d, const FleetLaunch &l, hipStream_t s);
+// a submit that holds a scan wider than RFLEET_MAX_OBS_DEV: k_fleet_step_wide, whatever l.fix, l.M_map and l.track say (fleet_wide.hip)
+hipError_t rfleet_launch_step_wide(const FleetDev &d, const FleetLaunch &l, FleetWideRec *wrec, hipStream_t s);

@@ -21,6 +21,11 @@
 // log (bounded: the oldest goes, counted) wherever a segment's launch is known to have finished: before the segment is reused and in
 // rfleet_sync, which every getter calls -- oldest segment first, so a member's records stay in order.  The untracked submit keeps its
 // segment layout, its "every event dropped => no launch" and its kernels.
+//
+// Wide scans (rfleet_set_wide_scans).  A submit that holds at least one scan of more than RFLEET_MAX_OBS observations launches
+// k_fleet_step_wide (fleet_wide.hip) instead of one of the four kernels above, with the same segment and the same FleetLaunch; every
+// other submit launches what it always did.  That kernel writes the match record of every member with a scan in the call into the
+// member's FleetWideRec, so the host remembers per member which kind of launch wrote its last record (rec_wide), as map_rec does.
 #include "fleet_dev.h"
 #include "fleet_reflectors.h"
 #include "../../include/rfleet.h"
@@ -101,6 +106,12 @@ struct rfleet {
     std::vector<TrackLog> track_log;
     std::vector<long> track_lost;
     std::vector<unsigned char> dropped;     // scratch of a tracked rfleet_submit: event i is one the untracked path drops
+    // wide scans: the switch, the members' wide match records (device, allocated when first switched on), who wrote each member's
+    // last record, and the host counters of rfleet_wide_counts
+    bool wide = false;
+    FleetWideRec *wide_rec = nullptr;
+    std::vector<unsigned char> rec_wide;
+    long wide_launches = 0, wide_scans = 0;
 };
 
 #define FLEET_HIP(f, call)                                                     \
@@ -178,6 +189,7 @@ void rfleet_destroy(rfleet_t *f)
     if (f->map_xy) (void)hipFree(f->map_xy);
     if (f->map_cov) (void)hipFree(f->map_cov);
     if (f->map_use_dev) (void)hipFree(f->map_use_dev);
+    if (f->wide_rec) (void)hipFree(f->wide_rec);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
@@ -251,6 +263,7 @@ int rfleet_create(const rekf_options *opts, int B, int max_landmarks, int device
     f->pos.resize((size_t)B);
     f->map_use.assign((size_t)B, 0);
     f->map_rec.assign((size_t)B, 0);
+    f->rec_wide.assign((size_t)B, 0);
     f->track_log.resize((size_t)B);
     f->track_lost.assign((size_t)B, 0);
     const int rc = fleet_create_body(f, opts);
@@ -287,13 +300,14 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
 {
     if (!f || count < 0 || (count > 0 && !ev)) return REKF_ERR_INVALID;
     // ---- validate everything before anything moves
+    const int max_obs = f->wide ? RFLEET_MAX_OBS_WIDE : RFLEET_MAX_OBS;
     for (int i = 0; i < count; ++i) {
         const rfleet_event &e = ev[i];
         if (e.member < 0 || e.member >= f->B) return REKF_ERR_INVALID;
         if (e.kind != RFLEET_EV_ODOM && e.kind != RFLEET_EV_SCAN) return REKF_ERR_INVALID;
         if (e.kind == RFLEET_EV_SCAN) {
             if (e.K < 0) return REKF_ERR_INVALID;
-            if (e.K > RFLEET_MAX_OBS) return REKF_ERR_TOO_MANY_OBS;
+            if (e.K > max_obs) return REKF_ERR_TOO_MANY_OBS;
             if (e.K > 0 && !e.xy) return REKF_ERR_INVALID;
             if (e.has_pose_fix && !(std::isfinite(e.pose_fix[0]) && std::isfinite(e.pose_fix[1]) && std::isfinite(e.pose_fix[2])))
                 return REKF_ERR_INVALID;
@@ -312,6 +326,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     f->scanned.clear();
     std::fill(f->cnt.begin(), f->cnt.end(), 0);
     size_t n_obs = 0, n_fix = 0;
+    long n_wide = 0;                                                       // scans of the call with K > RFLEET_MAX_OBS
     std::vector<double> &dts = f->stage;
     dts.resize((size_t)count * 4);
     for (int i = 0; i < count; ++i) {
@@ -330,6 +345,7 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
         } else {
             n_obs += (size_t)e.K;
             n_fix += e.has_pose_fix ? 1 : 0;
+            n_wide += e.K > RFLEET_MAX_OBS ? 1 : 0;
             f->scanned.push_back(b);
         }
         dts[4 * (size_t)i] = e.t - f->time_tmp[b];                         // cc:217-218 / :232-233
@@ -433,12 +449,20 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
         L.M_map = f->M_map;
     }
     if (tracked) L.track = (FleetTrackRec *)(s.dev + off_track);           // (non-NULL selects k_fleet_step_track, the map kernel's body)
-    FLEET_HIP(f, rfleet_launch_step(f->dev, L, f->stream));
+    if (n_wide > 0) FLEET_HIP(f, rfleet_launch_step_wide(f->dev, L, f->wide_rec, f->stream));   // (fix, map and track: chosen in the kernel)
+    else FLEET_HIP(f, rfleet_launch_step(f->dev, L, f->stream));
     if (tracked) {
         s.n_track = E;
         s.track = (const FleetTrackRec *)(s.host + off_track);
     }
-    for (int b : f->scanned) f->map_rec[b] = (with_map || tracked) ? 1 : 0;
+    for (int b : f->scanned) {
+        f->map_rec[b] = (with_map || tracked) ? 1 : 0;
+        f->rec_wide[b] = n_wide > 0 ? 1 : 0;
+    }
+    if (n_wide > 0) {
+        f->wide_launches += 1;
+        f->wide_scans += n_wide;
+    }
     f->time.swap(f->time_tmp);
     f->vt.swap(f->vt_tmp);
     FLEET_HIP(f, hipEventRecord(s.done, f->stream));
@@ -555,20 +579,74 @@ int rfleet_set_state(rfleet_t *f, int member, double t, int n, const double *mu,
     return REKF_OK;
 }
 
-int rfleet_get_last_match(rfleet_t *f, int member, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new, int *new_ids)
+// the member's last match record, whichever kind of launch wrote it: counts, then the lists if every count fits `cap`
+static int last_match_body(rfleet_t *f, int member, int cap, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new,
+                           int *new_ids)
 {
-    if (!f || member < 0 || member >= f->B) return REKF_ERR_INVALID;
+    if (!f || member < 0 || member >= f->B || cap < 0) return REKF_ERR_INVALID;
     const int rc = rfleet_sync(f);
     if (rc != REKF_OK) return rc;
+    int ns, nm, nn;
+    const int *sp, *mp, *nw;
     FleetMemberCtl c;
-    FLEET_HIP(f, hipMemcpy(&c, f->dev.ctl + member, sizeof(c), hipMemcpyDeviceToHost));
-    if (n_state) *n_state = c.n_state;
-    const int nm = f->map_rec[member] ? c.n_map : 0;                       // (only the map kernel writes the map part of a record)
+    std::vector<FleetWideRec> wr;
+    if (f->rec_wide[member]) {
+        wr.resize(1);
+        FLEET_HIP(f, hipMemcpy(wr.data(), f->wide_rec + member, sizeof(FleetWideRec), hipMemcpyDeviceToHost));
+        ns = wr[0].n_state; nm = wr[0].n_map; nn = wr[0].n_new;
+        sp = wr[0].state_pairs; mp = wr[0].map_pairs; nw = wr[0].new_ids;
+    } else {
+        FLEET_HIP(f, hipMemcpy(&c, f->dev.ctl + member, sizeof(c), hipMemcpyDeviceToHost));
+        ns = c.n_state; nn = c.n_new;
+        nm = f->map_rec[member] ? c.n_map : 0;                             // (only the map kernel writes the map part of a record)
+        sp = c.state_pairs; mp = c.map_pairs; nw = c.new_ids;
+    }
+    if (n_state) *n_state = ns;
     if (n_map) *n_map = nm;
-    if (map_pairs) memcpy(map_pairs, c.map_pairs, sizeof(int) * 2 * (size_t)nm);
-    if (n_new) *n_new = c.n_new;
-    if (state_pairs) memcpy(state_pairs, c.state_pairs, sizeof(int) * 2 * (size_t)c.n_state);
-    if (new_ids) memcpy(new_ids, c.new_ids, sizeof(int) * (size_t)c.n_new);
+    if (n_new) *n_new = nn;
+    if (ns > cap || nm > cap || nn > cap) return REKF_ERR_BUFFER;          // (the counts size the second call; no list is touched)
+    if (map_pairs) memcpy(map_pairs, mp, sizeof(int) * 2 * (size_t)nm);
+    if (state_pairs) memcpy(state_pairs, sp, sizeof(int) * 2 * (size_t)ns);
+    if (new_ids) memcpy(new_ids, nw, sizeof(int) * (size_t)nn);
+    return REKF_OK;
+}
+
+int rfleet_get_last_match(rfleet_t *f, int member, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new, int *new_ids)
+{
+    return last_match_body(f, member, RFLEET_MAX_OBS, n_state, state_pairs, n_map, map_pairs, n_new, new_ids);
+}
+
+int rfleet_get_last_match_wide(rfleet_t *f, int member, int cap, int *n_state, int *state_pairs, int *n_map, int *map_pairs, int *n_new,
+                               int *new_ids)
+{
+    return last_match_body(f, member, cap, n_state, state_pairs, n_map, map_pairs, n_new, new_ids);
+}
+
+int rfleet_set_wide_scans(rfleet_t *f, int on)
+{
+    if (!f) return REKF_ERR_INVALID;
+    if (on && !f->wide_rec) {                                              // (allocates once; launches nothing)
+        FLEET_HIP(f, hipSetDevice(f->device));
+        FleetWideRec *p = nullptr;
+        FLEET_HIP(f, hipMalloc((void **)&p, sizeof(FleetWideRec) * (size_t)f->B));
+        hipError_t e_ = hipMemset(p, 0, sizeof(FleetWideRec) * (size_t)f->B);
+        if (e_ == hipSuccess) e_ = hipDeviceSynchronize();                 // (the handle's stream does not wait for the null stream)
+        if (e_ != hipSuccess) {
+            (void)hipFree(p);
+            f->hip_error = std::string("rfleet_set_wide_scans: ") + hipGetErrorString(e_);
+            return REKF_ERR_HIP;
+        }
+        f->wide_rec = p;
+    }
+    f->wide = on != 0;
+    return REKF_OK;
+}
+
+int rfleet_wide_counts(rfleet_t *f, long *launches, long *scans)
+{
+    if (!f) return REKF_ERR_INVALID;
+    if (launches) *launches = f->wide_launches;
+    if (scans) *scans = f->wide_scans;
     return REKF_OK;
 }
 

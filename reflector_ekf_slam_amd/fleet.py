@@ -15,6 +15,10 @@ The pose and path stream (the node publishes the pose with its covariance after 
 reflectors) comes out of the step launch itself: after ``track()`` every ``submit`` also leaves one record per message -- the pose
 AFTER that message -- in pinned host memory, and ``take_track()`` reads them with one synchronisation and no launch.
 
+A scan of more than ``MAX_OBS`` observations is refused unless the fleet was made with ``wide_scans=True`` (or ``wide_scans()`` was
+called): then scans of up to ``MAX_OBS_WIDE`` observations are taken, applied in exact block steps of 32 pairs by a kernel of its own
+(k_fleet_step_wide), which a submit launches only when it holds such a scan; ``wide_counts()`` tells how often that happened.
+
 All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -29,6 +33,7 @@ from .ekf_slam import Map, ReflectorMatchResult, RekfError, State, loaded_map_ro
 RFLEET_ABI_VERSION = 2        # must equal RFLEET_ABI_VERSION of include/rfleet.h and rfleet_abi_version() of the built library
 MAX_LANDMARKS = 128
 MAX_OBS = 32
+MAX_OBS_WIDE = 256            # per scan on a fleet with wide scans switched on (RFLEET_MAX_OBS_WIDE)
 MAX_MAP_POINTS = 2048
 EV_ODOM, EV_SCAN = 0, 1
 
@@ -79,6 +84,19 @@ def _declare_reflectors(L):
 
 
 _reflectors_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_get_reflectors",), (), _declare_reflectors)
+
+
+def _declare_wide(L):
+    """``rfleet()`` with the argtypes of the wide-scan calls set.  They were added without a new ABI version and are looked up by
+    name: raises LibraryMissing when the built library has none; every other call keeps working then."""
+    ip = C.POINTER(C.c_int)
+    L.rfleet_set_wide_scans.argtypes = [C.c_void_p, C.c_int]
+    L.rfleet_get_last_match_wide.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_void_p, ip, C.c_void_p, ip, C.c_void_p]
+    L.rfleet_wide_counts.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+
+
+_wide_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_set_wide_scans", "rfleet_get_last_match_wide", "rfleet_wide_counts"), (),
+                         _declare_wide)
 
 
 class RfleetTrackRec(C.Structure):
@@ -156,8 +174,9 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
     """B independent ekf::ReflectorEKFSLAM filters on one MI355X, one kernel launch per ``submit``."""
     _destroy = "rfleet_destroy"
     _map = None                   # (Map, per-member switch or None) of the last successful set_map
+    _wide = False                 # wide_scans() has been called: records may be wider than MAX_OBS
 
-    def __init__(self, options_list, max_landmarks: int = MAX_LANDMARKS, device: int = 0):
+    def __init__(self, options_list, max_landmarks: int = MAX_LANDMARKS, device: int = 0, wide_scans: bool = False):
         self._L = rfleet()
         self._h = None
         self.options = list(options_list)
@@ -180,6 +199,8 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
         self._h = h
         self.B = B
         self.max_landmarks = int(max_landmarks)
+        if wide_scans:
+            self.wide_scans(True)
 
     def __len__(self):
         return self.B
@@ -292,13 +313,33 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
                   "rfleet_set_state")
 
     def last_match(self, i: int) -> ReflectorMatchResult:
-        sp = np.zeros((MAX_OBS, 2), np.int32)
-        mp = np.zeros((MAX_OBS, 2), np.int32)
-        nw = np.zeros((MAX_OBS,), np.int32)
+        """The member's last scan (a wide one too: the lists are sized for ``MAX_OBS_WIDE`` once wide scans were switched on)."""
+        cap = MAX_OBS_WIDE if self._wide else MAX_OBS
+        sp = np.zeros((cap, 2), np.int32)
+        mp = np.zeros((cap, 2), np.int32)
+        nw = np.zeros((cap,), np.int32)
         ns, nm, nn = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self._L.rfleet_get_last_match(self._h, int(i), C.byref(ns), sp.ctypes.data, C.byref(nm), mp.ctypes.data,
-                                                C.byref(nn), nw.ctypes.data), "rfleet_get_last_match")
+        if self._wide:
+            self._chk(_wide_lib().rfleet_get_last_match_wide(self._h, int(i), cap, C.byref(ns), sp.ctypes.data, C.byref(nm),
+                                                             mp.ctypes.data, C.byref(nn), nw.ctypes.data), "rfleet_get_last_match_wide")
+        else:
+            self._chk(self._L.rfleet_get_last_match(self._h, int(i), C.byref(ns), sp.ctypes.data, C.byref(nm), mp.ctypes.data,
+                                                    C.byref(nn), nw.ctypes.data), "rfleet_get_last_match")
         return ReflectorMatchResult(mp[: nm.value].copy(), sp[: ns.value].copy(), nw[: nn.value].copy())
+
+    # -- wide scans -----------------------------------------------------------------
+    def wide_scans(self, on: bool = True):
+        """Switches wide scans on or off for every later ``submit``: on, a scan may hold up to ``MAX_OBS_WIDE`` observations (more
+        raises, before anything moves); off (the default), more than ``MAX_OBS`` raises as ever.  Switching on allocates the members'
+        wide match records and launches nothing; a submit without a wide scan launches exactly what it launched before."""
+        self._chk(_wide_lib().rfleet_set_wide_scans(self._h, 1 if on else 0), "rfleet_set_wide_scans")
+        self._wide = self._wide or bool(on)                  # (records written while it was on stay readable)
+
+    def wide_counts(self):
+        """-> (launches of k_fleet_step_wide, scans wider than ``MAX_OBS`` submitted) since the fleet was made.  Host counters."""
+        a, b = C.c_long(), C.c_long()
+        self._chk(_wide_lib().rfleet_wide_counts(self._h, C.byref(a), C.byref(b)), "rfleet_wide_counts")
+        return int(a.value), int(b.value)
 
     # -- the shared pre-loaded map ------------------------------------------------
     def set_map_code(self, xy, cov, members=None) -> int:
@@ -469,6 +510,10 @@ class FleetMember:
 
     def last_match(self) -> ReflectorMatchResult:
         return self.fleet.last_match(self.index)
+
+    def wide_scans(self, on: bool = True):
+        """The switch is the fleet's: it holds for every member."""
+        self.fleet.wide_scans(on)
 
     def marker_ellipses(self) -> np.ndarray:
         return self.fleet.marker_ellipses([self.index])[0]

@@ -105,7 +105,8 @@ def cloud_events(clouds, observations):
 def scan_events(scans, observations):
     """The ``ReflectorEKFSLAMFleet.submit`` events of one tick: ``scans`` as given to ``submit`` ([(member, LaserScan), ...]),
     ``observations`` as ``collect`` returned them ([(status, Observation), ...]).  One ``fleet.scan_event`` per scan with status 0;
-    nothing is truncated (a scan with more than RFLEET_MAX_OBS centres is the fleet filter's REKF_ERR_TOO_MANY_OBS: the caller's call)."""
+    nothing is truncated (a scan with more than RFLEET_MAX_OBS centres is the fleet filter's REKF_ERR_TOO_MANY_OBS unless the filter
+    fleet has wide scans switched on, ``ReflectorEKFSLAMFleet.wide_scans``, which takes the detector's 256: the caller's call)."""
     scans, observations = list(scans), list(observations)
     if len(scans) != len(observations):
         raise ValueError("one observation per scan")

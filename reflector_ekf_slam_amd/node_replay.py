@@ -289,7 +289,12 @@ class FleetNode:
     ``map_path`` of a meta is served by the filter fleet's ONE shared map (``load_map_txt`` -> ``set_map`` for the members that name
     it): two different non-empty paths in one fleet raise ValueError.  A scan the detector refuses (status != 0) is logged in
     ``skipped`` and left out for that member -- the reference exits there.  A scan with more than ``fleet.MAX_OBS`` centres raises
-    ValueError before anything is submitted to the filter: include/rfleet.h puts such scans out of scope.
+    ValueError before anything is submitted to the filter: include/rfleet.h puts such scans out of scope on a fleet that has not
+    switched wide scans on.
+
+    ``wide_scans=True`` switches them on (``fleet.wide_scans()``): scans of up to ``fleet.MAX_OBS_WIDE`` centres -- as many as the
+    detector fleets hand over -- go through, in the tick's ONE submit, which then launches k_fleet_step_wide; more than that raises
+    ValueError.  With ``wide_scans=False`` no wide call reaches the backend.
 
     ``pose_log=True``: the pose log after every odometry message (``Node`` keeps one in ``log.path``) is opt-in and costs no
     synchronisation per message: the filter fleet's pose track is switched on (``fleet.track()``), the tick's ONE launch writes a
@@ -301,7 +306,7 @@ class FleetNode:
     PointCloudCallback; a device-to-device route from the detector's returns into rgrid_batch_add_range_data (the range
     data crosses the host once per tick, DESIGN.md 10.11 "not built")."""
 
-    def __init__(self, metas, backend: FleetBackend | None = None, pose_log: bool = False):
+    def __init__(self, metas, backend: FleetBackend | None = None, pose_log: bool = False, wide_scans: bool = False):
         from .detect import ReflectorDetectOptions
         from .ekf_slam import load_map_txt
         self.metas = [dict(m) for m in metas]
@@ -324,6 +329,9 @@ class FleetNode:
         self.pose_log = bool(pose_log)
         if self.pose_log:
             self.fleet.track(True)
+        self.wide_scans = bool(wide_scans)
+        if self.wide_scans:
+            self.fleet.wide_scans(True)
 
     @staticmethod
     def _ekf_options(m):
@@ -361,8 +369,9 @@ class FleetNode:
             for (m, sc), (status, obs) in zip(later, observations):
                 if status != 0:
                     self.logs[m].skipped.append((float(sc.stamp), int(status)))
-                elif obs.cloud_.shape[0] > F.MAX_OBS:
-                    raise ValueError(f"member {m}: {obs.cloud_.shape[0]} centres in one scan, the fleet filter takes {F.MAX_OBS}")
+                elif obs.cloud_.shape[0] > (F.MAX_OBS_WIDE if self.wide_scans else F.MAX_OBS):
+                    raise ValueError(f"member {m}: {obs.cloud_.shape[0]} centres in one scan, the fleet filter takes "
+                                     f"{F.MAX_OBS_WIDE if self.wide_scans else F.MAX_OBS}")
                 else:
                     kept.append((m, sc, obs))
             events += scan_events(later, observations)
