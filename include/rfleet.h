@@ -44,6 +44,11 @@
  * pairs are applied in exact block steps of 32, which equals the reference's joint update (csrc/fleet_wide.hip).  A submit that
  * holds such a scan takes one launch of a kernel of its own; every other submit launches what it always did.
  *
+ * A service hands its state over and takes it back as a fleet (a checkpoint, robots that move to another fleet, yesterday's maps with
+ * their full covariances): rfleet_snapshot packs the full states of any list of members -- n, flags, time, velocity, mean and the
+ * covariance's lower triangle -- into one self-describing blob with ONE launch, and rfleet_restore puts a blob's entries into any
+ * members of any fleet whose capacity holds them with ONE launch, zeros beyond n included (csrc/fleet_snapshot.hip).
+ *
  * Deliberately OUT OF SCOPE (use a rekf handle): a map per member, a map of more than RFLEET_MAX_MAP_POINTS points, scans
  * wider than RFLEET_MAX_OBS on a fleet that has not called rfleet_set_wide_scans, wider than RFLEET_MAX_OBS_WIDE on one that has,
  * auto-grow, PredictState's landmark part (the full state).
@@ -183,6 +188,53 @@ int rfleet_get_last_match_wide(rfleet_t *f, int member, int cap, int *n_state, i
 int rfleet_wide_counts(rfleet_t *f, long *launches, long *scans);
 /* sizeof(rfleet_track_rec) as the library was compiled */
 int rfleet_sizeof_track_rec(void);
+/* Snapshot and restore of full member states.  A snapshot is ONE caller-owned blob of bytes, position-independent and self-describing
+ * (it can be written to a file as it is): rfleet_snapshot_hdr, then `count` rfleet_snapshot_member entries in the order listed, then
+ * per entry at byte offset `off` its doubles -- mu[0:n], then the packed lower triangle of the covariance, n (n + 1) / 2 doubles,
+ * column-major: column j holds rows j .. n-1 -- the payloads in the entries' order, one behind the other without gaps.  A member's
+ * whole state is that, its sticky flags and the host's time and last odometry velocity: the fleet holds zeros beyond n. */
+#define RFLEET_SNAPSHOT_MAGIC "RFLTSNAP"   /* the header's 8 bytes, no terminator */
+#define RFLEET_SNAPSHOT_VERSION 1
+typedef struct rfleet_snapshot_hdr {
+    char magic[8];
+    int version;         /* RFLEET_SNAPSHOT_VERSION */
+    int count;           /* entries */
+    long bytes;          /* the blob's size */
+} rfleet_snapshot_hdr;
+typedef struct rfleet_snapshot_member {
+    double t;            /* state time */
+    double vt[3];        /* last odometry velocity */
+    int member;          /* the index it was taken from */
+    int n;               /* state dimension 3 + 2 L */
+    int flags;           /* sticky REKF_FLAGBIT_* */
+    int pad_;
+    long off;            /* byte offset of the member's doubles from the blob's start, a multiple of 8 */
+} rfleet_snapshot_member;
+/* The listed members' states into out, in the order listed (members NULL = all B members in order, count must be B).  Every event
+ * submitted before the call is in the snapshot; the call changes nothing in the fleet.  Synchronises (the pose slots hold each member's
+ * n), enqueues ONE launch of k_fleet_pack (csrc/fleet_snapshot.hip) whatever count is, copies the payload out and synchronises again; the
+ * host writes the header and the entries.  *bytes = the blob's size, always written on REKF_OK and REKF_ERR_BUFFER.  out NULL: only
+ * *bytes is written and nothing is launched.  cap_bytes < *bytes: REKF_ERR_BUFFER, out untouched.
+ * REKF_ERR_INVALID before any HIP call and before the handle is read: a null handle, count < 0, null bytes, cap_bytes < 0; after the
+ * handle is read and before any HIP call: a member outside 0 .. B-1, a member listed twice, members NULL with count != B.  count == 0
+ * with a list is REKF_OK: a blob of the header alone.  (Added without a new RFLEET_ABI_VERSION: a binding looks the calls up by name.) */
+int rfleet_snapshot(rfleet_t *f, const int *members, int count, void *out, long cap_bytes, long *bytes);
+/* Entry g of the blob becomes member members[g] (members NULL: the index it was taken from); count must equal the blob's count.
+ * EVERYTHING is validated on the host before anything moves and before any HIP call -- the blob as rfleet_snapshot_peek does, every n
+ * <= the TARGET fleet's 3 + 2 max_landmarks, targets inside 0 .. B-1 and distinct -- and a refused call (REKF_ERR_INVALID) leaves every
+ * member as it was.  Then: one synchronisation, one copy of the payload to the device, ONE launch of k_fleet_unpack, one synchronisation.
+ * A target then holds n, flags, mu[0:n] and the triangle from the blob, ZERO beyond n (as a member created fresh and grown to that
+ * state), its pose slot as rfleet_get_poses reads it, the blob's time and velocity, and a last-match record of zero counts.  The pose
+ * track logs nothing; members not listed keep every bit; the fleet's map, options, tracking and wide-scan switches are not touched.
+ * REKF_ERR_HIP when the device staging buffer cannot be allocated: nothing has moved. */
+int rfleet_restore(rfleet_t *f, const void *blob, long bytes, const int *members, int count);
+/* The validation of a blob alone, pure host, no handle: the magic, the version, `bytes` against the header, every entry's n odd,
+ * >= 3 and <= 3 + 2 RFLEET_MAX_LANDMARKS, its member >= 0, its off a multiple of 8, at or behind the end of the entry before it (the
+ * first: of the entries) and its payload inside the blob.  count, max_n (0 for an empty blob): nullable.  REKF_ERR_INVALID otherwise. */
+int rfleet_snapshot_peek(const void *blob, long bytes, int *count, int *max_n);
+/* sizeof(rfleet_snapshot_member) / sizeof(rfleet_snapshot_hdr) as the library was compiled */
+int rfleet_sizeof_snapshot_member(void);
+int rfleet_sizeof_snapshot_hdr(void);
 /* Wait for all enqueued work.  REKF_ERR_HIP when the device reported an error. */
 int rfleet_sync(rfleet_t *f);
 int rfleet_size(rfleet_t *f, int *B, int *max_landmarks);

@@ -7,7 +7,7 @@ synthetic session generator (``synth``) and the session driver (``session``).
 """
 from .ekf_slam import (DIFF, OMNI, EKFOptions, Map, Observation, OdometryData,  # noqa: F401
                        ReflectorEKFSLAM, ReflectorMatchResult, RekfError, State)
-from .fleet import ReflectorEKFSLAMFleet  # noqa: F401
+from .fleet import FleetSnapshot, ReflectorEKFSLAMFleet  # noqa: F401
 from .fleet_detect import LaserReflectorDetectFleet, PointCloud, PointCloudReflectorDetectFleet, cloud_events, scan_events  # noqa: F401
 from .grid import OccupancyGrid  # noqa: F401
 from .fleet_match import (FleetFilterResult, FleetOccupancyGrid, FleetRangeDataResult, FleetRefineResult, FleetScanMatchResult, FleetTexture,  # noqa: F401

@@ -26,8 +26,15 @@
 // k_fleet_step_wide (fleet_wide.hip) instead of one of the four kernels above, with the same segment and the same FleetLaunch; every
 // other submit launches what it always did.  That kernel writes the match record of every member with a scan in the call into the
 // member's FleetWideRec, so the host remembers per member which kind of launch wrote its last record (rec_wide), as map_rec does.
+//
+// Snapshot and restore (rfleet_snapshot / rfleet_restore / rfleet_snapshot_peek).  The blob's header and entries are written and read
+// by the host; the payloads move between the members' arrays and ONE device staging buffer (allocated on first use, grown to what a
+// call needs, freed in rfleet_destroy) by one launch of k_fleet_pack / k_fleet_unpack (fleet_snapshot.hip) over a host-built table of
+// (member, panel) records that sits in front of the payload in the same buffer.  Every copy goes through the handle's stream and is
+// followed by a synchronisation: the stream is non-blocking, so a legacy hipMemcpy would not be ordered behind it.
 #include "fleet_dev.h"
 #include "fleet_reflectors.h"
+#include "fleet_snapshot.h"
 #include "../../include/rfleet.h"
 
 #include <algorithm>
@@ -112,6 +119,11 @@ struct rfleet {
     FleetWideRec *wide_rec = nullptr;
     std::vector<unsigned char> rec_wide;
     long wide_launches = 0, wide_scans = 0;
+    // snapshot / restore: the device staging buffer (table | payload), and the host's scratch for the table and the payload offsets
+    char *snap_dev = nullptr;
+    size_t snap_cap = 0;
+    std::vector<FleetSnapRec> snap_rec;
+    std::vector<long> snap_off;
 };
 
 #define FLEET_HIP(f, call)                                                     \
@@ -190,6 +202,7 @@ void rfleet_destroy(rfleet_t *f)
     if (f->map_cov) (void)hipFree(f->map_cov);
     if (f->map_use_dev) (void)hipFree(f->map_use_dev);
     if (f->wide_rec) (void)hipFree(f->wide_rec);
+    if (f->snap_dev) (void)hipFree(f->snap_dev);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
@@ -782,6 +795,205 @@ int rfleet_get_reflectors(rfleet_t *f, const int *members, int count, int *count
     if (ellipses5) memcpy(ellipses5, f->refl_host, sizeof(double) * 5 * (size_t)rows);
     if (xy2) memcpy(xy2, f->refl_host + refl_off_xy(f), sizeof(double) * 2 * (size_t)rows);
     if (cov4) memcpy(cov4, f->refl_host + refl_off_cov(f), sizeof(double) * 4 * (size_t)rows);
+    return REKF_OK;
+}
+
+int rfleet_sizeof_snapshot_member(void) { return (int)sizeof(rfleet_snapshot_member); }
+
+int rfleet_sizeof_snapshot_hdr(void) { return (int)sizeof(rfleet_snapshot_hdr); }
+
+// entry g of a blob (a blob need not be aligned: a file's bytes)
+static rfleet_snapshot_member snap_entry(const void *blob, int g)
+{
+    rfleet_snapshot_member m;
+    memcpy(&m, (const char *)blob + sizeof(rfleet_snapshot_hdr) + sizeof(m) * (size_t)g, sizeof(m));
+    return m;
+}
+
+// what rfleet_snapshot_peek promises of a blob; pure host
+static int snap_validate(const void *blob, long bytes, rfleet_snapshot_hdr *hdr, int *max_n)
+{
+    if (!blob || bytes < (long)sizeof(rfleet_snapshot_hdr)) return REKF_ERR_INVALID;
+    rfleet_snapshot_hdr h;
+    memcpy(&h, blob, sizeof(h));
+    if (memcmp(h.magic, RFLEET_SNAPSHOT_MAGIC, sizeof(h.magic)) != 0 || h.version != RFLEET_SNAPSHOT_VERSION) return REKF_ERR_INVALID;
+    if (h.count < 0 || h.bytes != bytes) return REKF_ERR_INVALID;
+    long end = (long)sizeof(h) + (long)sizeof(rfleet_snapshot_member) * h.count;
+    if (end > bytes) return REKF_ERR_INVALID;
+    int widest = 0;
+    for (int g = 0; g < h.count; ++g) {
+        const rfleet_snapshot_member m = snap_entry(blob, g);
+        if (m.n < 3 || !(m.n & 1) || m.n > 3 + 2 * RFLEET_MAX_LANDMARKS || m.member < 0) return REKF_ERR_INVALID;
+        if (m.off < end || (m.off & 7)) return REKF_ERR_INVALID;          // (in order: behind the entries and behind the payload before it)
+        const long size = (long)sizeof(double) * fleet_snap_doubles(m.n);
+        if (m.off > bytes - size) return REKF_ERR_INVALID;
+        end = m.off + size;
+        widest = std::max(widest, m.n);
+    }
+    if (hdr) *hdr = h;
+    if (max_n) *max_n = widest;
+    return REKF_OK;
+}
+
+// the device staging buffer holds `need` bytes; a failed allocation leaves the old one in place
+static int snap_reserve(rfleet_t *f, size_t need)
+{
+    if (f->snap_cap >= need) return REKF_OK;
+    size_t cap = f->snap_cap ? f->snap_cap : (size_t)1 << 16;
+    while (cap < need) cap *= 2;
+    char *p = nullptr;
+    FLEET_HIP(f, hipMalloc((void **)&p, cap));
+    if (f->snap_dev) (void)hipFree(f->snap_dev);
+    f->snap_dev = p;
+    f->snap_cap = cap;
+    return REKF_OK;
+}
+
+int rfleet_snapshot_peek(const void *blob, long bytes, int *count, int *max_n)
+{
+    rfleet_snapshot_hdr h;
+    const int rc = snap_validate(blob, bytes, &h, max_n);
+    if (rc == REKF_OK && count) *count = h.count;
+    return rc;
+}
+
+int rfleet_snapshot(rfleet_t *f, const int *members, int count, void *out, long cap_bytes, long *bytes)
+{
+    if (!f || count < 0 || !bytes || cap_bytes < 0) return REKF_ERR_INVALID;
+    const int B = f->B;
+    if (!members && count != B) return REKF_ERR_INVALID;
+    if (members) {
+        if (count > B) return REKF_ERR_INVALID;                            // (more than B members: one is listed twice)
+        std::fill(f->cnt.begin(), f->cnt.end(), 0);
+        for (int g = 0; g < count; ++g) {
+            if (members[g] < 0 || members[g] >= B || f->cnt[members[g]]++) return REKF_ERR_INVALID;
+        }
+    }
+    const long head = (long)sizeof(rfleet_snapshot_hdr) + (long)sizeof(rfleet_snapshot_member) * count;
+    long total = head;
+    if (count > 0) {
+        const int rc = rfleet_sync(f);                                     // (the pose slots hold every member's n and flags)
+        if (rc != REKF_OK) return rc;
+        f->snap_off.resize((size_t)count);
+        for (int g = 0; g < count; ++g) {
+            const int n = f->pose_host[members ? members[g] : g].n;
+            if (n < 3 || n > f->n_max) {
+                f->hip_error = "rfleet_snapshot: a member's pose slot holds a state dimension outside 3 .. n_max";
+                return REKF_ERR_HIP;
+            }
+            f->snap_off[(size_t)g] = total;
+            total += (long)sizeof(double) * fleet_snap_doubles(n);
+        }
+    }
+    *bytes = total;
+    if (!out) return REKF_OK;                                              // (the call that asks for the size)
+    if (cap_bytes < total) return REKF_ERR_BUFFER;
+    rfleet_snapshot_hdr h;
+    memcpy(h.magic, RFLEET_SNAPSHOT_MAGIC, sizeof(h.magic));
+    h.version = RFLEET_SNAPSHOT_VERSION;
+    h.count = count;
+    h.bytes = total;
+    if (count > 0) {
+        f->snap_rec.clear();
+        for (int g = 0; g < count; ++g) {
+            const int b = members ? members[g] : g;
+            const int n = f->pose_host[b].n;
+            const long off = (f->snap_off[(size_t)g] - head) / (long)sizeof(double);
+            for (int p = 0; p < (n + RFLEET_SNAP_PANEL - 1) / RFLEET_SNAP_PANEL; ++p) f->snap_rec.push_back(FleetSnapRec{b, p, n, 0, off});
+        }
+        const size_t table = align128(sizeof(FleetSnapRec) * f->snap_rec.size()), payload = (size_t)(total - head);
+        FLEET_HIP(f, hipSetDevice(f->device));
+        const int rr = snap_reserve(f, table + payload);
+        if (rr != REKF_OK) return rr;
+        FleetSnapLaunch L{};
+        L.rec = (const FleetSnapRec *)f->snap_dev;
+        L.buf = (double *)(f->snap_dev + table);
+        L.cap = (long)(payload / sizeof(double));
+        L.count = (int)f->snap_rec.size();
+        FLEET_HIP(f, hipMemcpyAsync(f->snap_dev, f->snap_rec.data(), sizeof(FleetSnapRec) * f->snap_rec.size(), hipMemcpyHostToDevice, f->stream));
+        FLEET_HIP(f, rfleet_launch_pack(f->dev, L, f->stream));
+        FLEET_HIP(f, hipMemcpyAsync((char *)out + head, L.buf, payload, hipMemcpyDeviceToHost, f->stream));
+        const int rc = rfleet_sync(f);
+        if (rc != REKF_OK) return rc;
+    }
+    memcpy(out, &h, sizeof(h));
+    for (int g = 0; g < count; ++g) {
+        const int b = members ? members[g] : g;
+        rfleet_snapshot_member m;
+        memset(&m, 0, sizeof(m));
+        m.t = f->time[(size_t)b];
+        for (int k = 0; k < 3; ++k) m.vt[k] = f->vt[3 * (size_t)b + k];
+        m.member = b;
+        m.n = f->pose_host[b].n;
+        m.flags = f->pose_host[b].flags;
+        m.off = f->snap_off[(size_t)g];
+        memcpy((char *)out + sizeof(h) + sizeof(m) * (size_t)g, &m, sizeof(m));
+    }
+    return REKF_OK;
+}
+
+int rfleet_restore(rfleet_t *f, const void *blob, long bytes, const int *members, int count)
+{
+    if (!f || !blob || bytes < 0 || count < 0) return REKF_ERR_INVALID;
+    rfleet_snapshot_hdr h;
+    const int rv = snap_validate(blob, bytes, &h, nullptr);
+    if (rv != REKF_OK) return rv;
+    const int B = f->B;
+    if (count != h.count || count > B) return REKF_ERR_INVALID;            // (more than B entries: two share a target)
+    std::fill(f->cnt.begin(), f->cnt.end(), 0);
+    for (int g = 0; g < count; ++g) {
+        const rfleet_snapshot_member m = snap_entry(blob, g);
+        const int b = members ? members[g] : m.member;
+        if (m.n > f->n_max || b < 0 || b >= B || f->cnt[b]++) return REKF_ERR_INVALID;
+    }
+    if (count == 0) return REKF_OK;
+    const int rc = rfleet_sync(f);                                         // no launch touches a target any more
+    if (rc != REKF_OK) return rc;
+    // ---- the payload's span in the blob, the table of (target, panel of the target's ld) records
+    const rfleet_snapshot_member first = snap_entry(blob, 0), last = snap_entry(blob, count - 1);
+    const long lo = first.off, hi = last.off + (long)sizeof(double) * fleet_snap_doubles(last.n);
+    const int panels = f->ld / RFLEET_SNAP_PANEL;
+    f->snap_rec.clear();
+    for (int g = 0; g < count; ++g) {
+        const rfleet_snapshot_member m = snap_entry(blob, g);
+        const int b = members ? members[g] : m.member;
+        for (int p = 0; p < panels; ++p) f->snap_rec.push_back(FleetSnapRec{b, p, m.n, m.flags, (m.off - lo) / (long)sizeof(double)});
+    }
+    const size_t table = align128(sizeof(FleetSnapRec) * f->snap_rec.size()), payload = (size_t)(hi - lo);
+    FLEET_HIP(f, hipSetDevice(f->device));
+    const int rr = snap_reserve(f, table + payload);
+    if (rr != REKF_OK) return rr;
+    FleetSnapLaunch L{};
+    L.rec = (const FleetSnapRec *)f->snap_dev;
+    L.buf = (double *)(f->snap_dev + table);
+    L.cap = (long)(payload / sizeof(double));
+    L.count = (int)f->snap_rec.size();
+    FLEET_HIP(f, hipMemcpyAsync(f->snap_dev, f->snap_rec.data(), sizeof(FleetSnapRec) * f->snap_rec.size(), hipMemcpyHostToDevice, f->stream));
+    FLEET_HIP(f, hipMemcpyAsync(L.buf, (const char *)blob + lo, payload, hipMemcpyHostToDevice, f->stream));
+    FLEET_HIP(f, rfleet_launch_unpack(f->dev, L, f->stream));
+    const int rs = rfleet_sync(f);
+    if (rs != REKF_OK) return rs;
+    // ---- the host's part of a member: time, velocity, the pose slot as a launch would have left it, who wrote its match record
+    for (int g = 0; g < count; ++g) {
+        const rfleet_snapshot_member m = snap_entry(blob, g);
+        const int b = members ? members[g] : m.member;
+        const char *pay = (const char *)blob + m.off;
+        FleetPoseSlot &p = f->pose_host[b];
+        memcpy(p.mu3, pay, sizeof(p.mu3));
+        for (int j = 0; j < 3; ++j)
+            for (int i = j; i < 3; ++i) {
+                double v;
+                memcpy(&v, pay + sizeof(double) * (size_t)(m.n + ((long)j * m.n - (long)j * (j - 1) / 2) + (i - j)), sizeof(v));
+                p.C9[i + 3 * j] = v;
+                p.C9[j + 3 * i] = v;
+            }
+        p.n = m.n;
+        p.flags = m.flags;
+        f->time[(size_t)b] = m.t;
+        for (int k = 0; k < 3; ++k) f->vt[3 * (size_t)b + k] = m.vt[k];
+        f->map_rec[(size_t)b] = 0;
+        f->rec_wide[(size_t)b] = 0;
+    }
     return REKF_OK;
 }
 

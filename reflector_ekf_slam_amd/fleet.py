@@ -19,6 +19,11 @@ A scan of more than ``MAX_OBS`` observations is refused unless the fleet was mad
 called): then scans of up to ``MAX_OBS_WIDE`` observations are taken, applied in exact block steps of 32 pairs by a kernel of its own
 (k_fleet_step_wide), which a submit launches only when it holds such a scan; ``wide_counts()`` tells how often that happened.
 
+The fleet's own state goes out and comes back as a fleet: ``snapshot(members)`` packs the listed members' full states (n, flags, time,
+velocity, mean, the covariance's lower triangle) into one ``FleetSnapshot`` blob with ONE launch (k_fleet_pack), ``restore(snap, members)``
+puts a blob's entries into any members of any fleet whose capacity holds them with ONE launch (k_fleet_unpack), zeros beyond n included:
+a checkpoint (``save`` / ``load``), robots that move between fleets, a fleet seeded from yesterday's maps.
+
 All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -121,6 +126,109 @@ def _declare_track(L):
 
 _track_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_set_tracking", "rfleet_take_track"), [("rfleet_sizeof_track_rec", RfleetTrackRec)],
                           _declare_track)
+
+
+class RfleetSnapshotHdr(C.Structure):
+    """struct rfleet_snapshot_hdr (include/rfleet.h)."""
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_int), ("count", C.c_int), ("bytes", C.c_long)]
+
+
+class RfleetSnapshotMember(C.Structure):
+    """struct rfleet_snapshot_member (include/rfleet.h)."""
+    _fields_ = [("t", C.c_double), ("vt", C.c_double * 3), ("member", C.c_int), ("n", C.c_int), ("flags", C.c_int), ("pad_", C.c_int),
+                ("off", C.c_long)]
+
+
+SNAPSHOT_MAGIC = b"RFLTSNAP"
+SNAPSHOT_VERSION = 1
+SNAPSHOT_HDR_DTYPE = np.dtype([("magic", "S8"), ("version", "<i4"), ("count", "<i4"), ("bytes", "<i8")])
+SNAPSHOT_MEMBER_DTYPE = np.dtype([("t", "<f8"), ("vt", "<f8", (3,)), ("member", "<i4"), ("n", "<i4"), ("flags", "<i4"), ("pad_", "<i4"),
+                                  ("off", "<i8")])
+assert SNAPSHOT_HDR_DTYPE.itemsize == C.sizeof(RfleetSnapshotHdr) and SNAPSHOT_MEMBER_DTYPE.itemsize == C.sizeof(RfleetSnapshotMember)
+
+
+def _declare_snapshot(L):
+    """``rfleet()`` with the argtypes of the snapshot calls set.  They were added without a new ABI version and are looked up by
+    name: raises LibraryMissing when the built library has none; every other call keeps working then."""
+    lp = C.POINTER(C.c_long)
+    L.rfleet_snapshot.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_long, lp]
+    L.rfleet_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
+    L.rfleet_snapshot_peek.argtypes = [C.c_void_p, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+
+
+_snapshot_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_snapshot", "rfleet_restore", "rfleet_snapshot_peek"),
+                             [("rfleet_sizeof_snapshot_member", RfleetSnapshotMember), ("rfleet_sizeof_snapshot_hdr", RfleetSnapshotHdr)],
+                             _declare_snapshot)
+
+
+class FleetSnapshot:
+    """The full states of some members of a fleet as ONE blob of bytes (``blob``, np.uint8; the layout is include/rfleet.h's): what
+    ``ReflectorEKFSLAMFleet.snapshot`` returns and ``restore`` takes.  Entry g is the g-th member listed.  Views of the blob:
+
+        members [G]      the index each entry was taken from
+        t [G], vt [G, 3] state time and last odometry velocity
+        n [G], flags [G] state dimension and sticky REKF_FLAGBIT_* bits
+        mu(g) [n]        the mean
+        triangle(g)      the covariance's packed lower triangle, n (n + 1) / 2 doubles, column-major: column j holds rows j .. n-1
+
+    and, computed on demand, ``sigma(g)`` (the mirrored dense matrix) and ``state(g)`` (a ``State``).  ``save(path)`` writes the
+    blob's bytes and nothing else; ``FleetSnapshot.load(path)`` reads and validates them."""
+
+    def __init__(self, blob, validate: bool = True):
+        self.blob = blob if (type(blob) is np.ndarray and blob.dtype == np.uint8 and blob.ndim == 1 and blob.flags.c_contiguous) \
+            else np.frombuffer(bytes(blob), np.uint8).copy()
+        if validate:
+            count, max_n = C.c_int(), C.c_int()
+            rc = _snapshot_lib().rfleet_snapshot_peek(self.blob.ctypes.data if self.blob.size else None, self.blob.size,
+                                                      C.byref(count), C.byref(max_n))
+            if rc != 0:
+                raise RekfError(rc, "rfleet_snapshot_peek")
+        hdr = self.blob[:SNAPSHOT_HDR_DTYPE.itemsize].view(SNAPSHOT_HDR_DTYPE)[0]
+        self._entries = self.blob[SNAPSHOT_HDR_DTYPE.itemsize:][: int(hdr["count"]) * SNAPSHOT_MEMBER_DTYPE.itemsize].view(SNAPSHOT_MEMBER_DTYPE)
+
+    def __len__(self):
+        return self._entries.shape[0]
+
+    members = property(lambda self: self._entries["member"])
+    t = property(lambda self: self._entries["t"])
+    vt = property(lambda self: self._entries["vt"])
+    n = property(lambda self: self._entries["n"])
+    flags = property(lambda self: self._entries["flags"])
+
+    @property
+    def max_n(self) -> int:
+        return int(self.n.max()) if len(self) else 0
+
+    def _doubles(self, g, at, k):
+        off = int(self._entries["off"][g]) + 8 * at
+        return self.blob[off: off + 8 * k].view(np.float64)
+
+    def mu(self, g: int) -> np.ndarray:
+        return self._doubles(g, 0, int(self.n[g]))
+
+    def triangle(self, g: int) -> np.ndarray:
+        n = int(self.n[g])
+        return self._doubles(g, n, n * (n + 1) // 2)
+
+    def sigma(self, g: int) -> np.ndarray:
+        n = int(self.n[g])
+        s = np.zeros((n, n))
+        cols, rows = np.triu_indices(n)                     # (row-major order of the upper triangle = column-major of the lower)
+        s[rows, cols] = self.triangle(g)
+        s[cols, rows] = s[rows, cols]
+        return s
+
+    def state(self, g: int) -> State:
+        return State(float(self.t[g]), self.mu(g).copy(), self.sigma(g))
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            f.write(self.blob.tobytes())
+
+    @classmethod
+    def load(cls, path) -> "FleetSnapshot":
+        with open(path, "rb") as f:
+            return cls(np.frombuffer(f.read(), np.uint8).copy())
 
 
 _TRACK_FIELDS = ("t", "kind", "K", "dropped", "mu", "sigma", "n", "flags", "n_state", "n_map", "n_new")
@@ -415,6 +523,51 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
             res.append(MemberTrack(*cols, ls, at, k))
             at += k
         return res
+
+    # -- the fleet's own state: out as one blob with one launch, back in with one launch -----------------
+    def snapshot_code(self, members, out, cap_bytes, size) -> int:
+        """rfleet_snapshot as it is (for tests): numpy arrays or None, ``size`` a ctypes.c_long."""
+        mem = None if members is None else np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        count = self.B if mem is None else mem.shape[0]
+        if count == 0:
+            mem = np.zeros(1, np.int32)                      # (an empty list is still a list: a pointer that is not NULL)
+        return _snapshot_lib().rfleet_snapshot(self._h, None if mem is None else mem.ctypes.data, count,
+                                               None if out is None else out.ctypes.data, int(cap_bytes), C.byref(size))
+
+    def snapshot(self, members=None) -> FleetSnapshot:
+        """The full states of the listed members (None = all, in order) -- n, flags, time, velocity, mean, the covariance's lower
+        triangle -- as one ``FleetSnapshot``: a size call, one buffer, ONE launch of k_fleet_pack whatever the number of members.
+        Every event submitted before is in it; nothing in the fleet changes."""
+        size = C.c_long()
+        rc = self.snapshot_code(members, None, 0, size)                                # the sizing call
+        if rc != 0:
+            self._chk(rc, "rfleet_snapshot")
+        blob = np.zeros(size.value, np.uint8)
+        rc = self.snapshot_code(members, blob, blob.size, size)
+        if rc != 0:
+            self._chk(rc, "rfleet_snapshot")
+        return FleetSnapshot(blob[: size.value], validate=False)
+
+    def restore_code(self, snap, members=None) -> int:
+        blob = snap.blob if isinstance(snap, FleetSnapshot) else np.ascontiguousarray(snap, dtype=np.uint8).reshape(-1)
+        mem = None if members is None else np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        if mem is None:
+            count = int(blob[12:16].view(np.int32)[0]) if blob.size >= 16 else 0
+        else:
+            count = mem.shape[0]
+            if count == 0:
+                mem = np.zeros(1, np.int32)
+        return _snapshot_lib().rfleet_restore(self._h, blob.ctypes.data if blob.size else None, blob.size,
+                                              None if mem is None else mem.ctypes.data, count)
+
+    def restore(self, snap, members=None):
+        """Entry g of ``snap`` (a ``FleetSnapshot``, of this fleet or another) becomes member ``members[g]`` (None: the index it was
+        taken from): n, flags, time, velocity, mean and covariance from the blob, zeros beyond n, a last-match record of zero counts.
+        Everything is validated before anything moves (every n must fit this fleet's capacity, targets distinct); then one copy to
+        the device and ONE launch of k_fleet_unpack.  Members not listed keep every bit; the pose track logs nothing."""
+        rc = self.restore_code(snap, members)
+        if rc != 0:
+            self._chk(rc, "rfleet_restore")
 
     # -- what the node publishes: the reflectors of any list of members in one launch ----------------
     def reflectors(self, members=None, ellipses=True, xy=False, cov=False):
