@@ -1,5 +1,5 @@
-// batch_host.h -- the buffers a handle owns: the two kinds a fleet handle shares with the device (Pinned, Staging) and the two
-// that copies run between (Device, Host).  Each knows how its memory was taken: what alloc() took, release() gives back the same
+// batch_host.h -- the buffers a handle owns: the kinds a fleet handle shares with the device (Pinned, PinnedDefault, Staging) and the
+// two that copies run between (Device, Host).  Each knows how its memory was taken: what alloc() took, release() gives back the same
 // way, and release() of an empty buffer does nothing.  Plain aggregates: a handle holds them by value and releases them when it is
 // destroyed; nothing copies them (two of a handle's buffers may change places: std::swap).
 #pragma once
@@ -11,13 +11,13 @@ namespace batch_host {
 namespace {   // (a handle's translation unit exports its C functions and nothing else)
 
 // n elements of pinned host memory, mapped and coherent: the host reads and writes `h`, the device `dv`, both in place
-template <typename T>
+template <typename T, unsigned FLAGS = hipHostMallocMapped | hipHostMallocCoherent>
 struct Pinned {
     T *h = nullptr, *dv = nullptr;
     // all or nothing: a buffer whose device pointer cannot be had is given back
     hipError_t alloc(size_t n)
     {
-        hipError_t e = hipHostMalloc((void **)&h, sizeof(T) * n, hipHostMallocMapped | hipHostMallocCoherent);
+        hipError_t e = hipHostMalloc((void **)&h, sizeof(T) * n, FLAGS);
         if (e != hipSuccess) { h = nullptr; return e; }
         e = hipHostGetDevicePointer((void **)&dv, h, 0);
         if (e != hipSuccess) release();
@@ -29,6 +29,10 @@ struct Pinned {
         h = dv = nullptr;
     }
 };
+
+// the same, taken with the default flags and then asked for its device pointer (the fleet filter's ring, pose slots and reflector rows)
+template <typename T>
+using PinnedDefault = Pinned<T, hipHostMallocDefault>;
 
 // a staging area the host writes and a kernel reads in place: host-visible device memory where the platform gives it
 // (host_visible.h; `in_vram` says so), else pinned host memory
@@ -64,6 +68,32 @@ struct Host {
     hipError_t alloc(size_t n) { const hipError_t e = hipHostMalloc((void **)&h, sizeof(T) * n, hipHostMallocDefault); if (e != hipSuccess) h = nullptr; return e; }
     void release() { if (h) (void)hipHostFree(h); h = nullptr; }
 };
+
+// Grow or replace, the one rule: the new allocation first, then `fill(fresh)` -- everything else that can fail -- and only then is the
+// old buffer released and the fresh one put in its place.  On an error the fresh one is released and the old one stays as it was.
+template <typename Buf, typename Fill>
+hipError_t replace(Buf &old, size_t n, Fill &&fill)
+{
+    Buf fresh;
+    hipError_t e = fresh.alloc(n);
+    if (e == hipSuccess) e = fill(fresh);
+    if (e != hipSuccess) { fresh.release(); return e; }
+    old.release();
+    old = fresh;
+    return e;
+}
+
+// a buffer of `cap` elements holds `need`: grown by doubling, from `first` for an empty one, under replace()'s rule
+template <typename Buf>
+hipError_t reserve(Buf &b, size_t &cap, size_t need, size_t first)
+{
+    if (cap >= need) return hipSuccess;
+    size_t c = cap ? cap : first;
+    while (c < need) c *= 2;
+    const hipError_t e = replace(b, c, [](Buf &) { return hipSuccess; });
+    if (e == hipSuccess) cap = c;
+    return e;
+}
 
 // release() of every buffer named: what a handle's destroy calls
 template <typename... B>

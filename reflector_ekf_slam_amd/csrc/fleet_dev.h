@@ -98,3 +98,50 @@ struct FleetLaunch {         // one rfleet_submit: G members with events, member
 hipError_t rfleet_launch_step(const FleetDev &d, const FleetLaunch &l, hipStream_t s);
 // a submit that holds a scan wider than RFLEET_MAX_OBS_DEV: k_fleet_step_wide, whatever l.fix, l.M_map and l.track say (fleet_wide.hip)
 hipError_t rfleet_launch_step_wide(const FleetDev &d, const FleetLaunch &l, FleetWideRec *wrec, hipStream_t s);
+
+// ---- what the step kernels of fleet_kernels.hip and fleet_wide.hip share on the device
+typedef double v4d __attribute__((ext_vector_type(4)));
+
+#define FLEET_SLD 65             // row stride of S in LDS (odd: a column walk touches every bank)
+#define FLEET_LD_MAX 272         // roundup(3 + 2 * 128, 16)
+
+__device__ static inline void fleet_obs_to_global(double x, double y, double c, double s, float px, float py, float &gx, float &gy)
+{
+#pragma clang fp contract(off)
+    // cc:389-393 / :327-331: evaluated in double, rounded to float32 on assignment
+    gx = (float)((double)px * c - (double)py * s + x);
+    gy = (float)((double)px * s + (double)py * c + y);
+}
+
+// gps.cc:320-328: the yaw difference as quaternion (w, 0, 0, z) -> angle-axis z (reference transform.h:46-70)
+__device__ static inline double fleet_yaw_innovation(double delta_theta)
+{
+#pragma clang fp contract(off)
+    double w = cos(delta_theta / 2), z = sin(delta_theta / 2);
+    const double nrm = sqrt(w * w + z * z);
+    w /= nrm; z /= nrm;
+    if (w < 0.) { w = -w; z = -z; }
+    const double angle = 2. * atan2(fabs(z), w);
+    const double scale = angle < 1e-7 ? 2. : angle / sin(angle / 2.);
+    return scale * z;
+}
+
+// One event's record of a tracked launch: the pose, the pose block of the lower triangle, n, the flags and the scan's match counts,
+// staged in LDS and stored by lanes 0-15 of wave 0, 8 bytes each: ONE 128-byte line of the launch's ring segment in pinned host
+// memory.  The host sized the area for one record per packed event, so nothing counts and nothing can overflow.  The leading barrier
+// orders the reads behind the event's last write to s_mu, s_flags and P's corner (whichever phase that was); the next pass has
+// barriers of its own before anything here is staged again.
+__device__ static inline void fleet_track_write(FleetTrackRec *rec, double *s_trk, const double *s_mu, const double *P, int ld, int n,
+                                                const int *s_flags, int n_state, int n_new, int n_map)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();
+    if (tid < 3) s_trk[tid] = s_mu[tid];
+    else if (tid < 12) s_trk[tid] = rekf_plower(P, ld, (tid - 3) % 3, (tid - 3) / 3);
+    else if (tid == 12) {
+        int *q = (int *)(s_trk + 12);                       // FleetTrackRec's integers, in its order
+        q[0] = n; q[1] = *s_flags; q[2] = n_state; q[3] = n_new; q[4] = n_map; q[5] = 0; q[6] = 0; q[7] = 0;
+    }
+    __syncthreads();
+    if (tid < 16) ((double *)rec)[tid] = s_trk[tid];
+}

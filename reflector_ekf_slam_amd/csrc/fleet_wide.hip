@@ -21,49 +21,10 @@
 // Fix, map and track are chosen at RUN TIME from L.fix, L.M_map / L.map_use and L.track: the wide launch is the rare path and one
 // kernel serves all of them; what that costs is in DESIGN.md 10.13.  The match record of a wide launch goes into FleetWideRec.
 //
-// Phase P's statements are fleet_kernels.hip's own (pasted by inclusion, as that file pastes them into its body); the three small
-// device functions below are restated from there because that file keeps them beside its kernels.
+// Phase P's statements are fleet_kernels.hip's own (pasted by inclusion, as that file pastes them into its body).
 #include "fleet_dev.h"
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-#define FLEET_SLD 65             // as fleet_kernels.hip
-#define FLEET_LD_MAX 272
 #define FLEET_BLOCK_PAIRS 32     // pairs per block step: m <= 64 rows, what S in LDS and the W / Kn panels hold
-
-__device__ static inline void fleet_obs_to_global(double x, double y, double c, double s, float px, float py, float &gx, float &gy)
-{
-#pragma clang fp contract(off)
-    gx = (float)((double)px * c - (double)py * s + x);
-    gy = (float)((double)px * s + (double)py * c + y);
-}
-
-__device__ static inline double fleet_yaw_innovation(double delta_theta)
-{
-#pragma clang fp contract(off)
-    double w = cos(delta_theta / 2), z = sin(delta_theta / 2);
-    const double nrm = sqrt(w * w + z * z);
-    w /= nrm; z /= nrm;
-    if (w < 0.) { w = -w; z = -z; }
-    const double angle = 2. * atan2(fabs(z), w);
-    const double scale = angle < 1e-7 ? 2. : angle / sin(angle / 2.);
-    return scale * z;
-}
-
-__device__ static inline void fleet_track_write(FleetTrackRec *rec, double *s_trk, const double *s_mu, const double *P, int ld, int n,
-                                                const int *s_flags, int n_state, int n_new, int n_map)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    if (tid < 3) s_trk[tid] = s_mu[tid];
-    else if (tid < 12) s_trk[tid] = rekf_plower(P, ld, (tid - 3) % 3, (tid - 3) / 3);
-    else if (tid == 12) {
-        int *q = (int *)(s_trk + 12);
-        q[0] = n; q[1] = *s_flags; q[2] = n_state; q[3] = n_new; q[4] = n_map; q[5] = 0; q[6] = 0; q[7] = 0;
-    }
-    __syncthreads();
-    if (tid < 16) ((double *)rec)[tid] = s_trk[tid];
-}
 
 __global__ __launch_bounds__(RFLEET_THREADS) void k_fleet_step_wide(FleetDev d, FleetLaunch L, FleetWideRec *wrec)
 {

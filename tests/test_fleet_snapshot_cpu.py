@@ -305,7 +305,7 @@ def test_cases_cover_what_they_claim(oracle_lib):
 
 
 # ---- the measurement describes the tree ----------------------------------------------------------------------------------------------
-SNAPSHOT_BENCH_SOURCES = ["include/rfleet.h", "reflector_ekf_slam_amd/csrc/fleet_dev.h", "reflector_ekf_slam_amd/csrc/fleet_snapshot.h",
+SNAPSHOT_BENCH_SOURCES = ["include/rfleet.h", "reflector_ekf_slam_amd/csrc/fleet_dev.h", "reflector_ekf_slam_amd/csrc/fleet_host.h", "reflector_ekf_slam_amd/csrc/fleet_snapshot.h",
                           "reflector_ekf_slam_amd/csrc/fleet_snapshot.hip", "reflector_ekf_slam_amd/csrc/rfleet_api.hip",
                           "reflector_ekf_slam_amd/fleet.py", "scripts/fleet_snapshot_bench.py"]
 

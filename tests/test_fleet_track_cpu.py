@@ -19,7 +19,7 @@ from tests.fleet_harness import ROOT, _lib, fleet_mod
 # the dumps of tests/test_fleet_node_cpu.py
 SHAPES = ((6, 1440), (5, 2880), (4, 1440))
 START = (0, 2, 1)
-TRACK_BENCH_SOURCES = ["include/rfleet.h", "reflector_ekf_slam_amd/csrc/fleet_dev.h", "reflector_ekf_slam_amd/csrc/fleet_kernels.hip",
+TRACK_BENCH_SOURCES = ["include/rfleet.h", "reflector_ekf_slam_amd/csrc/fleet_dev.h", "reflector_ekf_slam_amd/csrc/fleet_host.h", "reflector_ekf_slam_amd/csrc/fleet_kernels.hip",
                        "reflector_ekf_slam_amd/csrc/rfleet_api.hip", "reflector_ekf_slam_amd/fleet.py", "scripts/fleet_track_bench.py"]
 
 

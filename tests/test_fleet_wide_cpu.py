@@ -18,7 +18,7 @@ from tests.witness import fleet_wide_witness as WW
 
 pytestmark = pytest.mark.skipif(not WW.available(), reason="numpy.longdouble has no 64-bit mantissa here")
 
-WIDE_BENCH_SOURCES = ["include/rfleet.h", "reflector_ekf_slam_amd/csrc/fleet_dev.h", "reflector_ekf_slam_amd/csrc/fleet_kernels.hip",
+WIDE_BENCH_SOURCES = ["include/rfleet.h", "reflector_ekf_slam_amd/csrc/fleet_dev.h", "reflector_ekf_slam_amd/csrc/fleet_host.h", "reflector_ekf_slam_amd/csrc/fleet_kernels.hip",
                       "reflector_ekf_slam_amd/csrc/fleet_wide.hip", "reflector_ekf_slam_amd/csrc/rfleet_api.hip", "reflector_ekf_slam_amd/fleet.py",
                       "scripts/fleet_wide_bench.py"]
 WIDE_CALLS = ("rfleet_set_wide_scans", "rfleet_get_last_match_wide", "rfleet_wide_counts")

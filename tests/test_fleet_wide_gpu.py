@@ -1,6 +1,6 @@
 """Fleet filter, wide scans on the GPU (-m gpu): k_fleet_step_wide against the longdouble JOINT witness on the cases of
 tests/fleet_wide_cases.py, the bits of narrow members and of call patterns, which kernel a submit launches, the limits, the pose
-track's counts and FleetNode(wide_scans=True).
+track's counts, FleetNode(wide_scans=True), and whose match record last_match reads behind every kind of launch.
 
 Worst figures of the lockstep run on an MI355X, as multiples of the suite's measured FP64 floor (bound: 16; printed by
 test_every_case_against_the_joint_witness, run with -s): sigma 1.30 x (wide_L128_MM63_N0_omni), mu 12.26 x (wide_tall_L1_MM40: 40
@@ -232,3 +232,64 @@ def test_fleet_node_takes_the_34_plate_scan(oracle_lib, tmp_path):
     finally:
         for f in (fn, plain):
             f.detector.close(); f.fleet.close(); f.map_builder._fleet.close()
+
+
+# ---- whose record is it ----------------------------------------------------------------------------------------------------------
+def _alone(case, state, t, scan, fix=None, with_map=None):
+    """last_match of a fresh one-member fleet that is set to `state` at time t and given `scan` alone."""
+    fl = H.fleet_mod().ReflectorEKFSLAMFleet([FC.options_of(case)], wide_scans=scan is not None and len(scan) > 32)
+    try:
+        fl.set_state(0, t, state[0], state[1], (0.0, 0.0, 0.0))
+        if with_map is not None:
+            fl.set_map(*with_map)
+        if scan is not None:
+            fl.submit([(0, FC.EV_SCAN, t + 0.1, (0.0, 0.0, 0.0), scan) + (() if fix is None else (fix,))])
+        return H.norm_match(fl.last_match(0))
+    finally:
+        fl.close()
+
+
+def test_last_match_follows_the_launch_that_wrote_it():
+    """Member 0's scans go through a plain, a fix, a map, a tracked and a wide launch, a narrow scan inside a wide launch, a plain
+    launch again and a restore; after each, its last_match is that of a fresh fleet set to the same state and given that scan alone."""
+    lms = FC.far_lattice(4)
+    cases = [FC.crafted(f"whose_{i}", lms, [], [], seed=9790 + i) for i in range(3)]
+    pts = FM.map_lattice(3)
+    the_map = (np.asarray(pts, np.float32), np.tile(np.asarray(FM.IDENTITY), (3, 1)))
+    no_map = (np.zeros((0, 2), np.float32), np.zeros((0, 4)))
+    cloud = lambda *p: np.asarray(p, np.float32).reshape(-1, 2)
+    by = lambda j, i: FM.near(lms[j], i)
+    far = FC.far_lattice(40)[8:37]
+    wide = cloud(*[by(j, j) for j in range(4)], *far)
+    wide1 = cloud(*[by(j, j + 2) for j in range(4)], *FC.far_lattice(80)[44:73])
+    assert wide.shape == wide1.shape == (33, 2)
+    fl = WC.make_fleet(cases, wide=True, with_map=False)
+    try:
+        def step(scan, fix=None, with_map=None, others=()):
+            before, t = FC.state_bits(fl, 0), float(fl.poses()[0][0])
+            fl.submit([(0, FC.EV_SCAN, t + 0.1, (0.0, 0.0, 0.0), scan) + (() if fix is None else (fix,))] + list(others))
+            got, want = H.norm_match(fl.last_match(0)), _alone(cases[0], before, t, scan, fix, with_map)
+            assert all(np.array_equal(x, y) for x, y in zip(got, want)), (got, want)
+            return tuple(len(x) for x in got)                 # (state pairs, map pairs, new)
+
+        other = lambda m, scan: (m, FC.EV_SCAN, 60.0, (0.0, 0.0, 0.0), scan)
+        assert step(cloud(by(0, 0), by(1, 1), (0.0, 2.5)), others=[other(2, cloud(by(2, 3)))]) == (2, 0, 1)              # plain
+        snap = fl.snapshot([0])
+        assert step(cloud(by(1, 2), by(2, 3)), fix=FM.FIX) == (2, 0, 0)                                                  # fix
+        fl.set_map(*the_map)
+        assert step(cloud(FM.near(pts[0], 1), by(3, 4), FM.near(pts[2], 2)), with_map=the_map) == (1, 2, 0)              # map
+        fl.set_map(*no_map)
+        fl.track(True)
+        assert step(cloud(by(0, 5), FM.near(pts[1], 3), by(2, 6))) == (2, 0, 1)                                          # tracked: no map pairs
+        fl.track(False)
+        assert fl.wide_counts() == (0, 0)
+        assert step(wide) == (4, 0, 29) and fl.wide_counts() == (1, 1)                                                   # wide
+        assert step(cloud(by(3, 1), by(0, 2)), others=[other(1, wide1)]) == (2, 0, 0) and fl.wide_counts() == (2, 2)     # narrow in a wide launch
+        assert len(H.norm_match(fl.last_match(1))[2]) == 29
+        assert step(cloud(by(1, 3))) == (1, 0, 0) and fl.wide_counts() == (2, 2)                                         # plain again
+        fl.restore(snap, [0])
+        got = H.norm_match(fl.last_match(0))
+        want = _alone(cases[0], FC.state_bits(fl, 0), float(fl.poses()[0][0]), None)
+        assert all(np.array_equal(x, y) for x, y in zip(got, want)) and [len(x) for x in got] == [0, 0, 0]               # restore: empty
+    finally:
+        fl.close()
