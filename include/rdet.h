@@ -23,6 +23,8 @@
 #ifndef RDET_H_
 #define RDET_H_
 
+#include "rlink.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -138,6 +140,17 @@ int rdet2d_batch_get_range_data(rdet2d_batch_t *b, int member, float origin_xy[2
  * nothing.  The handle's first launching call allocates B * max_beams points of pinned host memory. */
 int rdet2d_batch_get_range_data_all(rdet2d_batch_t *b, const int *members, int count, int *counts,
                                     float *origins_xy, float *returns_xy, long cap_points);
+/* The submit that has not been collected, as a consumer on the same device needs to see it (include/rlink.h; the fleet filter's
+ * rfleet_submit_linked takes one): valid only between submit and collect, RDET_ERR_INVALID otherwise or for a null pointer.  Launches
+ * nothing and waits for nothing: records the handle's `ready` event on its stream behind the submit's launch, fills *out -- the
+ * host arrays (member, stamp, the host's own status such as RDET_ERR_BAD_SCAN, the record index or -1 for an entry no workgroup runs
+ * for: N = 0 or a malformed message) stay valid until the NEXT submit, the records until the handle is destroyed -- and remembers
+ * that a link was taken: the next submit then makes the handle's STREAM (not the host) wait for `consumed`, which the consumer
+ * records once it has read the records, before its kernel overwrites them, and destroy waits for it on the host.  A consumer that
+ * never records `consumed` is not waited for.  collect is unchanged: it is still how the host gets the centres, the statuses and
+ * the range data, and behind the consumer's own synchronisation it returns without waiting.
+ * (Added without a new RDET_ABI_VERSION, as rdet3d_batch_link below: a binding looks them up by name.) */
+int rdet2d_batch_link(rdet2d_batch_t *b, rlink *out);
 int rdet2d_batch_sizeof_scan(void);
 const char *rdet2d_batch_last_hip_error(rdet2d_batch_t *b);
 
@@ -207,6 +220,9 @@ int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count
  * be null when max_centers is 0; obs_time and n_bright may be null. */
 int rdet3d_batch_collect(rdet3d_batch_t *b, int *status, int *K, float *centers_xy, int max_centers,
                          double *obs_time, int *n_bright);
+/* As rdet2d_batch_link: record -1 for a cloud with N = 0. */
+int rdet3d_batch_link(rdet3d_batch_t *b, rlink *out);
+int rdet_sizeof_link(void);           /* sizeof(rlink) as the library was compiled */
 int rdet3d_batch_max_bright(void);    /* 5120 */
 int rdet3d_batch_sizeof_cloud(void);
 const char *rdet3d_batch_last_hip_error(rdet3d_batch_t *b);

@@ -59,6 +59,7 @@
 #define RFLEET_H_
 
 #include "rekf.h"
+#include "rlink.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -72,7 +73,8 @@ extern "C" {
 
 typedef struct rfleet rfleet_t;
 
-enum { RFLEET_EV_ODOM = 0, RFLEET_EV_SCAN = 1 };
+/* RFLEET_EV_SCAN_LINKED: a scan of rfleet_submit_linked whose observations a fleet detector's launch is still producing (below) */
+enum { RFLEET_EV_ODOM = 0, RFLEET_EV_SCAN = 1, RFLEET_EV_SCAN_LINKED = 2 };
 
 typedef struct rfleet_event {
     int member;          /* 0 .. B-1 */
@@ -235,6 +237,40 @@ int rfleet_snapshot_peek(const void *blob, long bytes, int *count, int *max_n);
 /* sizeof(rfleet_snapshot_member) / sizeof(rfleet_snapshot_hdr) as the library was compiled */
 int rfleet_sizeof_snapshot_member(void);
 int rfleet_sizeof_snapshot_hdr(void);
+/* The detector's centres bound to the filter on the device.  rfleet_submit with one more kind of event: RFLEET_EV_SCAN_LINKED is a
+ * scan whose observations are entry ev.K of `link` (include/rlink.h: one outstanding submit of a fleet detector, rdet2d_batch_link /
+ * rdet3d_batch_link of rdet.h, or records the caller planted).  Its xy is not looked at, its t is used as given (the entry's stamp is
+ * the caller's to copy), has_pose_fix / pose_fix work as for a scan; events of the other two kinds may be mixed in freely.  The host
+ * never sees the centres and waits for nothing: the fleet's stream waits for link->ready (when not NULL), ONE launch of k_fleet_bind
+ * (csrc/fleet_link.hip), one 64-lane workgroup per linked scan whose entry has a record, copies the centres into the segment and
+ * stores their count into the packed event, link->consumed (when not NULL) is recorded behind it, and the step launch follows: two
+ * launches per call instead of one, and no kernel of rfleet_submit differs.  Per linked scan the bind reads K and err from the
+ * record once and takes the scan or leaves it EMPTY -- a Predict to its stamp, as a scan with K = 0 is:
+ *     err != 0                             status err                       taken 0
+ *     K < 0 or K > link->max_centers       status -4 (RDET_ERR_CAPACITY)    taken 0
+ *     K > RFLEET_MAX_OBS (_WIDE)           status REKF_ERR_TOO_MANY_OBS     taken 0      (what rfleet_submit refuses on the host)
+ *     otherwise                            status 0                         taken K
+ * so the state and the host's time mirror stay well defined whatever a record holds; rfleet_link_status tells the host afterwards.
+ * An entry with record == -1 is packed as the empty scan the detector's host knows it to be and needs no bind.
+ * On a fleet with rfleet_set_wide_scans on, a call that holds a linked scan with a record takes k_fleet_step_wide -- the host cannot
+ * know whether K > RFLEET_MAX_OBS -- with the same bits for narrow scans; rfleet_wide_counts counts that launch, and counts scans
+ * only as far as the host knows them: a linked scan that turns out wide is not in `scans`.
+ * EVERYTHING is validated first and a refused call (REKF_ERR_INVALID) touches nothing: what rfleet_submit refuses, a linked scan with
+ * a null or malformed link, an entry index outside the link, an entry named twice, an entry whose member differs from the event's,
+ * an entry with host_status != 0, a link of another device, a linked scan on a fleet with rfleet_set_tracking on (the track's K is
+ * the host's).  link may be NULL when no event is linked: the call is rfleet_submit.  The link's host arrays are read during the call
+ * only.  (Added without a new RFLEET_ABI_VERSION: a binding looks the three calls up by name.) */
+int rfleet_submit_linked(rfleet_t *f, const rfleet_event *ev, int count, const rlink *link);
+/* What the binds of the LAST rfleet_submit_linked that held a linked scan did, one record per linked scan in event order: taken,
+ * status and K as read from the record (0, 0, 0 for an entry without a record).  Synchronises.  Returns the number of records
+ * (>= 0; 0 before any linked submit), REKF_ERR_BUFFER when cap holds fewer (nothing written), REKF_ERR_INVALID for a null handle or
+ * cap < 0.  Each output may be NULL. */
+int rfleet_link_status(rfleet_t *f, int *taken, int *status, int *K_seen, int cap);
+/* Host counters since rfleet_create: calls that held a linked scan, launches of k_fleet_bind, linked scans submitted, and linked scans
+ * a bind left empty (status != 0) -- that one is updated when rfleet_link_status reads a submit's records, once per submit.  No HIP call. */
+int rfleet_link_counts(rfleet_t *f, long *submits, long *binds, long *scans, long *emptied);
+/* sizeof(rlink) as the library was compiled */
+int rfleet_sizeof_link(void);
 /* Wait for all enqueued work.  REKF_ERR_HIP when the device reported an error. */
 int rfleet_sync(rfleet_t *f);
 int rfleet_size(rfleet_t *f, int *B, int *max_landmarks);

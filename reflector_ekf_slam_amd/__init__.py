@@ -7,8 +7,9 @@ synthetic session generator (``synth``) and the session driver (``session``).
 """
 from .ekf_slam import (DIFF, OMNI, EKFOptions, Map, Observation, OdometryData,  # noqa: F401
                        ReflectorEKFSLAM, ReflectorMatchResult, RekfError, State)
-from .fleet import FleetSnapshot, ReflectorEKFSLAMFleet  # noqa: F401
-from .fleet_detect import LaserReflectorDetectFleet, PointCloud, PointCloudReflectorDetectFleet, cloud_events, scan_events  # noqa: F401
+from .fleet import FleetSnapshot, ReflectorEKFSLAMFleet, linked_scan_event  # noqa: F401
+from .fleet_detect import (DetectLink, LaserReflectorDetectFleet, PointCloud, PointCloudReflectorDetectFleet, cloud_events,  # noqa: F401
+                           linked_scan_events, scan_events)
 from .grid import OccupancyGrid  # noqa: F401
 from .fleet_match import (FleetFilterResult, FleetOccupancyGrid, FleetRangeDataResult, FleetRefineResult, FleetScanMatchResult, FleetTexture,  # noqa: F401
                           RgridBatchFilterScan, RgridBatchInsertScan, RgridBatchRangeData, ScanMatchFleet, gravity_aligned_scans, pose_fixes)

@@ -21,6 +21,14 @@ class RekfOptions(C.Structure):
                 ("angular_velocity_cov", C.c_double), ("observation_cov", C.c_double)]
 
 
+class Rlink(C.Structure):
+    """struct rlink (include/rlink.h): one outstanding submit of a fleet detector as librfleet.so reads it.  Neither library's
+    binding owns it."""
+    _fields_ = [("count", C.c_int), ("device", C.c_int), ("member", C.c_void_p), ("stamp", C.c_void_p), ("host_status", C.c_void_p),
+                ("record", C.c_void_p), ("records", C.c_void_p), ("record_bytes", C.c_long), ("k_off", C.c_int), ("err_off", C.c_int),
+                ("centers_off", C.c_int), ("max_centers", C.c_int), ("ready", C.c_void_p), ("consumed", C.c_void_p)]
+
+
 class LibraryMissing(RuntimeError):
     pass
 

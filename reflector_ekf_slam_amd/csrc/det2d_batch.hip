@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -592,6 +593,11 @@ struct rdet2d_batch {
     std::vector<int> sub_member, sub_status, sub_runs;
     std::vector<double> sub_stamp;
     std::vector<char> seen;
+    // rdet2d_batch_link (include/rlink.h): the record index of every entry of the outstanding submit; `ready`, recorded by link behind
+    // the launch, and `consumed`, recorded by the consumer: both made by the first link; a link of the outstanding submit was taken
+    std::vector<int> sub_record;
+    hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
+    bool link_taken = false;
     // rdet2d_batch_get_range_data_all, allocated by its first call that launches: the rows of a call, and its records with the
     // workgroup table behind them
     batch_host::Pinned<float2> rd_out;           // [B][max_beams]
@@ -647,6 +653,7 @@ int rdet2d_batch_create(const rdet2d_options *opts, const double *s2b_xyyaw, int
     }
     b->sub_member.resize((size_t)B); b->sub_status.resize((size_t)B); b->sub_runs.resize((size_t)B);
     b->sub_stamp.resize((size_t)B); b->seen.assign((size_t)B, 0);
+    b->sub_record.resize((size_t)B);
     const size_t nb = (size_t)max_beams, nB = (size_t)B;
     int rc = [&]() -> int {
         DETB_TRY(b, hipSetDevice(device));
@@ -671,6 +678,8 @@ void rdet2d_batch_destroy(rdet2d_batch_t *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->ev_consumed) { (void)hipEventSynchronize(b->ev_consumed); (void)hipEventDestroy(b->ev_consumed); }   // (a consumer may still read the records)
+    if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
     (void)hipFree(b->d_tables); (void)hipFree(b->d_contrib); (void)hipFree(b->d_returns);
     if (b->h_tables) (void)hipHostFree(b->h_tables);
     b->stage.release(); b->recs.release(); b->out.release(); b->rd_out.release(); b->rd_tab.release();
@@ -722,6 +731,11 @@ int rdet2d_batch_submit(rdet2d_batch_t *b, const rdet2d_scan *scans, int count)
     }
     if (count > b->B) return RDET_ERR_INVALID;      // (unreachable: one scan per member)
     DETB_TRY(b, hipSetDevice(b->device));
+    // a link of the submit before was taken: the consumer's reads of the records come first, on the stream.  Until then the host
+    // leaves the records alone too (what it would clear below is never read: collect looks at sub_runs first)
+    const bool linked = b->link_taken;
+    if (linked) DETB_TRY(b, hipStreamWaitEvent(b->stream, b->ev_consumed, 0));
+    b->link_taken = false;
     ++b->n_submit;
     const size_t mb = (size_t)b->max_beams;
     // the tables this call needs and already has: none of them may be the one that is replaced
@@ -804,9 +818,36 @@ int rdet2d_batch_submit(rdet2d_batch_t *b, const rdet2d_scan *scans, int count)
         Bf.returns = b->d_returns; Bf.out = b->out.dv; Bf.max_beams = b->max_beams;
         hipLaunchKernelGGL(k_det2d_batch, dim3((unsigned)count), dim3(1024), 0, b->stream, Bf);
         DETB_TRY(b, hipGetLastError());
-    } else {
+    } else if (!linked) {
         for (int i = 0; i < count; ++i) std::memset(&b->out.h[i], 0, 4 * sizeof(int));
     }
+    return RDET_OK;
+}
+
+int rdet2d_batch_link(rdet2d_batch_t *b, rlink *out)
+{
+    if (!b || !out || !b->outstanding) return RDET_ERR_INVALID;
+    DETB_TRY(b, hipSetDevice(b->device));
+    if (!b->ev_ready) DETB_TRY(b, hipEventCreateWithFlags(&b->ev_ready, hipEventDisableTiming));
+    if (!b->ev_consumed) DETB_TRY(b, hipEventCreateWithFlags(&b->ev_consumed, hipEventDisableTiming));
+    DETB_TRY(b, hipEventRecord(b->ev_ready, b->stream));
+    for (int i = 0; i < b->sub_count; ++i) b->sub_record[(size_t)i] = b->sub_runs[(size_t)i] ? i : -1;
+    std::memset(out, 0, sizeof(*out));
+    out->count = b->sub_count;
+    out->device = b->device;
+    out->member = b->sub_member.data();
+    out->stamp = b->sub_stamp.data();
+    out->host_status = b->sub_status.data();
+    out->record = b->sub_record.data();
+    out->records = b->out.dv;
+    out->record_bytes = (long)sizeof(BatchOut);
+    out->k_off = (int)offsetof(BatchOut, K);
+    out->err_off = (int)offsetof(BatchOut, err);
+    out->centers_off = (int)offsetof(BatchOut, centers);
+    out->max_centers = RDET_MAX_CENTERS;
+    out->ready = b->ev_ready;
+    out->consumed = b->ev_consumed;
+    b->link_taken = true;
     return RDET_OK;
 }
 

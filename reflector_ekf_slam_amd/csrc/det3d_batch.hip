@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -476,6 +477,12 @@ struct rdet3d_batch {
     std::vector<int> sub_runs;
     std::vector<double> sub_stamp;
     std::vector<char> seen;
+    // rdet3d_batch_link (include/rlink.h): member, host status (always 0) and record index of every entry of the outstanding submit;
+    // `ready`, recorded by link behind the launch, and `consumed`, recorded by the consumer: both made by the first link; a link of
+    // the outstanding submit was taken
+    std::vector<int> sub_member, sub_status, sub_record;
+    hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
+    bool link_taken = false;
     std::string hip_error;
 };
 
@@ -513,6 +520,7 @@ int rdet3d_batch_create(const rdet3d_options *opts, const double *s2b_xyyaw, int
         std::memcpy(b->m[(size_t)i].s2b, s2b_xyyaw + 3 * i, sizeof(double) * 3);
     }
     b->sub_runs.resize((size_t)B); b->sub_stamp.resize((size_t)B); b->seen.assign((size_t)B, 0);
+    b->sub_member.resize((size_t)B); b->sub_status.assign((size_t)B, RDET_OK); b->sub_record.resize((size_t)B);
     const size_t np = (size_t)max_points, nB = (size_t)B;
     int rc = [&]() -> int {
         DET3B_TRY(b, hipSetDevice(device));
@@ -535,6 +543,8 @@ void rdet3d_batch_destroy(rdet3d_batch_t *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->ev_consumed) { (void)hipEventSynchronize(b->ev_consumed); (void)hipEventDestroy(b->ev_consumed); }   // (a consumer may still read the records)
+    if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
     b->stage.release(); b->recs.release(); b->out.release();
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
@@ -574,6 +584,11 @@ int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count
         if (rc != RDET_OK) return rc;
     }
     DET3B_TRY(b, hipSetDevice(b->device));
+    // a link of the submit before was taken: the consumer's reads of the records come first, on the stream.  Until then the host
+    // leaves the records alone too (what it would clear below is never read: collect looks at sub_runs first)
+    const bool linked = b->link_taken;
+    if (linked) DET3B_TRY(b, hipStreamWaitEvent(b->stream, b->ev_consumed, 0));
+    b->link_taken = false;
     const size_t np = (size_t)b->max_points;
     int n_run = 0, n_max = 0;
     for (int i = 0; i < count; ++i) {
@@ -581,7 +596,8 @@ int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count
         const rdet3d_batch_member &M = b->m[(size_t)c.member];
         b->sub_stamp[(size_t)i] = c.stamp;                                          // observation.time_ (:97)
         b->sub_runs[(size_t)i] = 0;
-        std::memset(&b->out.h[i], 0, 4 * sizeof(int));
+        b->sub_member[(size_t)i] = c.member;
+        if (!linked) std::memset(&b->out.h[i], 0, 4 * sizeof(int));
         if (c.N == 0) continue;                                                     // nothing to detect: no workgroup
         b->sub_runs[(size_t)i] = 1;
         Cloud3Rec &A = b->recs.h[n_run++];
@@ -610,6 +626,35 @@ int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count
     }
     return RDET_OK;
 }
+
+int rdet3d_batch_link(rdet3d_batch_t *b, rlink *out)
+{
+    if (!b || !out || !b->outstanding) return RDET_ERR_INVALID;
+    DET3B_TRY(b, hipSetDevice(b->device));
+    if (!b->ev_ready) DET3B_TRY(b, hipEventCreateWithFlags(&b->ev_ready, hipEventDisableTiming));
+    if (!b->ev_consumed) DET3B_TRY(b, hipEventCreateWithFlags(&b->ev_consumed, hipEventDisableTiming));
+    DET3B_TRY(b, hipEventRecord(b->ev_ready, b->stream));
+    for (int i = 0; i < b->sub_count; ++i) b->sub_record[(size_t)i] = b->sub_runs[(size_t)i] ? i : -1;
+    std::memset(out, 0, sizeof(*out));
+    out->count = b->sub_count;
+    out->device = b->device;
+    out->member = b->sub_member.data();
+    out->stamp = b->sub_stamp.data();
+    out->host_status = b->sub_status.data();
+    out->record = b->sub_record.data();
+    out->records = b->out.dv;
+    out->record_bytes = (long)sizeof(Cloud3Out);
+    out->k_off = (int)offsetof(Cloud3Out, K);
+    out->err_off = (int)offsetof(Cloud3Out, err);
+    out->centers_off = (int)offsetof(Cloud3Out, centers);
+    out->max_centers = RDET_MAX_CENTERS;
+    out->ready = b->ev_ready;
+    out->consumed = b->ev_consumed;
+    b->link_taken = true;
+    return RDET_OK;
+}
+
+int rdet_sizeof_link(void) { return (int)sizeof(rlink); }
 
 int rdet3d_batch_collect(rdet3d_batch_t *b, int *status, int *K, float *centers_xy, int max_centers, double *obs_time, int *n_bright)
 {

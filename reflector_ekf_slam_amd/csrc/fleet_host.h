@@ -8,9 +8,15 @@
 // (5, submit_launch in rfleet_api.hip: take and grow the ring segment, fill FleetLaunch, launch, commit.)  A segment is
 //   members[G] | ev_begin[G + 1] | FleetEvent[E] | fix[3 n_fix] | obs[2 n_obs]   each at the next 16-byte boundary, and for a tracked
 // submit | FleetTrackRec[E] at the next 128-byte boundary; events grouped by member, stable: a member's events keep their order.
+// A linked submit (rfleet_submit_linked: scans of kind RFLEET_EV_SCAN_LINKED, whose observations a fleet detector's launch is still
+// producing; fleet_link.h) goes through the same four steps, given the rlink: a linked scan whose entry has a record reserves
+// 2 * max_obs floats of obs (max_obs = 32, 256 on a fleet with wide scans on) and is packed with K = 0, and the segment grows a fifth
+// part | FleetBindRec[n_bind] at the next 16-byte boundary behind obs's slack, which k_fleet_bind walks; an entry without a record
+// (record == -1: the detector's host knows K = 0) is packed as the empty scan it is.  Without a linked scan nothing differs by a byte.
 // Also here: the getters' member-list check, a snapshot blob's validation, a pose slot from a lower triangle, the odometry model.
 #pragma once
 #include "fleet_snapshot.h"
+#include "fleet_link.h"
 #include "../../include/rfleet.h"
 
 #include <algorithm>
@@ -41,6 +47,7 @@ struct SubmitScratch {
     std::vector<double> time, vt;           // the mirror's copy: committed behind the launch
     std::vector<double> dts;                // [count][4]: dt and the velocity of event i
     std::vector<unsigned char> dropped;     // a tracked submit: event i is one the untracked path drops
+    std::vector<unsigned char> link_used;   // a linked submit: entry k of the link is named by an event of the call
 };
 
 struct SubmitPlan {
@@ -49,15 +56,51 @@ struct SubmitPlan {
     size_t n_obs = 0, n_fix = 0, n_wide = 0;   // n_wide: scans of the call with K > RFLEET_MAX_OBS
     LastRec rec = LastRec::None;            // who owns the match record of every scanned member behind this launch
     size_t off_mem = 0, off_beg = 0, off_ev = 0, off_fix = 0, off_obs = 0, off_track = 0, need = 0;
+    // a linked submit: linked scans of the call, those with a record (one workgroup of k_fleet_bind each), the pairs reserved for each
+    int n_linked = 0, n_bind = 0, max_obs = RFLEET_MAX_OBS;
+    bool wide_launch = false;               // k_fleet_step_wide: a scan known to be wide, or on a wide fleet one whose K only the device knows
+    size_t off_bind = 0;
 };
 
+static_assert(FLEET_LINK_ERR_TOO_MANY_OBS == REKF_ERR_TOO_MANY_OBS, "fleet_link.h restates rekf.h's code");
+
+// what rfleet_submit_linked asks of the link itself before any of its entries is looked at
+inline bool link_well_formed(const rlink &l)
+{
+    if (l.count < 0) return false;
+    if (l.count > 0 && (!l.member || !l.stamp || !l.host_status || !l.record)) return false;
+    if (l.record_bytes <= 0 || (l.record_bytes & 7) || l.max_centers < 1) return false;
+    if (l.k_off < 0 || (l.k_off & 3) || l.err_off < 0 || (l.err_off & 3) || l.centers_off < 0 || (l.centers_off & 7)) return false;
+    if ((long)l.k_off + 4 > l.record_bytes || (long)l.err_off + 4 > l.record_bytes) return false;
+    return (long)l.centers_off + 8 * (long)l.max_centers <= l.record_bytes;
+}
+
 // ---- 1: validate everything before anything moves
-inline int submit_validate(const rfleet_event *ev, int count, int B, bool wide)
+// link: the rlink of an rfleet_submit_linked (NULL: rfleet_submit, which refuses a linked scan); device, tracked: the fleet's;
+// s: link_used is the scratch of the "an entry used twice" test.
+inline int submit_validate(const rfleet_event *ev, int count, int B, bool wide, const rlink *link = nullptr, int device = 0,
+                           bool tracked = false, SubmitScratch *s = nullptr)
 {
     const int max_obs = wide ? RFLEET_MAX_OBS_WIDE : RFLEET_MAX_OBS;
+    if (link) {
+        if (!s || !link_well_formed(*link)) return REKF_ERR_INVALID;
+        s->link_used.assign((size_t)link->count, 0);
+    }
     for (int i = 0; i < count; ++i) {
         const rfleet_event &e = ev[i];
         if (e.member < 0 || e.member >= B) return REKF_ERR_INVALID;
+        if (e.kind == RFLEET_EV_SCAN_LINKED) {
+            // (TrackMeta::K is the host's: a tracked fleet takes no scan whose K only the device knows)
+            if (!link || tracked || link->device != device) return REKF_ERR_INVALID;
+            const int k = e.K;
+            if (k < 0 || k >= link->count || s->link_used[(size_t)k]) return REKF_ERR_INVALID;
+            s->link_used[(size_t)k] = 1;
+            if (link->member[k] != e.member || link->host_status[k] != 0) return REKF_ERR_INVALID;
+            if (link->record[k] < -1 || link->record[k] >= link->count || (link->record[k] >= 0 && !link->records)) return REKF_ERR_INVALID;
+            if (e.has_pose_fix && !(std::isfinite(e.pose_fix[0]) && std::isfinite(e.pose_fix[1]) && std::isfinite(e.pose_fix[2])))
+                return REKF_ERR_INVALID;
+            continue;
+        }
         if (e.kind != RFLEET_EV_ODOM && e.kind != RFLEET_EV_SCAN) return REKF_ERR_INVALID;
         if (e.kind == RFLEET_EV_SCAN) {
             if (e.K < 0) return REKF_ERR_INVALID;
@@ -75,10 +118,11 @@ inline int submit_validate(const rfleet_event *ev, int count, int B, bool wide)
 // ---- 2: which events reach the device; time [B] / vt [B][3] are the mirror.  p.E == 0 (every event dropped, untracked): no launch.
 inline SubmitPlan submit_plan(const rfleet_event *ev, int count, const std::vector<rekf_options> &opts, const std::vector<double> &time,
                               const std::vector<double> &vt, bool tracked, int M_map, const std::vector<unsigned char> &map_use,
-                              SubmitScratch &s)
+                              SubmitScratch &s, const rlink *link = nullptr, bool wide = false)
 {
     SubmitPlan p;
     p.tracked = tracked;
+    p.max_obs = wide ? RFLEET_MAX_OBS_WIDE : RFLEET_MAX_OBS;
     if (tracked) s.dropped.assign((size_t)count, 0);
     s.time = time;
     s.vt = vt;
@@ -99,6 +143,13 @@ inline SubmitPlan submit_plan(const rfleet_event *ev, int count, const std::vect
                 continue;
             }
             for (int k = 0; k < 3; ++k) s.vt[3 * b + k] = e.v[k];          // cc:216
+        } else if (e.kind == RFLEET_EV_SCAN_LINKED) {
+            const bool bound = link->record[e.K] >= 0;                     // (e.K: the entry; the scan's own K is the device's to tell)
+            p.n_linked += 1;
+            p.n_bind += bound ? 1 : 0;
+            p.n_obs += bound ? (size_t)p.max_obs : 0;
+            p.n_fix += e.has_pose_fix ? 1 : 0;
+            s.scanned.push_back(b);
         } else {
             p.n_obs += (size_t)e.K;
             p.n_fix += e.has_pose_fix ? 1 : 0;
@@ -116,7 +167,8 @@ inline SubmitPlan submit_plan(const rfleet_event *ev, int count, const std::vect
         p.G += s.cnt[b] > 0;
         p.with_map = p.with_map || (s.cnt[b] > 0 && M_map > 0 && map_use[b]);
     }
-    p.rec = p.n_wide > 0 ? LastRec::Wide : (p.with_map || tracked) ? LastRec::NarrowMap : LastRec::Narrow;
+    p.wide_launch = p.n_wide > 0 || (wide && p.n_bind > 0);               // (K > 32 may come out of a record: the host cannot know)
+    p.rec = p.wide_launch ? LastRec::Wide : (p.with_map || tracked) ? LastRec::NarrowMap : LastRec::Narrow;
     return p;
 }
 
@@ -130,10 +182,16 @@ inline void submit_layout(SubmitPlan &p)
     p.need = align16(p.off_obs + sizeof(float) * 2 * p.n_obs + 16);
     p.off_track = align128(p.need);                                        // a tracked submit: | track[E], one 128-byte line each
     if (p.tracked) p.need = p.off_track + sizeof(FleetTrackRec) * (size_t)p.E;
+    if (p.n_bind > 0) {                                                    // (never tracked: validated)
+        p.off_bind = align16(p.need);
+        p.need = p.off_bind + sizeof(FleetBindRec) * (size_t)p.n_bind;
+    }
 }
 
 // ---- 4: the segment's bytes into seg[0, p.need) (the track area is the kernel's to write), meta[E] of a tracked submit
-inline void submit_pack(const rfleet_event *ev, const SubmitPlan &p, SubmitScratch &s, char *seg, std::vector<TrackMeta> &meta)
+// link_known (a linked submit): per linked scan of the call, in event order, 1 = the host knows it is empty (no record, no bind)
+inline void submit_pack(const rfleet_event *ev, const SubmitPlan &p, SubmitScratch &s, char *seg, std::vector<TrackMeta> &meta,
+                        const rlink *link = nullptr, std::vector<unsigned char> *link_known = nullptr)
 {
     int *members = (int *)(seg + p.off_mem), *ev_begin = (int *)(seg + p.off_beg);
     FleetEvent *pev = (FleetEvent *)(seg + p.off_ev);
@@ -150,7 +208,9 @@ inline void submit_pack(const rfleet_event *ev, const SubmitPlan &p, SubmitScrat
     }
     ev_begin[p.G] = acc;
     size_t obs_at = 0;
-    int fix_at = 0;
+    int fix_at = 0, bind_at = 0, slot = 0;
+    FleetBindRec *pbind = (FleetBindRec *)(seg + p.off_bind);
+    if (link_known) link_known->clear();
     if (p.tracked) meta.resize((size_t)p.E);
     for (int q = 0; q < p.E; ++q) {
         const int i = s.order[q];
@@ -167,11 +227,21 @@ inline void submit_pack(const rfleet_event *ev, const SubmitPlan &p, SubmitScrat
         }
         pe.dt = s.dts[4 * (size_t)i];
         for (int k = 0; k < 3; ++k) pe.vt[k] = s.dts[4 * (size_t)i + 1 + k];
-        pe.kind = (e.kind == RFLEET_EV_SCAN) ? 1 : 0;
-        pe.K = (e.kind == RFLEET_EV_SCAN) ? e.K : 0;
+        const bool linked = e.kind == RFLEET_EV_SCAN_LINKED;
+        pe.kind = (e.kind == RFLEET_EV_SCAN || linked) ? 1 : 0;
+        pe.K = (e.kind == RFLEET_EV_SCAN) ? e.K : 0;                       // (a linked scan: 0 until k_fleet_bind says otherwise)
         pe.obs_off = (int)obs_at;
         pe.fix_off = -1;
-        if (e.kind == RFLEET_EV_SCAN && e.has_pose_fix) {
+        if (linked) {
+            const int record = link->record[e.K];
+            if (link_known) link_known->push_back(record < 0);
+            if (record >= 0) {
+                pbind[bind_at++] = FleetBindRec{at, (int)obs_at, record, slot};
+                obs_at += 2 * (size_t)p.max_obs;
+            }
+            ++slot;
+        }
+        if ((e.kind == RFLEET_EV_SCAN || linked) && e.has_pose_fix) {
             pe.fix_off = fix_at;
             for (int k = 0; k < 3; ++k) pfix[fix_at + k] = e.pose_fix[k];
             fix_at += 3;

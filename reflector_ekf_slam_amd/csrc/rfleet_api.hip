@@ -41,6 +41,13 @@
 // that sits in front of the payload in the same buffer; snap_stage is the device half both calls share.  Every copy goes through
 // the handle's stream and is followed by a synchronisation: the stream is non-blocking, so a legacy hipMemcpy would not be ordered
 // behind it.
+//
+// A linked submit (rfleet_submit_linked; include/rlink.h, fleet_link.h) is rfleet_submit's five steps with the link handed to the
+// first four.  Step five then puts, in front of the step launch and on the same stream: a wait for the detector's `ready` event, ONE
+// launch of k_fleet_bind (fleet_link.hip) over the segment's FleetBindRec table -- it writes the centres and the counts into the
+// segment the step kernel is about to read --, and the record of the detector's `consumed` event.  The host waits for nothing.  The
+// binds' status records go to one pinned buffer on the handle (link_stat), which only the device writes: what the host knows by itself
+// (an entry without a record) it keeps in link_known, so a bind of an earlier call that is still in flight cannot overwrite it.
 #include "batch_host.h"
 #include "fleet_host.h"
 #include "fleet_reflectors.h"
@@ -115,6 +122,13 @@ struct rfleet {
     bool wide = false;
     Device<FleetWideRec> wide_rec;
     long wide_launches = 0, wide_scans = 0;
+    // linked submits: the binds' status records (device-written), the last linked call's scans (1 = the host knows the scan is empty),
+    // whether that call's emptied scans are counted yet, rfleet_link_counts' counters
+    PinnedDefault<FleetLinkStatus> link_stat;
+    size_t link_stat_cap = 0;
+    std::vector<unsigned char> link_known, link_known_next;
+    bool link_counted = true;
+    long link_submits = 0, link_binds = 0, link_scans = 0, link_emptied = 0;
     // snapshot / restore: the device staging buffer (table | payload); host scratch: the table, the payload offsets, a restore's targets
     Device<char> snap;
     size_t snap_cap = 0;
@@ -179,7 +193,8 @@ void rfleet_destroy(rfleet_t *f)
         if (s.done) (void)hipEventDestroy(s.done);
         s.buf.release();
     }
-    release_all(f->mu, f->P, f->W, f->Kn, f->ctl, f->opt, f->pose, f->refl, f->map_xy, f->map_cov, f->map_use_dev, f->wide_rec, f->snap);
+    release_all(f->mu, f->P, f->W, f->Kn, f->ctl, f->opt, f->pose, f->refl, f->map_xy, f->map_cov, f->map_use_dev, f->wide_rec, f->snap,
+                f->link_stat);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
@@ -280,9 +295,14 @@ int rfleet_sync(rfleet_t *f)
 }
 
 // ---- step 5 of a submit: a ring segment of p.need bytes, the launch over it, and the commit
-static int submit_launch(rfleet_t *f, const rfleet_event *ev, const SubmitPlan &p)
+static int submit_launch(rfleet_t *f, const rfleet_event *ev, const SubmitPlan &p, const rlink *link = nullptr)
 {
     FLEET_HIP(f, hipSetDevice(f->device));
+    if ((size_t)p.n_linked > f->link_stat_cap) {                           // (a bind in flight writes the old buffer: wait before it goes)
+        const int rc = rfleet_sync(f);
+        if (rc != REKF_OK) return rc;
+        FLEET_HIP(f, reserve(f->link_stat, f->link_stat_cap, (size_t)p.n_linked, 256));
+    }
     Segment &s = f->seg[f->next_seg];
     if (s.busy) {
         FLEET_HIP(f, hipEventSynchronize(s.done));
@@ -290,7 +310,7 @@ static int submit_launch(rfleet_t *f, const rfleet_event *ev, const SubmitPlan &
     }
     if (s.n_track) track_harvest(f, s);                                    // (the oldest segment: every later record comes behind these)
     FLEET_HIP(f, reserve(s.buf, s.cap, p.need, 4096));
-    submit_pack(ev, p, f->sub, s.buf.h, s.meta);
+    submit_pack(ev, p, f->sub, s.buf.h, s.meta, link, &f->link_known_next);
     const char *dv = s.buf.dv;
     FleetLaunch L{};
     L.members = (const int *)(dv + p.off_mem);
@@ -306,7 +326,22 @@ static int submit_launch(rfleet_t *f, const rfleet_event *ev, const SubmitPlan &
         L.M_map = f->M_map;
     }
     if (p.tracked) L.track = (FleetTrackRec *)(s.buf.dv + p.off_track);    // (non-NULL selects k_fleet_step_track, the map kernel's body)
-    if (p.n_wide > 0) FLEET_HIP(f, rfleet_launch_step_wide(f->dev, L, f->wide_rec.d, f->stream));   // (fix, map and track: chosen in the kernel)
+    if (p.n_bind > 0) {                                                    // the centres and the counts into the segment, on the device
+        if (link->ready) FLEET_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)link->ready, 0));
+        FleetBindLaunch Lb{};
+        Lb.bind = (const FleetBindRec *)(dv + p.off_bind);
+        Lb.ev = (FleetEvent *)(s.buf.dv + p.off_ev);
+        Lb.obs = (float *)(s.buf.dv + p.off_obs);
+        Lb.status = f->link_stat.dv;
+        Lb.records = (const char *)link->records;
+        Lb.record_bytes = link->record_bytes;
+        Lb.k_off = link->k_off; Lb.err_off = link->err_off; Lb.centers_off = link->centers_off; Lb.max_centers = link->max_centers;
+        Lb.max_obs = p.max_obs;
+        Lb.n_bind = p.n_bind;
+        FLEET_HIP(f, rfleet_launch_bind(Lb, f->stream));
+    }
+    if (p.n_linked > 0 && link->consumed) FLEET_HIP(f, hipEventRecord((hipEvent_t)link->consumed, f->stream));
+    if (p.wide_launch) FLEET_HIP(f, rfleet_launch_step_wide(f->dev, L, f->wide_rec.d, f->stream));   // (fix, map and track: chosen in the kernel)
     else FLEET_HIP(f, rfleet_launch_step(f->dev, L, f->stream));
     // ---- commit: the launch is in the stream
     if (p.tracked) {
@@ -314,7 +349,14 @@ static int submit_launch(rfleet_t *f, const rfleet_event *ev, const SubmitPlan &
         s.track = (const FleetTrackRec *)(s.buf.h + p.off_track);
     }
     for (int b : f->sub.scanned) f->last_rec[(size_t)b] = p.rec;
-    f->wide_launches += p.n_wide > 0;
+    f->wide_launches += p.wide_launch;
+    if (p.n_linked > 0) {
+        f->link_known.swap(f->link_known_next);
+        f->link_counted = false;
+        f->link_submits += 1;
+        f->link_binds += p.n_bind > 0;
+        f->link_scans += p.n_linked;
+    }
     f->wide_scans += p.n_wide;
     f->time.swap(f->sub.time);
     f->vt.swap(f->sub.vt);
@@ -329,10 +371,53 @@ int rfleet_submit(rfleet_t *f, const rfleet_event *ev, int count)
     if (!f || count < 0 || (count > 0 && !ev)) return REKF_ERR_INVALID;
     const int rc = submit_validate(ev, count, f->B, f->wide);
     if (rc != REKF_OK || count == 0) return rc;
-    SubmitPlan p = submit_plan(ev, count, f->opts, f->time, f->vt, f->tracking, f->M_map, f->map_use, f->sub);
+    SubmitPlan p = submit_plan(ev, count, f->opts, f->time, f->vt, f->tracking, f->M_map, f->map_use, f->sub, nullptr, f->wide);
     if (p.E == 0) return REKF_OK;                                          // (every event dropped, untracked: no launch)
     submit_layout(p);
     return submit_launch(f, ev, p);
+}
+
+int rfleet_submit_linked(rfleet_t *f, const rfleet_event *ev, int count, const rlink *link)
+{
+    if (!f || count < 0 || (count > 0 && !ev)) return REKF_ERR_INVALID;
+    const int rc = submit_validate(ev, count, f->B, f->wide, link, f->device, f->tracking, &f->sub);
+    if (rc != REKF_OK || count == 0) return rc;
+    SubmitPlan p = submit_plan(ev, count, f->opts, f->time, f->vt, f->tracking, f->M_map, f->map_use, f->sub, link, f->wide);
+    if (p.E == 0) return REKF_OK;                                          // (every event dropped, untracked: no launch)
+    submit_layout(p);
+    return submit_launch(f, ev, p, link);
+}
+
+int rfleet_sizeof_link(void) { return (int)sizeof(rlink); }
+
+int rfleet_link_status(rfleet_t *f, int *taken, int *status, int *K_seen, int cap)
+{
+    if (!f || cap < 0) return REKF_ERR_INVALID;
+    const int n = (int)f->link_known.size();
+    if (n > cap) return REKF_ERR_BUFFER;
+    const int rc = rfleet_sync(f);
+    if (rc != REKF_OK) return rc;
+    long emptied = 0;
+    for (int i = 0; i < n; ++i) {
+        const FleetLinkStatus st = f->link_known[(size_t)i] ? FleetLinkStatus{0, 0, 0, 0} : f->link_stat.h[i];
+        if (taken) taken[i] = st.taken;
+        if (status) status[i] = st.status;
+        if (K_seen) K_seen[i] = st.K_seen;
+        emptied += st.status != 0;
+    }
+    if (!f->link_counted) f->link_emptied += emptied;
+    f->link_counted = true;
+    return n;
+}
+
+int rfleet_link_counts(rfleet_t *f, long *submits, long *binds, long *scans, long *emptied)
+{
+    if (!f) return REKF_ERR_INVALID;
+    if (submits) *submits = f->link_submits;
+    if (binds) *binds = f->link_binds;
+    if (scans) *scans = f->link_scans;
+    if (emptied) *emptied = f->link_emptied;
+    return REKF_OK;
 }
 
 int rfleet_get_poses(rfleet_t *f, double *t, double *mu3, double *sigma3x3)

@@ -24,6 +24,12 @@ velocity, mean, the covariance's lower triangle) into one ``FleetSnapshot`` blob
 puts a blob's entries into any members of any fleet whose capacity holds them with ONE launch (k_fleet_unpack), zeros beyond n included:
 a checkpoint (``save`` / ``load``), robots that move between fleets, a fleet seeded from yesterday's maps.
 
+A tick whose scans come from a detector fleet needs no host between the two launches: ``submit_linked(events, det.link())`` takes
+``linked_scan_event``s -- scans whose centres the detector's launch is still producing -- makes the fleet's stream wait for that launch
+and lets ONE launch of k_fleet_bind move every scan's centres and count into the call's segment on the device, in front of the step
+launch.  The tick: ``det.submit(scans)`` -> ``flt.submit_linked(odometry + fleet_detect.linked_scan_events(det.link()), link)`` ->
+``flt.poses()`` (the one wait) -> ``det.collect()``.  ``link_status()`` tells which scans a bind left empty and why.
+
 All arithmetic happens in the HIP kernel behind librfleet.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -41,6 +47,7 @@ MAX_OBS = 32
 MAX_OBS_WIDE = 256            # per scan on a fleet with wide scans switched on (RFLEET_MAX_OBS_WIDE)
 MAX_MAP_POINTS = 2048
 EV_ODOM, EV_SCAN = 0, 1
+EV_SCAN_LINKED = 2            # a scan of ``submit_linked`` whose observations are an entry of a detector fleet's link
 
 
 class RfleetEvent(C.Structure):
@@ -161,6 +168,19 @@ _snapshot_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_snapshot", "rfleet
                              _declare_snapshot)
 
 
+def _declare_link(L):
+    """``rfleet()`` with the argtypes of the linked submit's calls set.  They were added without a new ABI version and are looked up
+    by name: raises LibraryMissing when the built library has none; every other call keeps working then."""
+    lp = C.POINTER(C.c_long)
+    L.rfleet_submit_linked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.rfleet_link_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.rfleet_link_counts.argtypes = [C.c_void_p, lp, lp, lp, lp]
+
+
+_link_lib = _lib.Feature(rfleet, "librfleet.so", ("rfleet_submit_linked", "rfleet_link_status", "rfleet_link_counts"),
+                         [("rfleet_sizeof_link", _lib.Rlink)], _declare_link)
+
+
 class FleetSnapshot:
     """The full states of some members of a fleet as ONE blob of bytes (``blob``, np.uint8; the layout is include/rfleet.h's): what
     ``ReflectorEKFSLAMFleet.snapshot`` returns and ``restore`` takes.  Entry g is the g-th member listed.  Views of the blob:
@@ -278,6 +298,14 @@ def scan_event(member, t, cloud, pose_fix=None):
     return (int(member), EV_SCAN, float(t), (0.0, 0.0, 0.0), cloud, tuple(float(v) for v in pose_fix))
 
 
+def linked_scan_event(member, t, entry, pose_fix=None):
+    """A scan whose observations are entry ``entry`` of the link handed to ``submit_linked`` (a detector fleet's ``link()``): the
+    filter's host never sees them.  ``t``: the entry's stamp; pose_fix as for ``scan_event``."""
+    if pose_fix is None:
+        return (int(member), EV_SCAN_LINKED, float(t), (0.0, 0.0, 0.0), int(entry))
+    return (int(member), EV_SCAN_LINKED, float(t), (0.0, 0.0, 0.0), int(entry), tuple(float(v) for v in pose_fix))
+
+
 class ReflectorEKFSLAMFleet(_lib.Handle):
     """B independent ekf::ReflectorEKFSLAM filters on one MI355X, one kernel launch per ``submit``."""
     _destroy = "rfleet_destroy"
@@ -341,6 +369,8 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
                 keep.append(cloud)
                 e.xy = cloud.ctypes.data if cloud.size else None
                 e.K = cloud.size >> 1
+            elif kind == EV_SCAN_LINKED:
+                e.K = int(cloud)                             # (the entry of the link: ``linked_scan_event``)
             if fix is not None:
                 e.has_pose_fix = 1
                 e.pose_fix[0], e.pose_fix[1], e.pose_fix[2] = float(fix[0]), float(fix[1]), float(fix[2])
@@ -360,6 +390,46 @@ class ReflectorEKFSLAMFleet(_lib.Handle):
         rc = self._L.rfleet_submit(self._h, C.cast(packed[0], C.c_void_p), packed[1])
         if rc != 0:
             self._chk(rc, "rfleet_submit")
+
+    # -- the detector's centres bound on the device ------------------------------------
+    def submit_linked_code(self, events, link) -> int:
+        """rfleet_submit_linked as it is: ``link`` a ``fleet_detect.DetectLink``, a ``_lib.Rlink`` or None."""
+        arr, count, _keep = self.pack(events)
+        raw = getattr(link, "raw", link)
+        return _link_lib().rfleet_submit_linked(self._h, C.cast(arr, C.c_void_p), count, None if raw is None else C.addressof(raw))
+
+    def submit_linked(self, events, link):
+        """``submit`` for a call that holds ``linked_scan_event``s (``fleet_detect.linked_scan_events(link)``): scans whose centres
+        the detector fleet's launch is still producing.  The host waits for nothing and never sees the centres: the fleet's stream
+        waits for the detector's launch, ONE launch of k_fleet_bind moves every linked scan's centres and count into the call's
+        segment, and the step launch follows.  A scan whose record holds an error or more centres than the fleet takes is applied as
+        an EMPTY scan (``link_status`` tells).  Everything is validated first; events of the other kinds may be mixed in."""
+        rc = self.submit_linked_code(events, link)
+        if rc != 0:
+            self._chk(rc, "rfleet_submit_linked")
+
+    def link_status(self):
+        """-> (taken [S], status [S], K_seen [S]) of the S linked scans of the last ``submit_linked`` that held one, in event order:
+        the centres the filter took, 0 or why it took none (the record's own error, -4 for a count outside the record, -3 for more
+        than the fleet takes), and the count as read.  Synchronises."""
+        L = _link_lib()
+        cap = 64
+        while True:
+            out = np.zeros((3, cap), np.int32)
+            n = L.rfleet_link_status(self._h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, cap)
+            if n != -6:                                      # (REKF_ERR_BUFFER: more linked scans than ``cap``)
+                break
+            cap *= 4
+        if n < 0:
+            self._chk(n, "rfleet_link_status")
+        return out[0, :n].copy(), out[1, :n].copy(), out[2, :n].copy()
+
+    def link_counts(self):
+        """-> (linked submits, launches of k_fleet_bind, linked scans, linked scans a bind left empty) since the fleet was made.
+        Host counters; the last is brought up to date by ``link_status``."""
+        v = [C.c_long() for _ in range(4)]
+        self._chk(_link_lib().rfleet_link_counts(self._h, *(C.byref(x) for x in v)), "rfleet_link_counts")
+        return tuple(int(x.value) for x in v)
 
     def poses(self):
         """-> (t [B], mu [B, 3], sigma [B, 3, 3]) of all members.  Synchronises; no copy of any state."""

@@ -93,6 +93,54 @@ def _declare_batch3(L):
 _batch3_lib = _lib.Feature(_rdet, "librdet.so", ("rdet3d_batch_create",), [("rdet3d_batch_sizeof_cloud", Rdet3dCloud)], _declare_batch3)
 
 
+def _declare_link2(L):
+    """``_batch_lib()`` with the argtypes of rdet2d_batch_link set.  It was added without a new ABI version and is looked up by name:
+    raises LibraryMissing when the built library has none; every other call keeps working then."""
+    L.rdet2d_batch_link.argtypes = [C.c_void_p, C.c_void_p]
+
+
+def _declare_link3(L):
+    """``_batch3_lib()`` with the argtypes of rdet3d_batch_link set; as ``_declare_link2``."""
+    L.rdet3d_batch_link.argtypes = [C.c_void_p, C.c_void_p]
+
+
+_link2_lib = _lib.Feature(_batch_lib, "librdet.so", ("rdet2d_batch_link",), [("rdet_sizeof_link", _lib.Rlink)], _declare_link2)
+_link3_lib = _lib.Feature(_batch3_lib, "librdet.so", ("rdet3d_batch_link",), [("rdet_sizeof_link", _lib.Rlink)], _declare_link3)
+
+
+class DetectLink:
+    """One outstanding submit of a detector fleet as the fleet filter takes it (``ReflectorEKFSLAMFleet.submit_linked``): ``raw`` the
+    ``struct rlink`` (include/rlink.h), and copies of what the detector's host knows per entry -- ``members``, ``stamps``, ``status``
+    (0, or what ``collect`` will report from the host alone, e.g. -3 for a malformed scan) and ``records`` (-1: no workgroup runs for
+    the entry, it is empty).  ``raw`` points into the detector's handle: it holds until that detector's next submit."""
+
+    def __init__(self, raw, owner=None):
+        self.raw, self._owner = raw, owner
+        n = int(raw.count)
+
+        def column(address, tp, dtype):
+            return np.array((tp * n).from_address(address), dtype=dtype) if n else np.zeros(0, dtype)
+
+        self.members = column(raw.member, C.c_int, np.int32)
+        self.stamps = column(raw.stamp, C.c_double, np.float64)
+        self.status = column(raw.host_status, C.c_int, np.int32)
+        self.records = column(raw.record, C.c_int, np.int32)
+
+    def __len__(self):
+        return int(self.raw.count)
+
+
+def linked_scan_events(link, pose_fixes=None):
+    """The ``ReflectorEKFSLAMFleet.submit_linked`` events of one tick whose scans are still being detected: one
+    ``fleet.linked_scan_event`` per entry of ``link`` with host status 0 -- the omission rule of ``scan_events``, as far as the host can
+    apply it: what only the launch knows (the kernel's own error, too many centres) empties the scan on the device instead.
+    ``pose_fixes``: None, or per ENTRY an (x, y, yaw) or None."""
+    if pose_fixes is not None and len(pose_fixes) != len(link):
+        raise ValueError("one pose fix (or None) per entry of the link")
+    return [fleet.linked_scan_event(int(link.members[i]), float(link.stamps[i]), i, None if pose_fixes is None else pose_fixes[i])
+            for i in range(len(link)) if link.status[i] == 0]
+
+
 def cloud_events(clouds, observations):
     """``scan_events`` for a 3D tick given as ``PointCloudReflectorDetectFleet.submit`` takes it in its first form
     ([(member, stamp, xyzi), ...]): one ``fleet.scan_event`` per cloud with status 0, nothing truncated."""
@@ -117,7 +165,7 @@ def scan_events(scans, observations):
 class _DetectFleet(_lib.Handle):
     """What the two detector fleets share: a handle of the ``_prefix`` calls, made for one ``_Options`` per member, whose submit
     takes the records of ``pack``."""
-    _prefix = _Options = None
+    _prefix = _Options = _link_lib = None
 
     def _create(self, L, opts, capacity, device, sensor_to_base_link):
         """The handle for ``opts`` (one ``_Options`` per member); ``sensor_to_base_link``: None, one (x, y, yaw) for all, or [B, 3]."""
@@ -192,10 +240,24 @@ class _DetectFleet(_lib.Handle):
         self.submit(scans)
         return self.collect(max_centers)
 
+    def link_code(self):
+        """-> (rc, ``_lib.Rlink``) of the class's ``_link`` call on the submit that has not been collected."""
+        raw = _lib.Rlink()
+        return getattr(self._link_lib(), self._prefix + "_link")(self._h, C.addressof(raw)), raw
+
+    def link(self) -> DetectLink:
+        """The submit that has not been collected as ``ReflectorEKFSLAMFleet.submit_linked`` takes it: launches nothing, waits for
+        nothing.  Valid between ``submit`` and ``collect`` (raises otherwise); ``collect`` afterwards is still how the host gets the
+        centres, and behind the filter's own wait it returns at once."""
+        rc, raw = self.link_code()
+        self._chk(rc, self._prefix + "_link")
+        return DetectLink(raw, self)
+
 
 class LaserReflectorDetectFleet(_DetectFleet):
     """B reflector_detect::LaserReflectorDetect on one MI355X, one kernel launch per ``submit``."""
     _prefix, _destroy, _Options = "rdet2d_batch", "rdet2d_batch_destroy", Rdet2dOptions
+    _link_lib = _link2_lib        # (looked up on the first ``link()``: a library without it still serves everything else)
 
     def __init__(self, options_list, max_beams: int = MAX_BEAMS, device: int = 0, sensor_to_base_link=None):
         L = _batch_lib()
@@ -295,6 +357,7 @@ class LaserReflectorDetectFleet(_DetectFleet):
 class PointCloudReflectorDetectFleet(_DetectFleet):
     """B reflector_detect::PointCloudReflectorDetect on one MI355X, one kernel launch per ``submit``."""
     _prefix, _destroy, _Options = "rdet3d_batch", "rdet3d_batch_destroy", Rdet3dOptions
+    _link_lib = _link3_lib
 
     def __init__(self, options_list, max_points: int = 65536, device: int = 0, sensor_to_base_link=None):
         L = _batch3_lib()
