@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+from types import SimpleNamespace
 
 import numpy as np
 from scipy.sparse import coo_matrix
@@ -42,8 +43,22 @@ def _d2_f32(a: np.ndarray, b: np.ndarray) -> np.ndarray:
 
 def detect3d_witness(xyzi, intensity_min=160.0, sensor_to_base_link=(0.0, 0.0, 0.0)):
     """-> (centers (K,2) float32, n_after_intensity, n_after_sor)."""
+    d = detect3d_witness_detail(xyzi, intensity_min, sensor_to_base_link)
+    return d.centers, d.M, d.M2
+
+
+def detect3d_witness_detail(xyzi, intensity_min=160.0, sensor_to_base_link=(0.0, 0.0, 0.0)):
+    """-> a namespace: centers, M, M2 (the triple of detect3d_witness) and what they came from:
+      rows        [M]  the input rows that pass the intensity gate, in arrival order (a survivor's position here is its NODE number);
+      dist        [M]  float32 mean distance to the MeanK nearest neighbours (zeros where M <= MeanK);
+      thr              the outlier threshold mean + 0.5 sigma (double; NaN keeps everything);
+      kept        [M2] the nodes the outlier removal keeps;
+      components       [(nodes ascending = arrival order, accepted)] every connected component of the kept points, in order of
+                       its first member, whether the size gate [4, 160] accepts it or not;
+      order            the accepted components (indices into `components`) in output order: centers[k] is of components[order[k]]."""
     xyzi = np.ascontiguousarray(xyzi, dtype=np.float32).reshape(-1, 4)
-    pts = xyzi[xyzi[:, 3].astype(np.float64) > float(intensity_min), :3]          # :31-37
+    rows = np.flatnonzero(xyzi[:, 3].astype(np.float64) > float(intensity_min))
+    pts = xyzi[rows, :3]                                                          # :31-37
     M = pts.shape[0]
     # ---- StatisticalOutlierRemoval, MeanK = 30, StddevMulThresh = 0.5 (:43-47)
     dist = np.zeros(M, np.float32)
@@ -72,10 +87,12 @@ def detect3d_witness(xyzi, intensity_min=160.0, sensor_to_base_link=(0.0, 0.0, 0
     else:
         thr = float("nan")
     keep = ~(dist.astype(np.float64) > thr)
+    kept = np.flatnonzero(keep)
     q = pts[keep]
     M2 = q.shape[0]
     # ---- EuclideanClusterExtraction: tolerance 0.2, sizes [4, 160] (:65-74)
     centers = np.zeros((0, 2), np.float32)
+    components, order = [], []
     if M2 > 0:
         tree = cKDTree(q.astype(np.float64))
         pairs = tree.query_pairs(TOL * 1.001, output_type="ndarray")
@@ -86,8 +103,12 @@ def detect3d_witness(xyzi, intensity_min=160.0, sensor_to_base_link=(0.0, 0.0, 0
         g = coo_matrix((np.ones(pairs.shape[0], np.int8), (pairs[:, 0], pairs[:, 1])), shape=(M2, M2))
         ncomp, lab = connected_components(g, directed=False)
         comps = [np.nonzero(lab == c)[0] for c in range(ncomp)]
+        every = sorted(comps, key=lambda c: int(c[0]))
+        components = [(kept[c], bool(MIN_SIZE <= c.size <= MAX_SIZE)) for c in every]
         comps = [c for c in comps if MIN_SIZE <= c.size <= MAX_SIZE]
         comps.sort(key=lambda c: (-c.size, int(c[0])))          # size descending; ties (unspecified in PCL): first member ascending
+        at = {int(c[0]): k for k, c in enumerate(every)}
+        order = [at[int(c[0])] for c in comps]
         sx, sy, sa = (np.float32(v) for v in sensor_to_base_link)
         cs, sn = np.float32(_libm.cosf(float(sa))), np.float32(_libm.sinf(float(sa)))
         out = []
@@ -102,4 +123,4 @@ def detect3d_witness(xyzi, intensity_min=160.0, sensor_to_base_link=(0.0, 0.0, 0
             y = np.float32(np.float32(np.float32(sn * cx) + np.float32(cs * cy)) + sy)
             out.append((x, y))
         centers = np.array(out, np.float32).reshape(-1, 2)
-    return centers, M, M2
+    return SimpleNamespace(centers=centers, M=M, M2=M2, rows=rows, dist=dist, thr=thr, kept=kept, components=components, order=order)
