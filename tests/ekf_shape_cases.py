@@ -138,14 +138,17 @@ class Builder:
     """Lays the scans of a case down one after the other on a run of oracle/ekf_numpy.py (the predicted pose and the current
     means of the reflectors are where the observations are placed)."""
 
-    def __init__(self, L, model, seed, cap, auto_grow=False, n_map=0, map_cov=None):
-        """n_map > 0: a pre-loaded map of that many points, free lattice cells (so at least 1.6 m from every reflector and every
+    def __init__(self, L, model, seed, cap, auto_grow=False, n_map=0, map_cov=None, grid=GRID):
+        """grid: the lattice has grid x grid cells (256 by default; tests/ekf_range_cases.py needs more reflectors than that).  Positions
+        are float32 values whatever the lattice's size (pitch 2 m: below 2^7 m up to grid = 63, 2^-17 m apart there).
+        n_map > 0: a pre-loaded map of that many points, free lattice cells (so at least 1.6 m from every reflector and every
         new point); map_cov: its weights (n_map x 4, row-major 2 x 2), identity when None."""
         rng = self.rng = np.random.default_rng(seed)
         self.L0, self.model, self.cap, self.auto_grow = L, model, cap, auto_grow
         n = 3 + 2 * L
-        cells = rng.permutation(GRID * GRID)
-        pts = np.stack([cells % GRID, cells // GRID], -1) * PITCH + rng.uniform(-JITTER, JITTER, size=(GRID * GRID, 2))
+        assert L < grid * grid <= 63 * 63
+        cells = rng.permutation(grid * grid)
+        pts = np.stack([cells % grid, cells // grid], -1) * PITCH + rng.uniform(-JITTER, JITTER, size=(grid * grid, 2))
         pts = pts.astype(np.float32).astype(np.float64)
         lm, free = pts[:L], pts[L:]
         if L >= 2:
@@ -160,7 +163,7 @@ class Builder:
             assert np.array_equal(self.map_xy.astype(np.float64), np.asarray(free[:n_map]))
             self.map_cov = np.tile(np.asarray((1.0, 0.0, 0.0, 1.0)), (n_map, 1)) if map_cov is None else np.asarray(map_cov, np.float64).reshape(n_map, 4)
         mu = np.zeros(n)
-        mu[0:2] = 0.5 * GRID * PITCH + rng.uniform(-1.5, 1.5, size=2)
+        mu[0:2] = 0.5 * grid * PITCH + rng.uniform(-1.5, 1.5, size=2)
         mu[2] = rng.uniform(-3.0, 3.0)
         mu[3:] = lm.reshape(-1)
         P = dense_spd(n, rng, 10.0 ** rng.uniform(-3.7, -2.3))     # as fleet_cases.sweep_case: diagonal 3e-4 .. 6e-3
@@ -171,6 +174,7 @@ class Builder:
             self.ek.set_map(self.map_xy, self.map_cov)
         self.events, self.expect, self.kept, self.marg, self.map_marg = [], {}, {}, {}, {}
         self.fix_rng = None
+        self.cond = None                      # a dict: cond(S) of every scan is recorded as the scan is laid down (else case() runs cond_S_of)
 
     def with_fixes(self, seed):
         self.fix_rng = np.random.default_rng(seed)
@@ -185,7 +189,7 @@ class Builder:
         points).  On a full filter the far ones are dropped, on any other they become reflectors."""
         rng, ek, k = self.rng, self.ek, len(self.events)
         t = T0 + DT * (k + 1)
-        mu_p = ek.predict_state(t)[0]
+        mu_p, P_p = ek.predict_state(t)
         pose = tuple(float(v) for v in mu_p[:3])
         n_s, n_m = len(ids), len(map_ids)
         assert n_m == 0 or self.map_xy is not None
@@ -227,6 +231,8 @@ class Builder:
         self.expect[k] = (pairs, mpairs, [] if dropped else new) if has_map else (pairs, [] if dropped else new)
         kc = cloud if keep is None else np.ascontiguousarray(cloud[keep])
         self.marg[k] = margins(mu_p, kc)
+        if self.cond is not None and pairs:
+            self.cond[k] = float(np.linalg.cond(FC.innovation_cov(mu_p, P_p, pairs)))
         for a, b in self.marg[k]:
             assert a >= MARGIN_MIN and b >= MARGIN_MIN, (k, a, b)      # no case is excused
         if has_map:
@@ -285,7 +291,7 @@ class Builder:
         if self.map_xy is not None:
             c.map_xy, c.map_cov, c.use, c.map_margins = self.map_xy, self.map_cov, True, self.map_marg
         c.margins = self.marg
-        c.cond_S = cond_S_of(c)
+        c.cond_S = cond_S_of(c) if self.cond is None else dict(self.cond)
         c.flags = FC.FLAG_CAPACITY if self.kept else 0
         c.auto_grow = self.auto_grow
         c.sets = getattr(self, "sets", None)

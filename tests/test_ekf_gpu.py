@@ -158,7 +158,9 @@ def test_c3_full_size_steps_match_oracle(c3_built, oracle_lib):
 
 @pytest.mark.parametrize("L", [1472, 2048])
 def test_states_beyond_the_baseline_size_take_the_generic_downdate_loop(oracle_lib, L):
-    """n = 2947 / 4099 (T = 46 / 64 tile rows): class-B workgroups of k_downdate2 hold 5 / 11 tiles, i.e. the generic tile
+    """n = 2947 / 4099 (T = 47 / 65 tile rows): on 256 CUs class-B workgroups of k_downdate2 hold 4 or 5 / 10 or 11 tiles
+    (tests/downdate_schedule.py: host_plan(47, 256) = lo 4, x 199, sub 2; host_plan(65, 256) = lo 10, x 106, sub 2;
+    tests/test_ekf_ranges_cpu.py pins these figures), i.e. the generic tile
     loop instead of the straight-line code of the BASELINE sizes (<= 4 tiles).  A synthetic state is loaded into both paths
     (landmarks on a grid, a random SPD covariance), then a few updates with 32 observations each."""
     rng = np.random.default_rng(L)
