@@ -63,9 +63,10 @@ def wrap(a):
     return math.atan2(math.sin(a), math.cos(a))
 
 
-def wide_case(name, L, scans, model, seed, use=False, max_landmarks=128, heading=None, turn=0.0, **tags):
+def wide_case(name, L, scans, model, seed, use=False, max_landmarks=128, heading=None, turn=0.0, fix_offset=FIX_OFFSET, **tags):
     """heading: the PREDICTED heading of scan 0 (the prior's is set so that Predict arrives there); turn: scan 0 was taken at the
-    predicted pose turned by this much, so that the update has to carry the heading there."""
+    predicted pose turned by this much, so that the update has to carry the heading there; fix_offset: where a fix stands against
+    the pose its scan was taken at."""
     rng = np.random.default_rng(seed)
     n = 3 + 2 * L
     cells = rng.permutation(GRID * GRID)
@@ -139,7 +140,7 @@ def wide_case(name, L, scans, model, seed, use=False, max_landmarks=128, heading
                 case.flags = FC.FLAG_CAPACITY
         fix = None
         if sp.fix:
-            fix = (pose[0] + FIX_OFFSET[0], pose[1] + FIX_OFFSET[1], wrap(pose[2] + FIX_OFFSET[2]))
+            fix = (pose[0] + fix_offset[0], pose[1] + fix_offset[1], wrap(pose[2] + fix_offset[2]))
         case.events.append((EV_SCAN, t, (0.0, 0.0, 0.0), cloud, fix))
         case.expect[k] = (spairs, mpairs, new)
         if len(keep) < len(toks):
