@@ -1,7 +1,8 @@
 // batch_host.h -- the buffers a handle owns: the kinds a fleet handle shares with the device (Pinned, PinnedDefault, Staging) and the
 // two that copies run between (Device, Host).  Each knows how its memory was taken: what alloc() took, release() gives back the same
 // way, and release() of an empty buffer does nothing.  Plain aggregates: a handle holds them by value and releases them when it is
-// destroyed; nothing copies them (two of a handle's buffers may change places: std::swap).
+// destroyed; nothing copies them (two of a handle's buffers may change places: std::swap).  LinkEvents, the two events of a
+// producer's rlink, is released the same way.
 #pragma once
 #include "host_visible.h"
 
@@ -94,6 +95,37 @@ hipError_t reserve(Buf &b, size_t &cap, size_t need, size_t first)
     if (e == hipSuccess) cap = c;
     return e;
 }
+
+// The two events of a producer's rlink (include/rlink.h) and whether a link of its outstanding submit was taken.  `ready` is recorded
+// behind the producer's launch, `consumed` by the consumer once everything that reads the records is enqueued; both are made by
+// the first link.
+struct LinkEvents {
+    hipEvent_t ready = nullptr, consumed = nullptr;
+    bool taken = false;
+    // before a submit: a link of the submit before was taken (*linked) -> the consumer's reads of the records come first, on the stream
+    hipError_t wait(hipStream_t stream, bool *linked)
+    {
+        *linked = taken;
+        const hipError_t e = taken ? hipStreamWaitEvent(stream, consumed, 0) : hipSuccess;
+        if (e == hipSuccess) taken = false;
+        return e;
+    }
+    // a link is taken: `ready` behind everything the stream holds
+    hipError_t record(hipStream_t stream)
+    {
+        hipError_t e = ready ? hipSuccess : hipEventCreateWithFlags(&ready, hipEventDisableTiming);
+        if (e == hipSuccess && !consumed) e = hipEventCreateWithFlags(&consumed, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ready, stream);
+        if (e == hipSuccess) taken = true;
+        return e;
+    }
+    void release()
+    {
+        if (consumed) { (void)hipEventSynchronize(consumed); (void)hipEventDestroy(consumed); }   // (a consumer may still read the records)
+        if (ready) (void)hipEventDestroy(ready);
+        ready = consumed = nullptr;
+    }
+};
 
 // release() of every buffer named: what a handle's destroy calls
 template <typename... B>

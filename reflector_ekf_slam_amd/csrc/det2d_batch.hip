@@ -17,51 +17,25 @@
 // Per beam the workgroup keeps 15 B in LDS (range, point, last valid beam, flags) plus the run tables: 141 KB at the 8192-beam
 // limit.  The contributions to the centres (8 B per beam) go to a per-member slice in device memory that only this workgroup
 // touches, ordered by a __syncthreads(); the de-skewed returns go straight to the member's point-cloud buffer, compacted.
-#include "../../include/rdet.h"
-#include "batch_host.h"
-
-#include <hip/hip_runtime.h>
+//
+// Here: the kernels, the handle's buffers, the copies and the launches.  The host's rules that need no HIP call are det_batch_host.h's
+// (tested without a GPU), create / destroy / link / collect as both detector handles make them det_batch_dev.h's.
+#include "det_batch_dev.h"         // det_batch_host.h: BatchRec, RangeRec and the host's rules
 
 #include <cmath>
-#include <cstddef>
 #include <cstdio>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
+
+namespace host = det_batch_host;
+namespace dev = det_batch_dev;
 
 namespace {
 
-// PoseExtrapolator sample (see det2d.hip): yaw = 2 atan2(q.z, q.w) taken once on the host
-struct Odom {
-    double time, px, py, yaw, vx, vy, wz;
-};
+using det_batch_host::BatchRec;
+using det_batch_host::Odom;
+using det_batch_host::RangeRec;
 
 struct R2d { double x, y, a; };
 struct R2f { float x, y, a; };
-
-#define RDET2DB_MAX_BEAMS 8192            // a workgroup holds its whole scan in LDS
-#define RDET2DB_TABLES 8                  // cached beam-angle tables
-
-// One scan of a call: everything k_det2d_batch needs that is not a beam.  An array of these, indexed by blockIdx.x, lies in
-// the call's staging segment.
-struct BatchRec {
-    // options (laser_reflector_detect.h:8-15)
-    double intensity_min, min_length, length_error;
-    double first_point_time, point_delta_t;
-    // pose extrapolator state: 0, 1 or 2 samples (front, back)
-    Odom front, back;
-    int n_odom;
-    float opt_range_min, opt_range_max;
-    // message header
-    float msg_range_min, msg_range_max, angle_increment;
-    int N, is_circle;
-    int member;                    // whose staging slice, scratch slice and point-cloud buffer
-    int table;                     // which cached beam-angle table
-    int run;                       // 0: nothing to detect (N == 0 or a malformed message): the slot is cleared
-    // sensor_to_base_link as Rigid2f + host-evaluated cos/sin of its angle
-    float s2b_x, s2b_y, s2b_a, s2b_c, s2b_s;
-};
 
 // What a scan hands back, in pinned host memory: plain stores, published by the end of the kernel
 struct BatchOut {
@@ -520,15 +494,6 @@ __global__ __launch_bounds__(1024) void k_det2d_batch(BatchBufs B)
 // 8-byte stores, every pair between them as one 16-byte store.  The load of a pair is one 16-byte load when the source is on the
 // same grid ((src_off + i) even), else two 8-byte loads: uniform over the record.  A member with n rows costs
 // ceil((n + lead) / RDET2DB_RANGE_TILE) workgroups, an empty one none.
-#define RDET2DB_RANGE_THREADS 256
-#define RDET2DB_RANGE_TILE (2 * RDET2DB_RANGE_THREADS)    // rows (slots) per workgroup
-
-struct RangeRec {
-    long long src_off;             // the member's first row in `returns` (member * max_beams)
-    long long dst_off;             // its first row in the output
-    int n, pad;
-};
-
 struct RangeBufs {
     const RangeRec *recs;          // [records], pinned host memory
     const int2 *wgmap;             // (record, tile) per workgroup, pinned host memory
@@ -559,76 +524,65 @@ __global__ __launch_bounds__(RDET2DB_RANGE_THREADS) void k_det2d_batch_range_dat
 }  // namespace
 
 // =================================================================================================
-struct rdet2d_batch_member {
-    rdet2d_options opt;
-    double s2b[3];
-    std::vector<Odom> odom;            // PoseExtrapolator::odometry_data_
-    int last_n_returns = 0;
-};
-
-struct rdet2d_batch_table {
-    int N = -1;
-    float angle_min = 0.f, inc = 0.f;
-    unsigned long long used = 0;       // the submit that used it last
-};
-
-struct rdet2d_batch {
-    int B = 0, max_beams = 0, device = 0;
-    hipStream_t stream = nullptr;
-    std::vector<rdet2d_batch_member> m;
+// The handle
+struct rdet2d_batch : dev::Handle {
+    int max_beams = 0;
+    std::vector<host::Member2d> m;
     // the staging area the host writes and the kernel reads in place: fine-grained DEVICE memory through the PCIe BAR where
     // the platform maps it, else pinned host memory (host_visible.h)
     batch_host::Staging<float> stage;  // [B][2][max_beams]
     batch_host::Pinned<BatchRec> recs; // [B]
     batch_host::Pinned<BatchOut> out;  // [B]
-    float *h_tables = nullptr;         // pinned image of d_tables
-    float *d_tables = nullptr;         // [RDET2DB_TABLES + B][3][max_beams]: the cached tables, then one per member for a call with more lidars than those
-    unsigned long long *d_contrib = nullptr;
-    float2 *d_returns = nullptr;
-    rdet2d_batch_table tab[RDET2DB_TABLES];
-    unsigned long long n_submit = 0;
-    // the submit that has not been collected
-    bool outstanding = false;
-    int sub_count = 0;
-    std::vector<int> sub_member, sub_status, sub_runs;
-    std::vector<double> sub_stamp;
-    std::vector<char> seen;
-    // rdet2d_batch_link (include/rlink.h): the record index of every entry of the outstanding submit; `ready`, recorded by link behind
-    // the launch, and `consumed`, recorded by the consumer: both made by the first link; a link of the outstanding submit was taken
-    std::vector<int> sub_record;
-    hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
-    bool link_taken = false;
+    batch_host::Host<float> h_tables;  // pinned image of d_tables
+    batch_host::Device<float> d_tables;   // [RDET2DB_TABLES + B][3][max_beams]: the cached tables, then one per member for a call with more lidars than those
+    batch_host::Device<unsigned long long> d_contrib;
+    batch_host::Device<float2> d_returns;
+    host::TableCache tables;
+    std::vector<host::TableUse> use;   // [B]: the tables of the call being submitted
     // rdet2d_batch_get_range_data_all, allocated by its first call that launches: the rows of a call, and its records with the
     // workgroup table behind them
     batch_host::Pinned<float2> rd_out;           // [B][max_beams]
-    batch_host::Pinned<unsigned char> rd_tab;    // RangeRec[B] | int2 [B * range_tiles]
-    std::string hip_error;
+    batch_host::Pinned<unsigned char> rd_tab;    // RangeRec[B] | RangeTile[B * range_tiles]
 };
-
-#define DETB_TRY(h, expr)                                                           \
-    do {                                                                            \
-        hipError_t e_ = (expr);                                                     \
-        if (e_ != hipSuccess) {                                                     \
-            if (h) (h)->hip_error = std::string(#expr) + ": " + hipGetErrorString(e_); \
-            return RDET_ERR_HIP;                                                    \
-        }                                                                           \
-    } while (0)
 
 namespace {
 
-bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; }
-
-bool malformed(const rdet2d_scan &s)
+// ---- 4 of submit: every scan that runs into its member's staging slice, unless it was received there; the tables plan_tables
+// wants filled into the pinned image and from there to the device, on the stream
+int submit_stage(rdet2d_batch *b, const rdet2d_scan *scans, int count)
 {
-    if (s.range_min < 0 || s.range_max <= s.range_min) return true;              // :27-32
-    return s.angle_increment < 0.f && s.angle_max <= s.angle_min;                // :33-38
+    const size_t mb = (size_t)b->max_beams;
+    for (int i = 0; i < count; ++i) {
+        if (!b->sub_runs[(size_t)i]) continue;
+        const rdet2d_scan &s = scans[i];
+        float *sr = b->stage.h + (size_t)s.member * 2 * mb, *si = sr + mb;
+        if (s.ranges != sr) std::memcpy(sr, s.ranges, sizeof(float) * (size_t)s.N);
+        if (s.intensities != si) std::memcpy(si, s.intensities, sizeof(float) * (size_t)s.N);
+        if (!b->use[(size_t)i].fill) continue;
+        const size_t at = (size_t)b->use[(size_t)i].table * 3 * mb;
+        host::fill_angle_table(b->h_tables.h + at, mb, s.angle_min, s.angle_increment, s.N);
+        for (size_t part = 0; part < 3; ++part)
+            DETB_TRY(b, hipMemcpyAsync(b->d_tables.d + at + part * mb, b->h_tables.h + at + part * mb, sizeof(float) * (size_t)s.N,
+                                       hipMemcpyHostToDevice, b->stream));
+    }
+    return RDET_OK;
 }
 
-int find_table(const rdet2d_batch *b, const rdet2d_scan &s)
+// ---- 5 of submit: one workgroup per scan of the call (a scan that does not run clears its record), and the submit is outstanding
+int submit_launch(rdet2d_batch *b, int count, int n_run, bool linked)
 {
-    for (int t = 0; t < RDET2DB_TABLES; ++t)
-        if (b->tab[t].N == s.N && same_bits(b->tab[t].angle_min, s.angle_min) && same_bits(b->tab[t].inc, s.angle_increment)) return t;
-    return -1;
+    b->outstanding = true;
+    if (n_run > 0) {
+        __atomic_thread_fence(__ATOMIC_SEQ_CST);              // write-combined stores drained before the doorbell
+        BatchBufs Bf;
+        Bf.recs = b->recs.dv; Bf.stage = b->stage.dv; Bf.tables = b->d_tables.d; Bf.contrib = b->d_contrib.d;
+        Bf.returns = b->d_returns.d; Bf.out = b->out.dv; Bf.max_beams = b->max_beams;
+        hipLaunchKernelGGL(k_det2d_batch, dim3((unsigned)count), dim3(1024), 0, b->stream, Bf);
+        DETB_TRY(b, hipGetLastError());
+    } else if (!linked) {
+        for (int i = 0; i < count; ++i) std::memset(&b->out.h[i], 0, 4 * sizeof(int));
+    }
+    return RDET_OK;
 }
 
 }  // namespace
@@ -643,17 +597,10 @@ int rdet2d_batch_create(const rdet2d_options *opts, const double *s2b_xyyaw, int
 {
     if (!opts || !s2b_xyyaw || !out || B < 1 || max_beams < 1) return RDET_ERR_INVALID;
     *out = nullptr;
-    rdet2d_batch_t *b = new (std::nothrow) rdet2d_batch();
+    rdet2d_batch_t *b = dev::make<rdet2d_batch>(opts, s2b_xyyaw, B, device);
     if (!b) return RDET_ERR_INVALID;
-    b->B = B; b->max_beams = max_beams; b->device = device;
-    b->m.resize((size_t)B);
-    for (int i = 0; i < B; ++i) {
-        b->m[(size_t)i].opt = opts[i];
-        std::memcpy(b->m[(size_t)i].s2b, s2b_xyyaw + 3 * i, sizeof(double) * 3);
-    }
-    b->sub_member.resize((size_t)B); b->sub_status.resize((size_t)B); b->sub_runs.resize((size_t)B);
-    b->sub_stamp.resize((size_t)B); b->seen.assign((size_t)B, 0);
-    b->sub_record.resize((size_t)B);
+    b->max_beams = max_beams;
+    b->use.reserve((size_t)B);
     const size_t nb = (size_t)max_beams, nB = (size_t)B;
     int rc = [&]() -> int {
         DETB_TRY(b, hipSetDevice(device));
@@ -662,10 +609,10 @@ int rdet2d_batch_create(const rdet2d_options *opts, const double *s2b_xyyaw, int
         DETB_TRY(b, b->recs.alloc(nB));
         DETB_TRY(b, b->out.alloc(nB));
         std::memset(b->out.h, 0, sizeof(BatchOut) * nB);
-        DETB_TRY(b, hipHostMalloc(&b->h_tables, 4 * nb * 3 * (RDET2DB_TABLES + nB)));
-        DETB_TRY(b, hipMalloc(&b->d_tables, 4 * nb * 3 * (RDET2DB_TABLES + nB)));
-        DETB_TRY(b, hipMalloc(&b->d_contrib, 8 * nb * nB));
-        DETB_TRY(b, hipMalloc(&b->d_returns, 8 * nb * nB));
+        DETB_TRY(b, b->h_tables.alloc(nb * 3 * (RDET2DB_TABLES + nB)));
+        DETB_TRY(b, b->d_tables.alloc(nb * 3 * (RDET2DB_TABLES + nB)));
+        DETB_TRY(b, b->d_contrib.alloc(nb * nB));
+        DETB_TRY(b, b->d_returns.alloc(nb * nB));
         return RDET_OK;
     }();
     if (rc != RDET_OK) { std::fprintf(stderr, "rdet2d_batch_create: %s\n", b->hip_error.c_str()); rdet2d_batch_destroy(b); return rc; }
@@ -676,23 +623,11 @@ int rdet2d_batch_create(const rdet2d_options *opts, const double *s2b_xyyaw, int
 void rdet2d_batch_destroy(rdet2d_batch_t *b)
 {
     if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->ev_consumed) { (void)hipEventSynchronize(b->ev_consumed); (void)hipEventDestroy(b->ev_consumed); }   // (a consumer may still read the records)
-    if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
-    (void)hipFree(b->d_tables); (void)hipFree(b->d_contrib); (void)hipFree(b->d_returns);
-    if (b->h_tables) (void)hipHostFree(b->h_tables);
-    b->stage.release(); b->recs.release(); b->out.release(); b->rd_out.release(); b->rd_tab.release();
-    if (b->stream) (void)hipStreamDestroy(b->stream);
+    dev::destroy(b, b->d_tables, b->d_contrib, b->d_returns, b->h_tables, b->stage, b->recs, b->out, b->rd_out, b->rd_tab);
     delete b;
 }
 
-int rdet2d_batch_set_sensor_to_base_link(rdet2d_batch_t *b, int member, const double xyyaw[3])
-{
-    if (!b || !xyyaw || member < 0 || member >= b->B) return RDET_ERR_INVALID;
-    std::memcpy(b->m[(size_t)member].s2b, xyyaw, sizeof(double) * 3);
-    return RDET_OK;
-}
+int rdet2d_batch_set_sensor_to_base_link(rdet2d_batch_t *b, int member, const double xyyaw[3]) { return dev::set_sensor_to_base_link(b, member, xyyaw); }
 
 int rdet2d_batch_handle_odometry(rdet2d_batch_t *b, int member, double t, const double pos_xy[2], const double quat_zw[2],
                                  double vx, double vy, double wz)
@@ -713,172 +648,31 @@ int rdet2d_batch_staging(rdet2d_batch_t *b, int member, float **ranges, float **
 int rdet2d_batch_submit(rdet2d_batch_t *b, const rdet2d_scan *scans, int count)
 {
     if (!b || count < 0 || (count > 0 && !scans) || b->outstanding) return RDET_ERR_INVALID;
-    // ---- validate the whole call: nothing changes before every scan has passed
-    {
-        int rc = RDET_OK;
-        for (int i = 0; i < count && rc == RDET_OK; ++i) {
-            const rdet2d_scan &s = scans[i];
-            if (s.member < 0 || s.member >= b->B || b->seen[(size_t)s.member] || s.N < 0 || (s.N > 0 && (!s.ranges || !s.intensities))) {
-                rc = RDET_ERR_INVALID;
-                break;
-            }
-            b->seen[(size_t)s.member] = 1;
-            if (s.N > b->max_beams || s.N > RDET2DB_MAX_BEAMS) rc = RDET_ERR_CAPACITY;
-        }
-        for (int i = 0; i < count; ++i)
-            if (scans[i].member >= 0 && scans[i].member < b->B) b->seen[(size_t)scans[i].member] = 0;
-        if (rc != RDET_OK) return rc;
-    }
-    if (count > b->B) return RDET_ERR_INVALID;      // (unreachable: one scan per member)
-    DETB_TRY(b, hipSetDevice(b->device));
-    // a link of the submit before was taken: the consumer's reads of the records come first, on the stream.  Until then the host
-    // leaves the records alone too (what it would clear below is never read: collect looks at sub_runs first)
-    const bool linked = b->link_taken;
-    if (linked) DETB_TRY(b, hipStreamWaitEvent(b->stream, b->ev_consumed, 0));
-    b->link_taken = false;
-    ++b->n_submit;
-    const size_t mb = (size_t)b->max_beams;
-    // the tables this call needs and already has: none of them may be the one that is replaced
-    for (int i = 0; i < count; ++i) {
-        const rdet2d_scan &s = scans[i];
-        if (s.N == 0 || malformed(s)) continue;
-        const int t = find_table(b, s);
-        if (t >= 0) b->tab[t].used = b->n_submit;
-    }
-    int n_run = 0;
-    for (int i = 0; i < count; ++i) {
-        const rdet2d_scan &s = scans[i];
-        rdet2d_batch_member &M = b->m[(size_t)s.member];
-        BatchRec &A = b->recs.h[i];
-        std::memset(&A, 0, sizeof(A));
-        b->sub_member[(size_t)i] = s.member;
-        b->sub_stamp[(size_t)i] = s.stamp;                                          // :26 (USE_CORRECT_TIME undefined)
-        b->sub_status[(size_t)i] = RDET_OK;
-        b->sub_runs[(size_t)i] = 0;
-        A.member = s.member;
-        if (malformed(s)) { b->sub_status[(size_t)i] = RDET_ERR_BAD_SCAN; continue; }   // (the member keeps its odometry and its range data)
-        if (s.N == 0) { M.last_n_returns = 0; continue; }
-        const int N = s.N;
-        A.run = 1;
-        b->sub_runs[(size_t)i] = 1;
-        ++n_run;
-        A.intensity_min = M.opt.intensity_min;
-        A.min_length = M.opt.reflector_min_length;
-        A.length_error = M.opt.reflector_length_error;
-        A.opt_range_min = M.opt.range_min; A.opt_range_max = M.opt.range_max;
-        A.msg_range_min = s.range_min; A.msg_range_max = s.range_max;
-        A.angle_increment = s.angle_increment;
-        const double last_point_time = s.stamp;                                     // :48
-        A.point_delta_t = (double)(s.scan_time / (float)N);                         // :49 (float / size_t)
-        A.first_point_time = last_point_time - s.scan_time;                         // :50
-        A.N = N;
-        A.is_circle = ((s.angle_max - s.angle_min - 2 * M_PI) < 1e-6) ? 1 : 0;      // :55
-        A.s2b_x = (float)M.s2b[0]; A.s2b_y = (float)M.s2b[1]; A.s2b_a = (float)M.s2b[2];   // :54
-        A.s2b_c = cosf(A.s2b_a); A.s2b_s = sinf(A.s2b_a);
-        // TrimDataByTime(first_point_time) (:52-53 -> pose_extrapolator.cc:12-26)
-        {
-            size_t drop = 0;
-            while (M.odom.size() - drop > 1 && M.odom[drop].time < A.first_point_time) ++drop;
-            if (drop) M.odom.erase(M.odom.begin(), M.odom.begin() + (long)drop);
-        }
-        A.n_odom = (int)(M.odom.size() > 2 ? 2 : M.odom.size());
-        if (!M.odom.empty()) { A.front = M.odom.front(); A.back = M.odom.back(); }
-        // the scan into the member's staging slice, unless it was received there
-        float *sr = b->stage.h + (size_t)s.member * 2 * mb, *si = sr + mb;
-        if (s.ranges != sr) std::memcpy(sr, s.ranges, sizeof(float) * (size_t)N);
-        if (s.intensities != si) std::memcpy(si, s.intensities, sizeof(float) * (size_t)N);
-        // beam-angle table: the float32 accumulation of :51/:175 and its cos/sin (:68), host libm; one per lidar
-        int t = find_table(b, s);
-        if (t < 0) {
-            int lru = 0;
-            for (int u = 1; u < RDET2DB_TABLES; ++u)
-                if (b->tab[u].used < b->tab[lru].used) lru = u;                      // least recently used
-            const bool cached = b->tab[lru].used != b->n_submit;                    // ... unless this call uses all of them: more lidars in
-            t = cached ? lru : RDET2DB_TABLES + s.member;                           // one call than cached tables -> the member's own, not kept
-            float *ta = b->h_tables + (size_t)t * 3 * mb, *tc = ta + mb, *ts = tc + mb;
-            float angle = s.angle_min;
-            for (int k = 0; k < N; ++k) {
-                ta[k] = angle; tc[k] = cosf(angle); ts[k] = sinf(angle);
-                angle += s.angle_increment;
-            }
-            float *dt = b->d_tables + (size_t)t * 3 * mb;
-            for (int part = 0; part < 3; ++part)
-                DETB_TRY(b, hipMemcpyAsync(dt + part * mb, ta + part * mb, sizeof(float) * (size_t)N, hipMemcpyHostToDevice, b->stream));
-            if (cached) { b->tab[t].N = N; b->tab[t].angle_min = s.angle_min; b->tab[t].inc = s.angle_increment; }
-        }
-        if (t < RDET2DB_TABLES) b->tab[t].used = b->n_submit;
-        A.table = t;
-    }
-    b->sub_count = count;
-    b->outstanding = true;
-    if (n_run > 0) {
-        __atomic_thread_fence(__ATOMIC_SEQ_CST);              // write-combined stores drained before the doorbell
-        BatchBufs Bf;
-        Bf.recs = b->recs.dv; Bf.stage = b->stage.dv; Bf.tables = b->d_tables; Bf.contrib = b->d_contrib;
-        Bf.returns = b->d_returns; Bf.out = b->out.dv; Bf.max_beams = b->max_beams;
-        hipLaunchKernelGGL(k_det2d_batch, dim3((unsigned)count), dim3(1024), 0, b->stream, Bf);
-        DETB_TRY(b, hipGetLastError());
-    } else if (!linked) {
-        for (int i = 0; i < count; ++i) std::memset(&b->out.h[i], 0, 4 * sizeof(int));
-    }
-    return RDET_OK;
+    int rc = host::validate_scans(scans, count, b->B, b->max_beams, b->seen);           // 1
+    bool linked = false;
+    if (rc == RDET_OK) rc = dev::begin_submit(b, &linked);
+    if (rc != RDET_OK) return rc;
+    host::plan_tables(b->tables, scans, count, b->use);                                 // 2
+    const int n_run = host::pack_scans(scans, count, b->m, b->use, *b, b->recs.h);      // 3
+    rc = submit_stage(b, scans, count);                                                 // 4
+    if (rc != RDET_OK) { b->tables = host::TableCache(); return rc; }                   // (a table planned and not uploaded)
+    return submit_launch(b, count, n_run, linked);                                      // 5
 }
 
-int rdet2d_batch_link(rdet2d_batch_t *b, rlink *out)
-{
-    if (!b || !out || !b->outstanding) return RDET_ERR_INVALID;
-    DETB_TRY(b, hipSetDevice(b->device));
-    if (!b->ev_ready) DETB_TRY(b, hipEventCreateWithFlags(&b->ev_ready, hipEventDisableTiming));
-    if (!b->ev_consumed) DETB_TRY(b, hipEventCreateWithFlags(&b->ev_consumed, hipEventDisableTiming));
-    DETB_TRY(b, hipEventRecord(b->ev_ready, b->stream));
-    for (int i = 0; i < b->sub_count; ++i) b->sub_record[(size_t)i] = b->sub_runs[(size_t)i] ? i : -1;
-    std::memset(out, 0, sizeof(*out));
-    out->count = b->sub_count;
-    out->device = b->device;
-    out->member = b->sub_member.data();
-    out->stamp = b->sub_stamp.data();
-    out->host_status = b->sub_status.data();
-    out->record = b->sub_record.data();
-    out->records = b->out.dv;
-    out->record_bytes = (long)sizeof(BatchOut);
-    out->k_off = (int)offsetof(BatchOut, K);
-    out->err_off = (int)offsetof(BatchOut, err);
-    out->centers_off = (int)offsetof(BatchOut, centers);
-    out->max_centers = RDET_MAX_CENTERS;
-    out->ready = b->ev_ready;
-    out->consumed = b->ev_consumed;
-    b->link_taken = true;
-    return RDET_OK;
-}
+int rdet2d_batch_link(rdet2d_batch_t *b, rlink *out) { return b ? dev::link(b, b->out.dv, out) : RDET_ERR_INVALID; }
 
 int rdet2d_batch_collect(rdet2d_batch_t *b, int *status, int *K, float *centers_xy, int max_centers, double *obs_time)
 {
-    if (!b || !b->outstanding) return RDET_ERR_INVALID;
-    const int count = b->sub_count;
-    if (max_centers < 0 || (count > 0 && (!status || !K || (max_centers > 0 && !centers_xy)))) return RDET_ERR_INVALID;
-    if (max_centers > RDET_MAX_CENTERS) max_centers = RDET_MAX_CENTERS;
-    b->outstanding = false;
-    DETB_TRY(b, hipSetDevice(b->device));
-    DETB_TRY(b, hipStreamSynchronize(b->stream));
-    for (int i = 0; i < count; ++i) {
-        const BatchOut &o = b->out.h[i];
-        K[i] = 0;
-        status[i] = b->sub_status[(size_t)i];
-        if (obs_time) obs_time[i] = b->sub_stamp[(size_t)i];
-        if (!b->sub_runs[(size_t)i]) continue;
-        b->m[(size_t)b->sub_member[(size_t)i]].last_n_returns = o.n_returns;
-        if (o.err) { status[i] = o.err; continue; }
-        if (o.K > max_centers) { status[i] = RDET_ERR_BUFFER; continue; }
-        K[i] = o.K;
-        if (o.K > 0) std::memcpy(centers_xy + (size_t)2 * (size_t)max_centers * (size_t)i, o.centers, sizeof(float2) * (size_t)o.K);
-    }
-    return RDET_OK;
+    if (!b) return RDET_ERR_INVALID;
+    return dev::collect(b, b->out.h, status, K, centers_xy, max_centers, obs_time, [&](int i, const BatchOut *o) {
+        if (o) b->m[(size_t)b->sub_member[(size_t)i]].last_n_returns = o->n_returns;
+    });
 }
 
 int rdet2d_batch_get_range_data(rdet2d_batch_t *b, int member, float origin_xy[2], float *returns_xy, int cap_points, int *n_returns)
 {
     if (!b || !n_returns || member < 0 || member >= b->B || b->outstanding) return RDET_ERR_INVALID;
-    const rdet2d_batch_member &M = b->m[(size_t)member];
+    const host::Member2d &M = b->m[(size_t)member];
     if (origin_xy) { origin_xy[0] = (float)M.s2b[0]; origin_xy[1] = (float)M.s2b[1]; }   // :243
     *n_returns = M.last_n_returns;
     if (returns_xy) {
@@ -886,7 +680,7 @@ int rdet2d_batch_get_range_data(rdet2d_batch_t *b, int member, float origin_xy[2
         if (M.last_n_returns > 0) {
             DETB_TRY(b, hipSetDevice(b->device));
             DETB_TRY(b, hipStreamSynchronize(b->stream));
-            DETB_TRY(b, hipMemcpy(returns_xy, b->d_returns + (size_t)member * (size_t)b->max_beams,
+            DETB_TRY(b, hipMemcpy(returns_xy, b->d_returns.d + (size_t)member * (size_t)b->max_beams,
                                   sizeof(float) * 2 * (size_t)M.last_n_returns, hipMemcpyDeviceToHost));
         }
     }
@@ -897,61 +691,28 @@ int rdet2d_batch_get_range_data_all(rdet2d_batch_t *b, const int *members, int c
                                     long cap_points)
 {
     if (!b || count < 0 || (count > 0 && !counts) || cap_points < 0 || b->outstanding) return RDET_ERR_INVALID;
-    const int B = b->B;
-    if (!members && count != B) return RDET_ERR_INVALID;
-    if (members) {
-        if (count > B) return RDET_ERR_INVALID;                            // (more than B members: one is listed twice)
-        bool bad = false;
-        for (int g = 0; g < count && !bad; ++g) {
-            const int m = members[g];
-            if (m < 0 || m >= B || b->seen[(size_t)m]) bad = true;
-            else b->seen[(size_t)m] = 1;
-        }
-        for (int g = 0; g < count; ++g)
-            if (members[g] >= 0 && members[g] < B) b->seen[(size_t)members[g]] = 0;
-        if (bad) return RDET_ERR_INVALID;
-    }
+    if (!host::members_named_once(members, count, b->B, b->seen)) return RDET_ERR_INVALID;
     if (count == 0) return RDET_OK;
-    const size_t mb = (size_t)b->max_beams;
-    long total = 0;
-    for (int g = 0; g < count; ++g) {
-        int n = b->m[(size_t)(members ? members[g] : g)].last_n_returns;
-        n = n < 0 ? 0 : (n > b->max_beams ? b->max_beams : n);             // (never true for a count k_det2d_batch wrote: keeps every access inside the buffers)
-        counts[g] = n;
-        total += n;
-    }
+    const long total = host::range_counts(members, count, b->max_beams, b->m, counts);
     if (returns_xy && cap_points < total) return RDET_ERR_BUFFER;
     if (origins_xy)
         for (int g = 0; g < count; ++g) {
-            const rdet2d_batch_member &M = b->m[(size_t)(members ? members[g] : g)];
+            const host::Member2d &M = b->m[(size_t)(members ? members[g] : g)];
             origins_xy[2 * g] = (float)M.s2b[0]; origins_xy[2 * g + 1] = (float)M.s2b[1];   // :243
         }
     if (!returns_xy || total == 0) return RDET_OK;
     DETB_TRY(b, hipSetDevice(b->device));
-    const size_t tiles = (mb + 1 + RDET2DB_RANGE_TILE - 1) / RDET2DB_RANGE_TILE;            // of a member with max_beams rows behind an odd offset
-    const size_t wgmap_off = (sizeof(RangeRec) * (size_t)B + 255) / 256 * 256;
-    if (!b->rd_out.h) DETB_TRY(b, b->rd_out.alloc(mb * (size_t)B));
-    if (!b->rd_tab.h) DETB_TRY(b, b->rd_tab.alloc(wgmap_off + sizeof(int2) * tiles * (size_t)B));
-    RangeRec *recs = reinterpret_cast<RangeRec *>(b->rd_tab.h);
-    int2 *wgmap = reinterpret_cast<int2 *>(b->rd_tab.h + wgmap_off);
-    int nrec = 0, nwg = 0;
-    long long at = 0;
-    for (int g = 0; g < count; ++g) {
-        if (counts[g] == 0) continue;
-        RangeRec &R = recs[nrec];
-        R.src_off = (long long)(members ? members[g] : g) * (long long)mb;
-        R.dst_off = at;
-        R.n = counts[g]; R.pad = 0;
-        const int slots = counts[g] + (int)(at & 1);
-        for (int t = 0; t * RDET2DB_RANGE_TILE < slots; ++t) wgmap[nwg++] = make_int2(nrec, t);
-        at += counts[g];
-        ++nrec;
-    }
+    const size_t wgmap_off = host::range_table_off(b->B);
+    if (!b->rd_out.h) DETB_TRY(b, b->rd_out.alloc((size_t)b->max_beams * (size_t)b->B));
+    if (!b->rd_tab.h) DETB_TRY(b, b->rd_tab.alloc(wgmap_off + sizeof(int2) * host::range_tiles(b->max_beams) * (size_t)b->B));
+    static_assert(sizeof(host::RangeTile) == sizeof(int2), "the kernel reads a workgroup's (record, tile) as an int2");
+    const int nwg = host::range_data_plan(members, counts, count, b->max_beams, reinterpret_cast<RangeRec *>(b->rd_tab.h),
+                                          reinterpret_cast<host::RangeTile *>(b->rd_tab.h + wgmap_off));
     __atomic_thread_fence(__ATOMIC_SEQ_CST);                  // the records and the table are written before the doorbell
     RangeBufs Rf;
     Rf.recs = reinterpret_cast<const RangeRec *>(b->rd_tab.dv);
     Rf.wgmap = reinterpret_cast<const int2 *>(b->rd_tab.dv + wgmap_off);
-    Rf.returns = b->d_returns; Rf.out = b->rd_out.dv;
+    Rf.returns = b->d_returns.d; Rf.out = b->rd_out.dv;
     hipLaunchKernelGGL(k_det2d_batch_range_data, dim3((unsigned)nwg), dim3(RDET2DB_RANGE_THREADS), 0, b->stream, Rf);
     DETB_TRY(b, hipGetLastError());
     DETB_TRY(b, hipStreamSynchronize(b->stream));

@@ -19,20 +19,16 @@
 // returns lie on one post, so the boxes are small), one wave takes one query with the candidates one per lane, tiles are opened nearest
 // first and only while their box is nearer than the query's current 31st distance (k3_knn's scheme on LDS).  The multiset of the 31
 // smallest distances is exact whatever the boxes are.
-#include "../../include/rdet.h"
-#include "batch_host.h"
-
-#include <hip/hip_runtime.h>
+//
+// Here: the kernel, the handle's buffers, the copies and the launch.  The host's rules that need no HIP call are det_batch_host.h's
+// (tested without a GPU), create / destroy / link / collect as both detector handles make them det_batch_dev.h's.
+#include "det_batch_dev.h"         // det_batch_host.h: Cloud3Rec and the host's rules
 
 #include <cmath>
-#include <cstddef>
 #include <cstdio>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
 
-#define RDET3DB_MAX_BRIGHT 5120
+namespace host = det_batch_host;
+namespace dev = det_batch_dev;
 
 namespace {
 
@@ -41,21 +37,12 @@ constexpr int KNN = MEAN_K + 1;
 constexpr double STD_MUL = 0.5;               // :46
 constexpr float TOL2 = (float)(0.2 * 0.2);    // :69 (FLANN radius search: squared distance < r^2)
 constexpr int MIN_SZ = 4, MAX_SZ = 160;       // :70-71
-constexpr int TILE = 64;                      // nodes per bounding box = candidates per step
+constexpr int TILE = det_batch_host::CLOUD_TILE;      // nodes per bounding box = candidates per step (64)
 constexpr int MAX_TILES = RDET3DB_MAX_BRIGHT / TILE;      // 80
 constexpr float BOX_MARGIN = 0.9999f;         // box distance^2 * margin < bound  <=>  "some point of the box may matter"
 constexpr int KNN_FEW = 6;                    // a step with at most this many admissible candidates inserts them one by one
 
-// One cloud of a call: an array of these, indexed by blockIdx.x, lies in pinned host memory.
-struct Cloud3Rec {
-    double intensity_min;
-    double stamp;
-    int member;                    // whose staging slice
-    int N;
-    int slot;                      // the cloud's index in the call: where its result goes
-    int pad;
-    float sx, sy, cs, sn;          // sensor_to_base_link as Rigid2f, cos / sin of its angle by the host's libm
-};
+using det_batch_host::Cloud3Rec;
 
 // What a cloud hands back, in pinned host memory: plain stores, published by the end of the kernel
 struct Cloud3Out {
@@ -454,50 +441,21 @@ __global__ __launch_bounds__(1024) void k_det3d_batch(Batch3Bufs B)
     if (tid == 0) { out->K = nacc; out->err = 0; out->M = M; out->pad = 0; }
 }
 
+constexpr size_t LDS_PER_NODE = 4 * sizeof(float) + sizeof(int);
+
 }  // namespace
 
 // =================================================================================================
-struct rdet3d_batch_member {
-    rdet3d_options opt;
-    double s2b[3];
-};
-
-struct rdet3d_batch {
-    int B = 0, max_points = 0, device = 0;
-    hipStream_t stream = nullptr;
-    std::vector<rdet3d_batch_member> m;
+// The handle
+struct rdet3d_batch : dev::Handle {
+    int max_points = 0;
+    std::vector<host::Member3d> m;
     // the staging area the host writes and the kernel reads in place: fine-grained DEVICE memory through the PCIe BAR where the platform
     // maps it, else pinned host memory (host_visible.h)
     batch_host::Staging<float> stage;  // [B][4 * max_points]
     batch_host::Pinned<Cloud3Rec> recs; // [B]
     batch_host::Pinned<Cloud3Out> out; // [B]
-    // the submit that has not been collected
-    bool outstanding = false;
-    int sub_count = 0;
-    std::vector<int> sub_runs;
-    std::vector<double> sub_stamp;
-    std::vector<char> seen;
-    // rdet3d_batch_link (include/rlink.h): member, host status (always 0) and record index of every entry of the outstanding submit;
-    // `ready`, recorded by link behind the launch, and `consumed`, recorded by the consumer: both made by the first link; a link of
-    // the outstanding submit was taken
-    std::vector<int> sub_member, sub_status, sub_record;
-    hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
-    bool link_taken = false;
-    std::string hip_error;
 };
-
-#define DET3B_TRY(h, expr)                                                          \
-    do {                                                                            \
-        hipError_t e_ = (expr);                                                     \
-        if (e_ != hipSuccess) {                                                     \
-            if (h) (h)->hip_error = std::string(#expr) + ": " + hipGetErrorString(e_); \
-            return RDET_ERR_HIP;                                                    \
-        }                                                                           \
-    } while (0)
-
-namespace {
-constexpr size_t LDS_PER_NODE = 4 * sizeof(float) + sizeof(int);
-}
 
 extern "C" {
 
@@ -511,26 +469,19 @@ int rdet3d_batch_create(const rdet3d_options *opts, const double *s2b_xyyaw, int
 {
     if (!opts || !s2b_xyyaw || !out || B < 1 || max_points < 1) return RDET_ERR_INVALID;
     *out = nullptr;
-    rdet3d_batch_t *b = new (std::nothrow) rdet3d_batch();
+    rdet3d_batch_t *b = dev::make<rdet3d_batch>(opts, s2b_xyyaw, B, device);
     if (!b) return RDET_ERR_INVALID;
-    b->B = B; b->max_points = max_points; b->device = device;
-    b->m.resize((size_t)B);
-    for (int i = 0; i < B; ++i) {
-        b->m[(size_t)i].opt = opts[i];
-        std::memcpy(b->m[(size_t)i].s2b, s2b_xyyaw + 3 * i, sizeof(double) * 3);
-    }
-    b->sub_runs.resize((size_t)B); b->sub_stamp.resize((size_t)B); b->seen.assign((size_t)B, 0);
-    b->sub_member.resize((size_t)B); b->sub_status.assign((size_t)B, RDET_OK); b->sub_record.resize((size_t)B);
+    b->max_points = max_points;
     const size_t np = (size_t)max_points, nB = (size_t)B;
     int rc = [&]() -> int {
-        DET3B_TRY(b, hipSetDevice(device));
-        DET3B_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-        DET3B_TRY(b, b->stage.alloc(4 * np * nB));
-        DET3B_TRY(b, b->recs.alloc(nB));
-        DET3B_TRY(b, b->out.alloc(nB));
+        DETB_TRY(b, hipSetDevice(device));
+        DETB_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        DETB_TRY(b, b->stage.alloc(4 * np * nB));
+        DETB_TRY(b, b->recs.alloc(nB));
+        DETB_TRY(b, b->out.alloc(nB));
         std::memset(b->out.h, 0, sizeof(Cloud3Out) * nB);
-        DET3B_TRY(b, hipFuncSetAttribute((const void *)k_det3d_batch, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(LDS_PER_NODE * RDET3DB_MAX_BRIGHT)));
+        DETB_TRY(b, hipFuncSetAttribute((const void *)k_det3d_batch, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)(LDS_PER_NODE * RDET3DB_MAX_BRIGHT)));
         return RDET_OK;
     }();
     if (rc != RDET_OK) { std::fprintf(stderr, "rdet3d_batch_create: %s\n", b->hip_error.c_str()); rdet3d_batch_destroy(b); return rc; }
@@ -541,21 +492,11 @@ int rdet3d_batch_create(const rdet3d_options *opts, const double *s2b_xyyaw, int
 void rdet3d_batch_destroy(rdet3d_batch_t *b)
 {
     if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->ev_consumed) { (void)hipEventSynchronize(b->ev_consumed); (void)hipEventDestroy(b->ev_consumed); }   // (a consumer may still read the records)
-    if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
-    b->stage.release(); b->recs.release(); b->out.release();
-    if (b->stream) (void)hipStreamDestroy(b->stream);
+    dev::destroy(b, b->stage, b->recs, b->out);
     delete b;
 }
 
-int rdet3d_batch_set_sensor_to_base_link(rdet3d_batch_t *b, int member, const double xyyaw[3])
-{
-    if (!b || !xyyaw || member < 0 || member >= b->B) return RDET_ERR_INVALID;
-    std::memcpy(b->m[(size_t)member].s2b, xyyaw, sizeof(double) * 3);
-    return RDET_OK;
-}
+int rdet3d_batch_set_sensor_to_base_link(rdet3d_batch_t *b, int member, const double xyyaw[3]) { return dev::set_sensor_to_base_link(b, member, xyyaw); }
 
 int rdet3d_batch_staging(rdet3d_batch_t *b, int member, float **xyzi)
 {
@@ -567,118 +508,41 @@ int rdet3d_batch_staging(rdet3d_batch_t *b, int member, float **xyzi)
 int rdet3d_batch_submit(rdet3d_batch_t *b, const rdet3d_cloud *clouds, int count)
 {
     if (!b || count < 0 || (count > 0 && !clouds) || b->outstanding) return RDET_ERR_INVALID;
-    // ---- validate the whole call: nothing changes before every cloud has passed
-    {
-        int rc = RDET_OK;
-        for (int i = 0; i < count && rc == RDET_OK; ++i) {
-            const rdet3d_cloud &c = clouds[i];
-            if (c.member < 0 || c.member >= b->B || b->seen[(size_t)c.member] || c.N < 0 || (c.N > 0 && !c.xyzi)) {
-                rc = RDET_ERR_INVALID;
-                break;
-            }
-            b->seen[(size_t)c.member] = 1;
-            if (c.N > b->max_points) rc = RDET_ERR_CAPACITY;
-        }
-        for (int i = 0; i < count; ++i)
-            if (clouds[i].member >= 0 && clouds[i].member < b->B) b->seen[(size_t)clouds[i].member] = 0;
-        if (rc != RDET_OK) return rc;
-    }
-    DET3B_TRY(b, hipSetDevice(b->device));
-    // a link of the submit before was taken: the consumer's reads of the records come first, on the stream.  Until then the host
-    // leaves the records alone too (what it would clear below is never read: collect looks at sub_runs first)
-    const bool linked = b->link_taken;
-    if (linked) DET3B_TRY(b, hipStreamWaitEvent(b->stream, b->ev_consumed, 0));
-    b->link_taken = false;
-    const size_t np = (size_t)b->max_points;
-    int n_run = 0, n_max = 0;
+    int rc = host::validate_clouds(clouds, count, b->B, b->max_points, b->seen);
+    bool linked = false;
+    if (rc == RDET_OK) rc = dev::begin_submit(b, &linked);
+    if (rc != RDET_OK) return rc;
+    int cap = 0;
+    const int n_run = host::pack_clouds(clouds, count, b->m, *b, b->recs.h, &cap);
     for (int i = 0; i < count; ++i) {
         const rdet3d_cloud &c = clouds[i];
-        const rdet3d_batch_member &M = b->m[(size_t)c.member];
-        b->sub_stamp[(size_t)i] = c.stamp;                                          // observation.time_ (:97)
-        b->sub_runs[(size_t)i] = 0;
-        b->sub_member[(size_t)i] = c.member;
         if (!linked) std::memset(&b->out.h[i], 0, 4 * sizeof(int));
-        if (c.N == 0) continue;                                                     // nothing to detect: no workgroup
-        b->sub_runs[(size_t)i] = 1;
-        Cloud3Rec &A = b->recs.h[n_run++];
-        std::memset(&A, 0, sizeof(A));
-        A.intensity_min = M.opt.intensity_min;
-        A.stamp = c.stamp;
-        A.member = c.member; A.N = c.N; A.slot = i;
-        A.sx = (float)M.s2b[0]; A.sy = (float)M.s2b[1];
-        const float sa = (float)M.s2b[2];
-        A.cs = cosf(sa); A.sn = sinf(sa);
-        if (c.N > n_max) n_max = c.N;
-        float *dst = b->stage.h + (size_t)c.member * 4 * np;                        // the cloud into the member's slice, unless it was received there
-        if (c.xyzi != dst) std::memcpy(dst, c.xyzi, sizeof(float) * 4 * (size_t)c.N);
+        float *dst = b->stage.h + (size_t)c.member * 4 * (size_t)b->max_points;     // the cloud into the member's slice, unless it was received there
+        if (c.N > 0 && c.xyzi != dst) std::memcpy(dst, c.xyzi, sizeof(float) * 4 * (size_t)c.N);
     }
-    b->sub_count = count;
     b->outstanding = true;
     if (n_run > 0) {
         __atomic_thread_fence(__ATOMIC_SEQ_CST);              // write-combined stores drained before the doorbell
         Batch3Bufs Bf;
         Bf.recs = b->recs.dv; Bf.stage = b->stage.dv; Bf.out = b->out.dv; Bf.max_points = b->max_points;
-        int cap = (n_max + TILE - 1) / TILE * TILE;           // no cloud of this call has more survivors than points
-        if (cap > RDET3DB_MAX_BRIGHT) cap = RDET3DB_MAX_BRIGHT;
         Bf.cap = cap;
         hipLaunchKernelGGL(k_det3d_batch, dim3((unsigned)n_run), dim3(1024), LDS_PER_NODE * (size_t)cap, b->stream, Bf);
-        DET3B_TRY(b, hipGetLastError());
+        DETB_TRY(b, hipGetLastError());
     }
     return RDET_OK;
 }
 
-int rdet3d_batch_link(rdet3d_batch_t *b, rlink *out)
-{
-    if (!b || !out || !b->outstanding) return RDET_ERR_INVALID;
-    DET3B_TRY(b, hipSetDevice(b->device));
-    if (!b->ev_ready) DET3B_TRY(b, hipEventCreateWithFlags(&b->ev_ready, hipEventDisableTiming));
-    if (!b->ev_consumed) DET3B_TRY(b, hipEventCreateWithFlags(&b->ev_consumed, hipEventDisableTiming));
-    DET3B_TRY(b, hipEventRecord(b->ev_ready, b->stream));
-    for (int i = 0; i < b->sub_count; ++i) b->sub_record[(size_t)i] = b->sub_runs[(size_t)i] ? i : -1;
-    std::memset(out, 0, sizeof(*out));
-    out->count = b->sub_count;
-    out->device = b->device;
-    out->member = b->sub_member.data();
-    out->stamp = b->sub_stamp.data();
-    out->host_status = b->sub_status.data();
-    out->record = b->sub_record.data();
-    out->records = b->out.dv;
-    out->record_bytes = (long)sizeof(Cloud3Out);
-    out->k_off = (int)offsetof(Cloud3Out, K);
-    out->err_off = (int)offsetof(Cloud3Out, err);
-    out->centers_off = (int)offsetof(Cloud3Out, centers);
-    out->max_centers = RDET_MAX_CENTERS;
-    out->ready = b->ev_ready;
-    out->consumed = b->ev_consumed;
-    b->link_taken = true;
-    return RDET_OK;
-}
+int rdet3d_batch_link(rdet3d_batch_t *b, rlink *out) { return b ? dev::link(b, b->out.dv, out) : RDET_ERR_INVALID; }
 
-int rdet_sizeof_link(void) { return (int)sizeof(rlink); }
+int rdet_sizeof_link(void) { return (int)sizeof(rlink); }     // (of both detectors' links: the library's one copy)
 
 int rdet3d_batch_collect(rdet3d_batch_t *b, int *status, int *K, float *centers_xy, int max_centers, double *obs_time, int *n_bright)
 {
-    if (!b || !b->outstanding) return RDET_ERR_INVALID;
-    const int count = b->sub_count;
-    if (max_centers < 0 || (count > 0 && (!status || !K || (max_centers > 0 && !centers_xy)))) return RDET_ERR_INVALID;
-    if (max_centers > RDET_MAX_CENTERS) max_centers = RDET_MAX_CENTERS;
-    b->outstanding = false;
-    DET3B_TRY(b, hipSetDevice(b->device));
-    DET3B_TRY(b, hipStreamSynchronize(b->stream));
-    for (int i = 0; i < count; ++i) {
-        const Cloud3Out &o = b->out.h[i];
-        K[i] = 0;
-        status[i] = RDET_OK;
-        if (obs_time) obs_time[i] = b->sub_stamp[(size_t)i];
-        if (n_bright) n_bright[i] = 0;
-        if (!b->sub_runs[(size_t)i]) continue;
-        if (n_bright) n_bright[i] = o.M;
-        if (o.err) { status[i] = o.err; continue; }
-        if (o.K > max_centers) { status[i] = RDET_ERR_BUFFER; continue; }
-        K[i] = o.K;
-        if (o.K > 0) std::memcpy(centers_xy + (size_t)2 * (size_t)max_centers * (size_t)i, o.centers, sizeof(float2) * (size_t)o.K);
-    }
-    return RDET_OK;
+    if (!b) return RDET_ERR_INVALID;
+    return dev::collect(b, b->out.h, status, K, centers_xy, max_centers, obs_time, [&](int i, const Cloud3Out *o) {
+        if (n_bright) n_bright[i] = o ? o->M : 0;
+    });
 }
 
 }  // extern "C"
+

@@ -33,7 +33,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-SOURCES = ["include/rdet.h", "reflector_ekf_slam_amd/csrc/det3d_batch.hip", "reflector_ekf_slam_amd/csrc/det3d.hip",
+SOURCES = ["include/rdet.h", "reflector_ekf_slam_amd/csrc/det3d_batch.hip", "reflector_ekf_slam_amd/csrc/det_batch_host.h", "reflector_ekf_slam_amd/csrc/det_batch_dev.h",
+           "reflector_ekf_slam_amd/csrc/det3d.hip",
            "reflector_ekf_slam_amd/fleet_detect.py", "reflector_ekf_slam_amd/detect.py", "scripts/fleet_detect3d_bench.py"]
 N_POSES = 16          # distinct poses (clouds); member b of tick k sees cloud (b + k) % N_POSES
 LEGS = ("batch", "staged", "handles")

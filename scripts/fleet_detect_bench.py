@@ -31,7 +31,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-SOURCES = ["include/rdet.h", "reflector_ekf_slam_amd/csrc/det2d_batch.hip", "reflector_ekf_slam_amd/csrc/det2d.hip",
+SOURCES = ["include/rdet.h", "reflector_ekf_slam_amd/csrc/det2d_batch.hip", "reflector_ekf_slam_amd/csrc/det_batch_host.h", "reflector_ekf_slam_amd/csrc/det_batch_dev.h",
+           "reflector_ekf_slam_amd/csrc/det2d.hip",
            "reflector_ekf_slam_amd/fleet_detect.py", "reflector_ekf_slam_amd/detect.py", "scripts/fleet_detect_bench.py"]
 N_POSES = 16          # distinct poses (scans); member b of tick k sees scan (b + k) % N_POSES
 N_BEAMS = 3600

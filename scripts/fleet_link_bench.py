@@ -32,7 +32,7 @@ for p in (ROOT, os.path.join(ROOT, "scripts")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-SOURCES = ["include/rlink.h", "include/rdet.h", "include/rfleet.h", "reflector_ekf_slam_amd/csrc/det2d_batch.hip",
+SOURCES = ["include/rlink.h", "include/rdet.h", "include/rfleet.h", "reflector_ekf_slam_amd/csrc/det2d_batch.hip", "reflector_ekf_slam_amd/csrc/det_batch_host.h", "reflector_ekf_slam_amd/csrc/det_batch_dev.h",
            "reflector_ekf_slam_amd/csrc/fleet_link.h", "reflector_ekf_slam_amd/csrc/fleet_link.hip", "reflector_ekf_slam_amd/csrc/fleet_host.h",
            "reflector_ekf_slam_amd/csrc/rfleet_api.hip", "reflector_ekf_slam_amd/fleet.py", "reflector_ekf_slam_amd/fleet_detect.py",
            "scripts/fleet_detect_bench.py", "scripts/fleet_link_bench.py"]

@@ -34,7 +34,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-SOURCES = ["include/rdet.h", "reflector_ekf_slam_amd/csrc/det2d_batch.hip", "reflector_ekf_slam_amd/fleet_detect.py",
+SOURCES = ["include/rdet.h", "reflector_ekf_slam_amd/csrc/det2d_batch.hip", "reflector_ekf_slam_amd/csrc/det_batch_host.h", "reflector_ekf_slam_amd/csrc/det_batch_dev.h",
+           "reflector_ekf_slam_amd/fleet_detect.py",
            "reflector_ekf_slam_amd/node_replay.py", "reflector_ekf_slam_amd/map_builder.py", "scripts/fleet_range_data_bench.py"]
 N_BEAMS = 3600
 N_POSES = 8

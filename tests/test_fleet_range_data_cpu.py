@@ -92,7 +92,7 @@ def test_a_scan_has_exactly_the_valid_beams_asked_for():
 
 def test_cases_cover_what_they_claim(oracle_lib):
     T = RC.TILE
-    src = open(os.path.join(ROOT, "reflector_ekf_slam_amd", "csrc", "det2d_batch.hip")).read()
+    src = open(os.path.join(ROOT, "reflector_ekf_slam_amd", "csrc", "det_batch_host.h")).read()
     threads = int(re.search(r"#define\s+RDET2DB_RANGE_THREADS\s+(\d+)", src).group(1))
     assert re.search(r"#define\s+RDET2DB_RANGE_TILE\s+\(2 \* RDET2DB_RANGE_THREADS\)", src) and 2 * threads == T
     E = RC.EDGE_COUNTS
